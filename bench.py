@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the OmniVGGT aggregator hot path on MI355X (contract: see the task prompt).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--views S] [--dtype bf16|f16|f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--views S] [--dtype bf16|f16|f32] [--dump-outputs DIR]
         (N > 1 without a launcher around it: the script starts its own N ranks -- self_launch -- and returns their exit code)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -28,6 +28,8 @@ At N=1 the same JSON line carries
                  block + one DINO block at the REAL 64-view shapes, extrapolated x24, plus a complete
                  2-view forward.
 --views S overrides the view count; --aux adds depth + camera tokens on every view (configs[2]).
+--dump-outputs DIR writes what the last timed step returned (a fixed, seeded sample of every layer's tokens, and
+patch_start_idx) as DIR/<name>.npy; the inputs and weights are seeded, so two builds can be compared output for output.
 
 N > 1 robustness: every rank runs a watchdog thread (--watchdog-s): a rank that makes no progress for that long dumps the
 stacks of all its threads to stderr, tagged with its rank and the stage it was in, rank 0 prints the JSON line with what has
@@ -239,7 +241,11 @@ def main():
                     help="abort (with thread stacks, rank-tagged, and a partial JSON line) after this many seconds without progress; 0 = off")
     ap.add_argument("--partial-aux", action="store_true", help="cameras on the even views, depth on the second half of the views "
                     "(BASELINE configs[4] with --views 128 --dtype f16)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                    "(every layer's tokens at a fixed, seeded sample of token rows, and patch_start_idx)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become the launcher of N ranks (one process per GPU) and hand back their verdict
@@ -329,8 +335,11 @@ def main():
         barrier()
         wd.stage("timed region: %d steps" % steps)
         t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
+        for i in range(steps):
+            if i + 1 < steps:
+                step()                                       # result dropped at once: the next step reuses its memory
+            else:
+                last = step()                                # what the last timed step returned (--dump-outputs)
             wd.stage("timed step queued", quiet=True)        # heartbeat only (no I/O inside the timed region)
         barrier()
         dt = time.perf_counter() - t0
@@ -338,13 +347,26 @@ def main():
         agg.disable_attention_events()
         fb = agg.read_fallback_counter() or 0
         dt, attn_ms, fb = reduce_max([dt, sum(ms), float(fb)])
-        return dt, attn_ms, sum(fl), len(ms), int(fb)
+        return dt, attn_ms, sum(fl), len(ms), int(fb), last
 
-    def measure(S, steps, warmup):
-        """Time `steps` aggregator forwards on S views; returns the result dict (rank-reduced)."""
+    def reduce_sum(t):
+        if dist is None:
+            return t
+        t = t.to(dev if args.backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t
+
+    def measure(S, steps, warmup, dump_dir=None):
+        """Time `steps` aggregator forwards on S views; returns the result dict (rank-reduced). With dump_dir, the outputs of the
+        last timed step are written there (dump_outputs) before anything else runs."""
         step = make_step(S)
         n_local = S // world + (1 if rank < S % world else 0)
-        dt, attn_ms, attn_flop, launches, fallbacks = timed_steps(step, steps, warmup)
+        dt, attn_ms, attn_flop, launches, fallbacks, last = timed_steps(step, steps, warmup)
+        if dump_dir is not None:
+            wd.stage("dump of the last timed step's outputs")
+            view0 = shard.last_partition[rank][0] if shard is not None else 0
+            result["dump_outputs"] = dump_outputs(dump_dir, last, S, view0, reduce_sum, rank == 0)
+        del last
         f_total, _ = agg_flops(S)
         achieved = attn_flop / (attn_ms * 1e-3) / 1e12 if attn_ms > 0 else 0.0
         peak = PEAK_TFLOPS[args.dtype]
@@ -436,7 +458,7 @@ def main():
             pre["primary_forced_to"] = "allgather"
         del step
     wd.stage("primary measurement: %d views" % S)
-    primary = measure(S, args.steps, args.warmup)
+    primary = measure(S, args.steps, args.warmup, dump_dir=args.dump_outputs)
     result.update({"value": primary["value"], "ms_per_step": primary["ms_per_step"]})
     result.update({k: primary[k] for k in ("config", "algorithmic_tflop_per_step", "tflops_per_gpu", "roofline")})
     if "comm" in primary:
@@ -535,6 +557,38 @@ def main():
         dist.destroy_process_group()
 
 
+DUMP_ROWS, DUMP_SEED, DUMP_MAX_BYTES = 256, 0, 64 << 20
+
+
+def dump_outputs(out_dir, last, S, view0, reduce_sum, write):
+    """Write what one aggregator forward returned, (tokens of every layer (1, S, 1374, 2048) f32, patch_start_idx), as .npy files that
+    two builds can compare output for output: tokens_layerNN.npy = the same DUMP_ROWS token rows of every layer (all 2048 channels),
+    rows drawn once by a seeded permutation of the S * 1374 (view, token) rows, so the files depend on S alone; patch_start_idx.npy
+    (float64 scalar). The forward may hold only views view0.. of the S (view sharding): each rank fills the sampled rows it holds,
+    the others stay 0, and reduce_sum (a sum over the ranks) assembles the full sample exactly. Returns the record for the JSON line."""
+    import numpy as np
+    outs, start = last
+    rows = S * P_TOK
+    pick = torch.randperm(rows, generator=torch.Generator().manual_seed(DUMP_SEED))[:DUMP_ROWS].sort().values
+    width = outs[0].shape[-1]
+    assert len(outs) * len(pick) * width * 4 <= DUMP_MAX_BYTES
+    arrays = {"patch_start_idx": np.array(start, dtype=np.float64)}
+    lo = view0 * P_TOK
+    for i, o in enumerate(outs):
+        flat = o.reshape(-1, width)
+        mine = (pick >= lo) & (pick < lo + flat.shape[0])
+        sample = torch.zeros(len(pick), width, dtype=torch.float32, device=o.device)
+        sample[mine.to(o.device)] = flat[(pick[mine] - lo).to(o.device)].float()
+        arrays["tokens_layer%02d" % i] = reduce_sum(sample).cpu().numpy()
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "sample": "tokens_layerNN = rows torch.randperm(%d, seed %d)[:%d] (sorted) of layer NN's tokens viewed as (S * 1374, 2048)"
+                      % (rows, DUMP_SEED, len(pick))}
+
+
 def parity_block(agg, dev, args, view_counts):
     """Cross-check of the TIMED 16-bit path against the f32 parity mode of the same library (itself <= 1e-4 of the
     reference CPU path: tests/test_gpu_aggregator.py) on the bench's own inputs and sizes. Per sampled layer:
@@ -610,37 +664,18 @@ def parity_block(agg, dev, args, view_counts):
 
 
 def _cpu_block_runners(sd):
-    """(kind, {name: callable(x, pos) -> tensor}) for one frame / global / DINOv2 block on the host.
-    kind "reference": the upstream modules themselves (omnivggt/layers/block.py:27 with layers/rope.py:62), imported from
-    /root/reference through oracle/ref_shim.py and loaded with the same weights -- possible in the build container only;
-    kind "port": the oracle restatement (bit-exact against those modules, tests/golden/oracle_vs_reference_report.json) --
-    what runs on the GPU box, where the reference tree does not exist."""
+    """(kind, {name: callable(x, pos) -> tensor}) for one frame / global / DINOv2 block on the host: kind "port", the oracle
+    restatement of the upstream modules (bit-exact against them, tests/golden/oracle_vs_reference_report.json)."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import aggregator_oracle as orc
-    import ref_shim
     rope = orc.rope_tables(38)
-    if ref_shim.available():
-        ref_shim.install()
-        from omnivggt.layers.block import Block
-        from omnivggt.layers.rope import RotaryPositionEmbedding2D
-
-        def make(prefix, qk_norm, with_rope, eps):
-            blk = Block(dim=1024, num_heads=16, mlp_ratio=4.0, init_values=0.01, qk_norm=qk_norm,
-                        rope=RotaryPositionEmbedding2D(frequency=100.0) if with_rope else None)
-            blk.norm1.eps = blk.norm2.eps = eps
-            blk.load_state_dict({k[len(prefix) + 1:]: v for k, v in sd.items() if k.startswith(prefix + ".")}, strict=True)
-            blk.eval()
-            return (lambda x, pos: blk(x, pos=pos)) if with_rope else (lambda x, pos: blk(x))
-        return "reference", {"frame": make("aggregator.frame_blocks.0", True, True, 1e-5),
-                             "global": make("aggregator.global_blocks.0", True, True, 1e-5),
-                             "dino": make("aggregator.patch_embed.blocks.0", False, False, 1e-6)}
     return "port", {"frame": lambda x, pos: orc.block(x, sd, "aggregator.frame_blocks.0", pos, rope, True),
                     "global": lambda x, pos: orc.block(x, sd, "aggregator.global_blocks.0", pos, rope, True),
                     "dino": lambda x, pos: orc.block(x, sd, "aggregator.patch_embed.blocks.0", None, None, False, eps=orc.DINO_LN_EPS)}
 
 
 def cpu_baseline(sd):
-    """The reference CPU path (its own modules where the reference tree exists, else the bit-exact oracle restatement) on the
+    """The reference CPU path (the bit-exact oracle restatement of its modules) on the
     host cores, one warm-up + one timed run of each piece:
     (1) headline config: ONE frame block, ONE global block and ONE DINOv2 block at the real 64-view shapes
         ((64,1374,1024) / (1,87936,1024)), extrapolated x24 each ("time ONE frame block + ONE global block
@@ -675,7 +710,7 @@ def cpu_baseline(sd):
         total = 24 * (t_frame + t_global + t_dino)
         inp = orc.synthetic_inputs(2)
         t2 = timed(lambda: orc.aggregator_forward(sd, inp["images"], inp["extrinsics"], inp["intrinsics"], inp["depth"], inp["mask"], [], []))
-    what = "the reference's own Block modules" if kind == "reference" else "oracle restatement of the reference (bit-exact against it)"
+    what = "oracle restatement of the reference (bit-exact against it)"
     return {"value": round(S / total, 5), "unit": "frames/s", "cores": cores, "host_cores": ncpu, "kind": kind, "extrapolated": True, "warmup": 1,
             "sample": "%s, fp32, torch CPU, %d threads of %d host cores, at the headline shapes (64 views 518^2), after one warm-up: one frame block "
                       "%.2f s, one global block %.2f s, one DINOv2 block %.2f s, extrapolated x24 each = %.0f s per forward"
