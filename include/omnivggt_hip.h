@@ -53,8 +53,9 @@ extern "C" {
  * 10: ovg_dpt_tail -- the output stage of the DPT head (upsample + position embedding + conv3x3 + ReLU + conv1x1 + activation) as one launch
  * 11: the lab GEMM selectors of ABI 9 (OVG_TILE_256P / OVG_TILE_DMA_M) are removed (OVG_E_ARG); the key-split tail of ABI 9 now also follows
  *     the 512-row attention launches (ovg_attn_plan_out: q_tile == tail_q_tile == 512, splits = key ranges of the tail rows, partials sized
- *     for the tail rows) when the caller passes a split workspace */
-#define OVG_ABI_VERSION 11
+ *     for the tail rows) when the caller passes a split workspace
+ * 12: + point-cloud extraction (ovg_percentile, ovg_point_filter and their *_workspace_bytes queries) */
+#define OVG_ABI_VERSION 12
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
        /* split-f16 ("f32x", the <= 1e-4 mode with throughput): a value x is stored as hi = f16(x) (saturated at +-65504) in the tensor the
@@ -495,6 +496,59 @@ typedef struct {
   int64_t S; int H; int W;
 } ovg_unproject_params;
 int ovg_unproject(const ovg_unproject_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Point-cloud extraction (ABI 12): the selection core of visual_util.py:113-236 (predictions_to_glb) on the device.
+ *
+ * ovg_percentile: numpy-2 percentile(..., method="linear") of f32 keys, bit for bit, for up to OVG_PCT_MAX_COLS strided columns and
+ * OVG_PCT_MAX_Q percentiles per column. Key i of column c is x[c * col_stride + i * stride], i < n; with `mask` (optional, [n] f32,
+ * contiguous) it is x * (mask[i] > 0.1f ? 1 : 0) evaluated literally (the reference's sky-mask rule, visual_util.py:187-188).
+ *   numpy's index rule runs in f32 (q = p / 100f, vi = f32(n - 1) * q; vi >= f32(n - 1) takes the maximum; lo = floor(vi),
+ *   hi = f32(lo + 1) clamped to n - 1 -- numpy itself raises there), NaN sorts last and makes the result NaN, and the lerp is numpy's
+ *   two-branch _lerp in f32 without contraction, so +-inf order statistics give numpy's values (NaN included).
+ *   Radix select on order-preserving u32 keys: three histogram passes (11 / 11 / 10 bits, per-workgroup LDS histograms flushed with
+ *   integer atomics -- exact, so deterministic), each followed by a one-workgroup pick of the bins holding the ranks; seven launches.
+ *   out [ncols][nq] f32 (device). norm_out (optional, requires nq == 2): || out[:, 1] - out[:, 0] || as numpy's np.linalg.norm
+ *   evaluates it for an f32 vector (f32 products summed in f64 left to right, rounded to f32, correctly rounded sqrt): the scene scale
+ *   of visual_util.py:231-236 when q = {5, 95} over the (M, 3) kept vertices (stride 3, col_stride 1, ncols 3).
+ *   ws: >= ovg_percentile_workspace_bytes(n, ncols) bytes, 16-byte aligned (returns -1 on bad arguments).
+ *   q must lie in [0, 100]; no host synchronisation, the result stays on the device.
+ *
+ * ovg_point_filter: keep = conf' >= *threshold && conf' > min_conf (threshold NULL: 0), conf' = conf with the mask rule above, and with
+ * flags OVG_PF_BLACK_BG: r + g + b >= 16, OVG_PF_WHITE_BG: !(r > 240 && g > 240 && b > 240) on the u8 colours
+ * u8(trunc(clamp(x * 255f, 0, 255))) (one f32 multiply; the clamp only matters outside [0, 1], NaN gives 0).
+ *   conf [n], mask [n] (optional) f32; images [n / hw][3][hw] f32 (NCHW, hw pixels per frame); points [n][3] f32.
+ *   stage OVG_PF_COUNT: keep mask + per-workgroup counts + their scan into ws, *out_count = M (int64, device);
+ *   stage OVG_PF_SCATTER: reads what COUNT left in ws and writes the kept pixels in pixel order: out_points [M][3] f32 (copies),
+ *   out_colors [M][3] u8, out_index [M] int64 (optional: index_base + pixel index), entries at positions >= capacity are dropped.
+ *   Both stages in one call need capacity >= M known in advance; the usual form is COUNT, read M, allocate, SCATTER with the same ws.
+ *   ws: >= ovg_point_filter_workspace_bytes(n) bytes (n keep bytes + two int64 per 4096 pixels), 16-byte aligned.
+ * ------------------------------------------------------------------ */
+#define OVG_PCT_MAX_COLS 4
+#define OVG_PCT_MAX_Q 4
+typedef struct {
+  const float* x; int64_t n; int64_t stride; int64_t col_stride; int32_t ncols;
+  int32_t nq; float q[OVG_PCT_MAX_Q];
+  const float* mask;
+  float* out; float* norm_out;
+  void* ws; int64_t ws_bytes;
+} ovg_percentile_params;
+int64_t ovg_percentile_workspace_bytes(int64_t n, int32_t ncols);
+int ovg_percentile(const ovg_percentile_params*, void* stream);
+
+enum { OVG_PF_BLACK_BG = 1, OVG_PF_WHITE_BG = 2 };
+enum { OVG_PF_COUNT = 1, OVG_PF_SCATTER = 2 };
+typedef struct {
+  const float* conf; const float* mask; const float* threshold; float min_conf; int32_t flags;
+  const float* images; int64_t hw;
+  const float* points; int64_t n;
+  int32_t stage; int32_t pad;
+  int64_t index_base; int64_t capacity;
+  float* out_points; uint8_t* out_colors; int64_t* out_index; int64_t* out_count;
+  void* ws; int64_t ws_bytes;
+} ovg_point_filter_params;
+int64_t ovg_point_filter_workspace_bytes(int64_t n);
+int ovg_point_filter(const ovg_point_filter_params*, void* stream);
 
 /* head-major -> token-major: x [heads, n_pad, 64] dtype -> y [n, heads*64] dtype (row stride ldy), the layout the
  * proj GEMM reads; used after the return all-to-all of the head-parallel sharded attention. */

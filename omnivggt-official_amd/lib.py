@@ -14,7 +14,7 @@ OVG_BF16, OVG_F16, OVG_F32, OVG_F16X2 = 0, 1, 2, 3
 EPI_STORE, EPI_GELU, EPI_RES, EPI_PATCH = 0, 1, 2, 3
 OVG_MAX_SEG = 8
 KV_TILE = 64
-ABI_VERSION = 11
+ABI_VERSION = 12
 TILE_AUTO, TILE_128, TILE_256 = 0, 1, 2
 ATTN_F32X_FAST_PV = 92                                         # ovg_attn_params.variant in the split-f16 mode (opt-in): PV without P_lo x V_hi, +16 % at 3e-5 .. 1e-4 instead of 1e-5 .. 5e-5
 TILE_R02_EPILOGUE, TILE_128X, TILE_256X = 16, 17, 18      # A/B flag (r02 epilogue forms) OR-ed onto a tile selector
@@ -180,6 +180,22 @@ class CameraTablesParams(C.Structure):
                 ("pose_w", vp), ("pose_b", vp), ("adapt_w", vp), ("adapt_b", vp), ("enc", vp), ("emb", vp), ("tables", vp)]
 
 
+PCT_MAX_COLS, PCT_MAX_Q = 4, 4
+PF_BLACK_BG, PF_WHITE_BG = 1, 2
+PF_COUNT, PF_SCATTER = 1, 2
+
+
+class PercentileParams(C.Structure):
+    _fields_ = [("x", vp), ("n", i64), ("stride", i64), ("col_stride", i64), ("ncols", i32), ("nq", i32), ("q", f32 * PCT_MAX_Q),
+                ("mask", vp), ("out", vp), ("norm_out", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
+class PointFilterParams(C.Structure):
+    _fields_ = [("conf", vp), ("mask", vp), ("threshold", vp), ("min_conf", f32), ("flags", i32), ("images", vp), ("hw", i64),
+                ("points", vp), ("n", i64), ("stage", i32), ("pad", i32), ("index_base", i64), ("capacity", i64),
+                ("out_points", vp), ("out_colors", vp), ("out_index", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 # every entry point of include/omnivggt_hip.h: name -> (restype, argtypes)
 SYMBOLS = {
     "ovg_abi_version": (i32, []),
@@ -211,6 +227,10 @@ SYMBOLS = {
     "ovg_camera_head": (i32, [C.POINTER(CameraHeadParams), vp]),
     "ovg_camera_head_workspace_bytes": (i64, [i32, i32]),
     "ovg_camera_tables": (i32, [C.POINTER(CameraTablesParams), vp]),
+    "ovg_percentile": (i32, [C.POINTER(PercentileParams), vp]),
+    "ovg_percentile_workspace_bytes": (i64, [i64, i32]),
+    "ovg_point_filter": (i32, [C.POINTER(PointFilterParams), vp]),
+    "ovg_point_filter_workspace_bytes": (i64, [i64]),
 }
 
 

@@ -526,3 +526,71 @@ def unproject(depth, cam):
     p = L.UnprojectParams(L.ptr(depth), L.ptr(cam), L.ptr(out), S, H, W)
     L.call("ovg_unproject", p, _stream())
     return out
+
+
+def percentile_workspace_bytes(n, ncols):
+    b = L.load().ovg_percentile_workspace_bytes(int(n), int(ncols))
+    if b < 0:
+        raise L.OvgError("ovg_percentile_workspace_bytes: unsupported (n=%d, ncols=%d)" % (n, ncols))
+    return int(b)
+
+
+def percentile(x, n, stride, col_stride, ncols, qs, mask=None, norm=False, ws=None):
+    """numpy-2 linear percentiles `qs` (<= 4, in [0, 100]) of `ncols` (<= 4) f32 columns of x: key i of column c at element
+    c * col_stride + i * stride (element offsets from x's data pointer). mask: optional contiguous f32 [n] (key * (mask > 0.1)).
+    -> out [ncols, len(qs)] f32 on the device (and, with norm=True and two percentiles, the 0-d f32 norm of out[:, 1] - out[:, 0])."""
+    _chk_dev(x, mask, ws)
+    if x.dtype != torch.float32 or (mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous())):
+        raise L.OvgError("percentile: x must be f32 and mask a contiguous f32 tensor")
+    last = (ncols - 1) * col_stride + (n - 1) * stride
+    if n < 1 or stride < 1 or col_stride < 0 or x.storage_offset() + last >= x.untyped_storage().nbytes() // 4 or \
+            (mask is not None and mask.numel() < n):
+        raise L.OvgError("percentile: the strided columns (or the mask) reach outside the tensor")
+    need = percentile_workspace_bytes(n, ncols)
+    if ws is None or nbytes(ws) < need:
+        ws = torch.empty(need, device=x.device, dtype=torch.uint8)
+    out = torch.empty(ncols, len(qs), device=x.device, dtype=torch.float32)
+    nrm = torch.empty((), device=x.device, dtype=torch.float32) if norm else None
+    p = L.PercentileParams()
+    p.x, p.n, p.stride, p.col_stride, p.ncols, p.nq = L.ptr(x), int(n), int(stride), int(col_stride), int(ncols), len(qs)
+    for j, q in enumerate(qs[:L.PCT_MAX_Q]):
+        p.q[j] = float(q)
+    p.mask, p.out, p.norm_out, p.ws, p.ws_bytes = L.ptr(mask), L.ptr(out), L.ptr(nrm), L.ptr(ws), nbytes(ws)
+    L.call("ovg_percentile", p, _stream())
+    return (out, nrm) if norm else out
+
+
+def point_filter_workspace_bytes(n):
+    b = L.load().ovg_point_filter_workspace_bytes(int(n))
+    if b < 0:
+        raise L.OvgError("ovg_point_filter_workspace_bytes: unsupported (n=%d)" % n)
+    return int(b)
+
+
+def point_filter(stage, conf, images, points, hw, ws, threshold=None, mask=None, min_conf=1e-5, flags=0, index_base=0,
+                 out_count=None, capacity=0, out_points=None, out_colors=None, out_index=None):
+    """ovg_point_filter on contiguous device tensors: conf f32 [n], images f32 NCHW [n / hw, 3, hw], points f32 [n, 3], threshold a
+    0-d / 1-element f32 device tensor or None (0), mask f32 [n] or None. stage L.PF_COUNT writes the int64 cloud size to out_count;
+    L.PF_SCATTER writes the first `capacity` kept pixels (in pixel order) to out_points / out_colors / out_index from what the COUNT
+    stage left in ws."""
+    _chk_dev(conf, images, points, ws, threshold, mask, out_count, out_points, out_colors, out_index)
+    for t in (conf, images, points, threshold, mask):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise L.OvgError("point_filter: conf / images / points / threshold / mask must be contiguous f32 tensors")
+    n = conf.numel()
+    if images.numel() != 3 * n or points.numel() != 3 * n or (mask is not None and mask.numel() != n) or hw <= 0 or n % hw:
+        raise L.OvgError("point_filter: images / points must hold 3 values per pixel, mask one, and hw divide the pixel count")
+    if stage & L.PF_SCATTER:
+        outs = ((out_points, torch.float32, 3), (out_colors, torch.uint8, 3), (out_index, torch.int64, 1))
+        for t, dt, k in outs:
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < k * capacity):
+                raise L.OvgError("point_filter: output buffers must be contiguous and hold `capacity` entries")
+    if out_count is not None and (out_count.dtype != torch.int64 or out_count.numel() < 1):
+        raise L.OvgError("point_filter: out_count must be an int64 device tensor")
+    p = L.PointFilterParams()
+    p.conf, p.mask, p.threshold, p.min_conf, p.flags = L.ptr(conf), L.ptr(mask), L.ptr(threshold), float(min_conf), int(flags)
+    p.images, p.hw, p.points, p.n, p.stage = L.ptr(images), int(hw), L.ptr(points), n, int(stage)
+    p.index_base, p.capacity = int(index_base), int(capacity)
+    p.out_points, p.out_colors, p.out_index, p.out_count = L.ptr(out_points), L.ptr(out_colors), L.ptr(out_index), L.ptr(out_count)
+    p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
+    L.call("ovg_point_filter", p, _stream())

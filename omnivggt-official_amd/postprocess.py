@@ -42,3 +42,257 @@ def unproject_depth_map_to_point_map(depth_map, extrinsics_cam, intrinsics_cam, 
     c = -torch.bmm(Rt, ext[:, :, 3:])                                        # camera centre in the world
     cam = torch.cat([Rt.reshape(S, 9), c.reshape(S, 3), intr[:, 0, 0:1], intr[:, 1, 1:2], intr[:, 0, 2:3], intr[:, 1, 2:3]], dim=1)
     return ops.unproject(d, cam.contiguous())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Point-cloud extraction and export (visual_util.py:42-73, :77-267, inference.py:368-384)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+def percentile(x, q, dim=None):
+    """numpy-2 `percentile(x, q, axis=dim, method="linear")` of a float32 HIP device tensor of any size, bit for bit (ovg_percentile;
+    the supported answer where torch.quantile refuses inputs above 2^24 elements). q: a scalar or a 1-D sequence of percentiles in
+    [0, 100]; dim None reduces over all elements, an int over that dimension. The result is a device tensor shaped like numpy's:
+    q's axis first (for 1-D q), then the remaining dimensions. A NaN anywhere in a reduced slice makes that slice's result NaN."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ops.L.OvgError("percentile needs a HIP device tensor: there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise ValueError("percentile: x must be float32 (numpy's rule depends on the dtype)")
+    scalar = not isinstance(q, (list, tuple, torch.Tensor)) and not hasattr(q, "__len__")
+    qs = [float(q)] if scalar else [float(v) for v in (q.tolist() if isinstance(q, torch.Tensor) else q)]
+    if not qs or any(not (0.0 <= v <= 100.0) for v in qs):
+        raise ValueError("percentiles must be in the range [0, 100]")
+    if dim is None:
+        cols, rest = x.reshape(-1, 1), ()
+    else:
+        xm = x.movedim(dim, 0)
+        rest = tuple(xm.shape[1:])
+        cols = xm.reshape(xm.shape[0], -1)
+    if cols.shape[0] == 0:
+        raise ValueError("percentile of an empty reduction")
+    n, C = cols.shape
+    out = torch.empty(len(qs), C, device=x.device, dtype=torch.float32)
+    ws = None
+    for c0 in range(0, C, ops.L.PCT_MAX_COLS):
+        nc = min(ops.L.PCT_MAX_COLS, C - c0)
+        view = cols[:, c0:c0 + nc]
+        if ws is None:
+            ws = torch.empty(ops.percentile_workspace_bytes(n, ops.L.PCT_MAX_COLS), device=x.device, dtype=torch.uint8)
+        for j0 in range(0, len(qs), ops.L.PCT_MAX_Q):
+            qq = qs[j0:j0 + ops.L.PCT_MAX_Q]
+            r = ops.percentile(view, n, view.stride(0), view.stride(1) if nc > 1 else 0, nc, qq, ws=ws)
+            out[j0:j0 + len(qq), c0:c0 + nc] = r.t()
+    out = out.reshape((len(qs),) + rest)
+    return out[0] if scalar else out
+
+
+def get_world_points_from_depth(predictions, gt_scale=1):
+    """Device analogue of visual_util.py:42-73: adds `extrinsic` (B,S,3,4), `intrinsic` (B,S,3,3) and `world_points_from_depth`
+    (B,S,H,W,3) f32 to the prediction dict as OmniVGGT.forward returns it (batch dimension kept, tensors stay on the device; the
+    reference squeezes the batch and converts every entry to numpy). Returns the dict."""
+    depth = predictions["depth"]
+    if not depth.is_cuda:
+        raise ops.L.OvgError("get_world_points_from_depth needs HIP device tensors: there is no CPU fallback")
+    extrinsic, intrinsic = pose_encoding_to_extri_intri(predictions["pose_enc"], predictions["images"].shape[-2:])
+    predictions["extrinsic"] = extrinsic
+    predictions["intrinsic"] = intrinsic
+    d = depth * gt_scale if gt_scale != 1 else depth
+    predictions["world_points_from_depth"] = torch.stack(
+        [unproject_depth_map_to_point_map(d[b], extrinsic[b], intrinsic[b], check_skew=False) for b in range(d.shape[0])])
+    return predictions
+
+
+class PointCloud:
+    """Result of predictions_to_point_cloud. points (M,3) f32, colors (M,3) u8 and indices (M,) int64 (flat pixel index into the
+    batch element's S x H x W maps, or None) are device tensors; conf_threshold (the f32 percentile, 0 when conf_thres == 0) and
+    scene_scale (f32) are 0-d device tensors; transform is the (4,4) float64 numpy alignment; extrinsic (S',3,4) the selected
+    frames' cameras on the device."""
+    __slots__ = ("points", "colors", "conf_threshold", "scene_scale", "transform", "extrinsic", "indices")
+
+    def __init__(self, points, colors, conf_threshold, scene_scale, transform, extrinsic, indices=None):
+        self.points, self.colors, self.conf_threshold, self.scene_scale = points, colors, conf_threshold, scene_scale
+        self.transform, self.extrinsic, self.indices = transform, extrinsic, indices
+
+    def __len__(self):
+        return int(self.points.shape[0])
+
+
+def _parse_frame(filter_by_frames):
+    if filter_by_frames in ("all", "All"):
+        return None
+    try:
+        return int(filter_by_frames.split(":")[0])
+    except (ValueError, IndexError, AttributeError):
+        return None
+
+
+def scene_alignment(extrinsic0):
+    """inv(E0) @ diag(1,-1,-1,1) @ R_y(180 deg) in float64 (visual_util.py:320-358); E0 the (3,4) camera-from-world of the first frame."""
+    import numpy as np
+    e = np.eye(4)
+    e[:3, :4] = np.asarray(extrinsic0, dtype=np.float64)
+    return np.linalg.inv(e) @ np.diag([1.0, -1.0, -1.0, 1.0]) @ np.diag([-1.0, 1.0, -1.0, 1.0])
+
+
+def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="all", mask_black_bg=False, mask_white_bg=False,
+                               prediction_mode="Predicted Pointmap", sky_mask=None, min_conf=1e-5, batch_index=0, return_indices=False):
+    """The point cloud of visual_util.predictions_to_glb (:77-267) on the device, for the dict OmniVGGT.forward returns (batch dimension
+    included; batch_index=0 is what the reference's select_first_batch keeps).
+
+    Same choices as the reference: "Pointmap" modes take world_points / world_points_conf (world_points_from_depth / depth_conf when
+    the dict has no world_points), other modes world_points_from_depth / depth_conf, computed here on the device when absent; a missing
+    confidence map is all ones. filter_by_frames "k: ..." keeps frame k, anything unparsable keeps all frames. conf_thres None means
+    10, 0 skips the percentile. The threshold is numpy's linear percentile of the (sky-masked) confidences of the selected frames, bit
+    for bit; a pixel is kept when conf >= threshold and conf > min_conf (f32), and, on request, when its u8 colour is not black
+    (r+g+b < 16) or white (all channels > 240). Colours are trunc(x * 255) of the f32 image, clamped to [0, 255] (the clamp only
+    matters for inputs outside [0, 1]). sky_mask: a user-supplied (S, H, W) tensor at the map size; the confidence is multiplied by
+    (sky_mask > 0.1) before the frame filter, as in the reference (mask resizing and the ONNX sky model are not part of this).
+    scene_scale is ||P95 - P5|| of the kept, untransformed vertices; transform is inv(E0) @ diag(1,-1,-1,1) @ R_y(180) with E0 the
+    first selected camera, which the writers apply (the vertices themselves are copied untransformed).
+
+    One divergence: an empty selection returns M = 0 (scene_scale 1); the reference substitutes one white point at (1, 0, 0).
+    Exactly one device -> host synchronisation: reading M (with the first selected camera) to size the result. CPU tensors raise
+    OvgError: there is no CPU fallback."""
+    L = ops.L
+    if not isinstance(predictions, dict):
+        raise ValueError("predictions must be a dictionary")
+    images = predictions["images"]
+    if images.dim() == 4:
+        images = images.unsqueeze(0)
+    B = images.shape[0]
+    if not isinstance(batch_index, int) or not 0 <= batch_index < B:
+        raise ValueError("batch_index %r out of range for a batch of %d" % (batch_index, B))
+    if conf_thres is None:
+        conf_thres = 10.0
+    b = batch_index
+    S, H, W = images.shape[1], images.shape[-2], images.shape[-1]
+    if sky_mask is not None and tuple(sky_mask.shape) != (S, H, W):
+        raise ValueError("sky_mask must be (S, H, W) = %r at the map size, got %r" % ((S, H, W), tuple(sky_mask.shape)))
+    if not images.is_cuda:
+        raise L.OvgError("predictions_to_point_cloud needs HIP device tensors: there is no CPU fallback")
+    extrinsic = predictions["extrinsic"][b] if "extrinsic" in predictions else None
+    if "Pointmap" in prediction_mode and "world_points" in predictions:
+        pts, conf = predictions["world_points"][b], predictions.get("world_points_conf")
+    elif "world_points_from_depth" in predictions:
+        pts, conf = predictions["world_points_from_depth"][b], predictions.get("depth_conf")
+    else:
+        sub = {"depth": predictions["depth"][b:b + 1], "pose_enc": predictions["pose_enc"][b:b + 1], "images": images[b:b + 1]}
+        get_world_points_from_depth(sub)
+        pts, conf = sub["world_points_from_depth"][0], predictions.get("depth_conf")
+        if extrinsic is None:
+            extrinsic = sub["extrinsic"][0]
+    if extrinsic is None:
+        if "pose_enc" not in predictions:
+            raise ValueError("predictions carry neither `extrinsic` nor `pose_enc`: the scene alignment needs the cameras")
+        extrinsic = pose_encoding_to_extri_intri(predictions["pose_enc"][b:b + 1], (H, W))[0][0]
+    conf = torch.ones(S, H, W, device=images.device, dtype=torch.float32) if conf is None else conf[b]
+    for t in (pts, conf, extrinsic):
+        if not t.is_cuda:
+            raise L.OvgError("predictions_to_point_cloud needs HIP device tensors: there is no CPU fallback")
+    pts = pts.reshape(S, H, W, 3).float().contiguous()
+    conf = conf.reshape(S, H, W).float().contiguous()
+    img = images[b].reshape(S, 3, H, W).float().contiguous()
+    mask = None
+    if sky_mask is not None:
+        mask = sky_mask.to(device=images.device, dtype=torch.float32).contiguous()
+    frame = _parse_frame(filter_by_frames)
+    base = 0
+    if frame is not None:
+        if not -S <= frame < S:
+            raise ValueError("filter_by_frames selects frame %d of %d" % (frame, S))
+        frame %= S
+        sl = slice(frame, frame + 1)
+        pts, conf, img, extrinsic = pts[sl], conf[sl], img[sl], extrinsic[sl]
+        mask = None if mask is None else mask[sl]
+        base = frame * H * W
+    n, hw = conf.numel(), H * W
+    dev = conf.device
+    cf = conf.reshape(-1)
+    mk = None if mask is None else mask.reshape(-1)
+    if conf_thres == 0.0:
+        thr = None
+        conf_threshold = torch.zeros((), device=dev, dtype=torch.float32)
+    else:
+        thr = ops.percentile(cf, n, 1, 0, 1, [float(conf_thres)], mask=mk).reshape(1)
+        conf_threshold = thr.reshape(())
+    flags = (L.PF_BLACK_BG if mask_black_bg else 0) | (L.PF_WHITE_BG if mask_white_bg else 0)
+    ws = torch.empty(ops.point_filter_workspace_bytes(n), device=dev, dtype=torch.uint8)
+    count = torch.empty(1, device=dev, dtype=torch.int64)
+    args = dict(conf=cf, images=img, points=pts, hw=hw, ws=ws, threshold=thr, mask=mk, min_conf=min_conf, flags=flags, index_base=base)
+    ops.point_filter(L.PF_COUNT, out_count=count, **args)
+    # the one synchronisation: the cloud size and the first selected camera in one copy (int64 counts are exact in float64 below 2^53)
+    host = torch.cat([count.double(), extrinsic[0].reshape(-1).double()]).cpu().numpy()
+    M = int(host[0])
+    transform = scene_alignment(host[1:13].reshape(3, 4))
+    out_pts = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    out_col = torch.empty(M, 3, device=dev, dtype=torch.uint8)
+    out_idx = torch.empty(M, device=dev, dtype=torch.int64) if return_indices else None
+    if M:
+        ops.point_filter(L.PF_SCATTER, capacity=M, out_points=out_pts, out_colors=out_col, out_index=out_idx, **args)
+        _, scale = ops.percentile(out_pts, M, 3, 1, 3, [5.0, 95.0], norm=True)
+    else:
+        scale = torch.ones((), device=dev, dtype=torch.float32)
+    return PointCloud(out_pts, out_col, conf_threshold, scale, transform, extrinsic, out_idx)
+
+
+def _host_cloud(cloud):
+    import numpy as np
+    pts = cloud.points.detach().cpu().numpy().astype(np.float32).reshape(-1, 3)
+    col = cloud.colors.detach().cpu().numpy().astype(np.uint8).reshape(-1, 3)
+    return pts, col
+
+
+def write_ply(path, cloud, apply_transform=True):
+    """Binary little-endian PLY of the cloud: `x y z` float, `red green blue` uchar per vertex. apply_transform: the vertices are
+    mapped by cloud.transform in float64 on the host and stored as float32 (as the aligned scene shows them); False stores them as
+    selected. An empty cloud (M = 0) writes a valid file with no vertices."""
+    import numpy as np
+    pts, col = _host_cloud(cloud)
+    if apply_transform and len(pts):
+        T = np.asarray(cloud.transform, dtype=np.float64)
+        pts = (pts.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+    rec = np.empty(len(pts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(pts))
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(rec.tobytes())
+
+
+def write_glb(path, cloud):
+    """glTF 2.0 binary of the cloud: one POINTS primitive with POSITION (f32 VEC3, with the min / max the spec requires) and COLOR_0
+    (normalized u8 VEC4, alpha 255), under one node whose `matrix` is cloud.transform (column-major, as glTF stores it). The vertices
+    stay untransformed, as in the reference's file: trimesh's Scene.apply_transform moves the scene graph, not the vertex buffer. This
+    follows the reference file's structure; it was not compared byte-wise with trimesh's export (trimesh is not a dependency here).
+    An empty cloud writes a node without a mesh."""
+    import json
+    import struct
+    import numpy as np
+    pts, col = _host_cloud(cloud)
+    M = len(pts)
+    node = {"matrix": [float(v) for v in np.asarray(cloud.transform, dtype=np.float64).T.reshape(-1)]}
+    gltf = {"asset": {"version": "2.0", "generator": "omnivggt_official_amd.postprocess"}, "scene": 0, "scenes": [{"nodes": [0]}],
+            "nodes": [node]}
+    binary = b""
+    if M:
+        rgba = np.concatenate([col, np.full((M, 1), 255, np.uint8)], axis=1)
+        pos_bytes, col_bytes = pts.astype("<f4").tobytes(), rgba.tobytes()
+        binary = pos_bytes + col_bytes
+        node["mesh"] = 0
+        gltf["meshes"] = [{"primitives": [{"attributes": {"POSITION": 0, "COLOR_0": 1}, "mode": 0}]}]
+        gltf["buffers"] = [{"byteLength": len(binary)}]
+        gltf["bufferViews"] = [{"buffer": 0, "byteOffset": 0, "byteLength": len(pos_bytes), "target": 34962},
+                               {"buffer": 0, "byteOffset": len(pos_bytes), "byteLength": len(col_bytes), "target": 34962}]
+        gltf["accessors"] = [{"bufferView": 0, "componentType": 5126, "count": M, "type": "VEC3",
+                              "min": [float(v) for v in pts.min(axis=0)], "max": [float(v) for v in pts.max(axis=0)]},
+                             {"bufferView": 1, "componentType": 5121, "normalized": True, "count": M, "type": "VEC4"}]
+    js = json.dumps(gltf, separators=(",", ":")).encode("utf-8")
+    js += b" " * (-len(js) % 4)
+    binary += b"\0" * (-len(binary) % 4)
+    chunks = struct.pack("<II", len(js), 0x4E4F534A) + js
+    if binary:
+        chunks += struct.pack("<II", len(binary), 0x004E4942) + binary
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<III", 0x46546C67, 2, 12 + len(chunks)))
+        fh.write(chunks)
