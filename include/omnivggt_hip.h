@@ -54,8 +54,9 @@ extern "C" {
  * 11: the lab GEMM selectors of ABI 9 (OVG_TILE_256P / OVG_TILE_DMA_M) are removed (OVG_E_ARG); the key-split tail of ABI 9 now also follows
  *     the 512-row attention launches (ovg_attn_plan_out: q_tile == tail_q_tile == 512, splits = key ranges of the tail rows, partials sized
  *     for the tail rows) when the caller passes a split workspace
- * 12: + point-cloud extraction (ovg_percentile, ovg_point_filter and their *_workspace_bytes queries) */
-#define OVG_ABI_VERSION 12
+ * 12: + point-cloud extraction (ovg_percentile, ovg_point_filter and their *_workspace_bytes queries)
+ * 13: + input preprocessing (ovg_resample_frames, ovg_depth_frames, ovg_resample_workspace_bytes) */
+#define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
        /* split-f16 ("f32x", the <= 1e-4 mode with throughput): a value x is stored as hi = f16(x) (saturated at +-65504) in the tensor the
@@ -549,6 +550,63 @@ typedef struct {
 } ovg_point_filter_params;
 int64_t ovg_point_filter_workspace_bytes(int64_t n);
 int ovg_point_filter(const ovg_point_filter_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do
+ * after PIL's convert("RGB"), for all frames of a call in one launch per pass.
+ *
+ * ovg_resample_frames: Pillow's 8-bit BICUBIC resize (Image.resize, a = -0.5, 22 fractional bits), then a vertical crop, placement
+ * in a canvas and, for OVG_RS_F32_CHW, ToTensor (lut[u8]) into f32 CHW planes with the canvas outside the content set to 1.0f.
+ *   src: packed RGB u8 HWC frames (3 bytes per pixel, rows of 3 * src_w bytes); frame f starts at src + frames[f].src_off.
+ *   coef: int32 tables built on the host per (in, out) axis pair. At bounds_off: out pairs (first input index, tap count);
+ *   at k_off: out rows of ksize fixed-point weights (Pillow's normalize_coeffs_8bpc). Output pixel i of a pass is
+ *   clamp((2^21 + sum_j in[first + j] * k[i][j]) >> 22, 0, 255) in int32 over its tap count.
+ *   Horizontal pass (only when h_k_off >= 0): source rows [mid_row0, mid_row0 + mid_rows) -> u8 rows of res_w pixels in ws at
+ *   mid_off; the vertical pass then reads those rows (first index - mid_row0), else the source rows directly (src_w == res_w).
+ *   Vertical pass: resized rows crop_y .. crop_y + out_h - 1 (a pass that keeps the height uses identity weights: the copy Pillow
+ *   makes) -> canvas rows pad_top .., columns pad_left .. pad_left + res_w - 1.
+ *   out (OVG_RS_F32_CHW): f32 [3][canvas_h][canvas_w] at out + canvas_off elements; (OVG_RS_U8_HWC): u8 [canvas_h][canvas_w][3].
+ *   frames / coef: device copies; frames_host / coef_host: the same bytes on the host, validated before any HIP call (every read
+ *   and write of the kernels stays inside src_bytes / coef_len / ws_bytes / out_elems, or the call returns OVG_E_ARG).
+ * ovg_resample_workspace_bytes: bytes of ws the frames need (max of mid_off + 3 * mid_rows * res_w), -1 on bad arguments.
+ *
+ * ovg_depth_frames: the depth half of visual_util.py:763-801: d = src (non-finite -> 0, then > max_depth -> 0, then < 1e-5f -> 0),
+ * gathered at rows index[rows_off + y] and columns index[cols_off + x] (cv2 INTER_NEAREST + the crop, computed on the host), written
+ * to depth[out_off + y * out_w + x] and mask = d > 1e-5f ? 1 : 0 at the same offset. Frames not listed are left untouched.
+ * ------------------------------------------------------------------ */
+enum { OVG_RS_F32_CHW = 0, OVG_RS_U8_HWC = 1 };
+typedef struct {
+  int64_t src_off; int32_t src_w; int32_t src_h;
+  int32_t res_w; int32_t res_h; int32_t crop_y; int32_t out_h;
+  int32_t mid_row0; int32_t mid_rows; int64_t mid_off;
+  int32_t h_bounds_off; int32_t h_k_off; int32_t h_ksize;
+  int32_t v_bounds_off; int32_t v_k_off; int32_t v_ksize;
+  int32_t canvas_w; int32_t canvas_h; int32_t pad_top; int32_t pad_left;
+  int64_t canvas_off;
+} ovg_resample_frame;
+typedef struct {
+  const ovg_resample_frame* frames; const ovg_resample_frame* frames_host; int32_t nframes; int32_t out_format;
+  const uint8_t* src; int64_t src_bytes;
+  const int32_t* coef; const int32_t* coef_host; int64_t coef_len;
+  const float* lut;
+  void* out; int64_t out_elems;
+  uint8_t* ws; int64_t ws_bytes;
+} ovg_resample_params;
+int64_t ovg_resample_workspace_bytes(const ovg_resample_frame* frames_host, int32_t nframes);
+int ovg_resample_frames(const ovg_resample_params*, void* stream);
+
+typedef struct {
+  int64_t src_off; int32_t src_w; int32_t src_h;
+  int32_t rows_off; int32_t cols_off; int32_t out_w; int32_t out_h;
+  int64_t out_off;
+} ovg_depth_frame;
+typedef struct {
+  const ovg_depth_frame* frames; const ovg_depth_frame* frames_host; int32_t nframes; float max_depth;
+  const float* src; int64_t src_elems;
+  const int32_t* index; const int32_t* index_host; int64_t index_len;
+  float* depth; float* mask; int64_t out_elems;
+} ovg_depth_params;
+int ovg_depth_frames(const ovg_depth_params*, void* stream);
 
 /* head-major -> token-major: x [heads, n_pad, 64] dtype -> y [n, heads*64] dtype (row stride ldy), the layout the
  * proj GEMM reads; used after the return all-to-all of the head-parallel sharded attention. */

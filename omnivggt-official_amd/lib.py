@@ -14,7 +14,7 @@ OVG_BF16, OVG_F16, OVG_F32, OVG_F16X2 = 0, 1, 2, 3
 EPI_STORE, EPI_GELU, EPI_RES, EPI_PATCH = 0, 1, 2, 3
 OVG_MAX_SEG = 8
 KV_TILE = 64
-ABI_VERSION = 12
+ABI_VERSION = 13
 TILE_AUTO, TILE_128, TILE_256 = 0, 1, 2
 ATTN_F32X_FAST_PV = 92                                         # ovg_attn_params.variant in the split-f16 mode (opt-in): PV without P_lo x V_hi, +16 % at 3e-5 .. 1e-4 instead of 1e-5 .. 5e-5
 TILE_R02_EPILOGUE, TILE_128X, TILE_256X = 16, 17, 18      # A/B flag (r02 epilogue forms) OR-ed onto a tile selector
@@ -196,6 +196,32 @@ class PointFilterParams(C.Structure):
                 ("out_points", vp), ("out_colors", vp), ("out_index", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
+RS_F32_CHW, RS_U8_HWC = 0, 1
+
+
+class ResampleFrame(C.Structure):
+    _fields_ = [("src_off", i64), ("src_w", i32), ("src_h", i32), ("res_w", i32), ("res_h", i32), ("crop_y", i32), ("out_h", i32),
+                ("mid_row0", i32), ("mid_rows", i32), ("mid_off", i64), ("h_bounds_off", i32), ("h_k_off", i32), ("h_ksize", i32),
+                ("v_bounds_off", i32), ("v_k_off", i32), ("v_ksize", i32), ("canvas_w", i32), ("canvas_h", i32), ("pad_top", i32),
+                ("pad_left", i32), ("canvas_off", i64)]
+
+
+class ResampleParams(C.Structure):
+    _fields_ = [("frames", vp), ("frames_host", vp), ("nframes", i32), ("out_format", i32), ("src", vp), ("src_bytes", i64),
+                ("coef", vp), ("coef_host", vp), ("coef_len", i64), ("lut", vp), ("out", vp), ("out_elems", i64),
+                ("ws", vp), ("ws_bytes", i64)]
+
+
+class DepthFrame(C.Structure):
+    _fields_ = [("src_off", i64), ("src_w", i32), ("src_h", i32), ("rows_off", i32), ("cols_off", i32), ("out_w", i32), ("out_h", i32),
+                ("out_off", i64)]
+
+
+class DepthParams(C.Structure):
+    _fields_ = [("frames", vp), ("frames_host", vp), ("nframes", i32), ("max_depth", f32), ("src", vp), ("src_elems", i64),
+                ("index", vp), ("index_host", vp), ("index_len", i64), ("depth", vp), ("mask", vp), ("out_elems", i64)]
+
+
 # every entry point of include/omnivggt_hip.h: name -> (restype, argtypes)
 SYMBOLS = {
     "ovg_abi_version": (i32, []),
@@ -231,6 +257,9 @@ SYMBOLS = {
     "ovg_percentile_workspace_bytes": (i64, [i64, i32]),
     "ovg_point_filter": (i32, [C.POINTER(PointFilterParams), vp]),
     "ovg_point_filter_workspace_bytes": (i64, [i64]),
+    "ovg_resample_frames": (i32, [C.POINTER(ResampleParams), vp]),
+    "ovg_resample_workspace_bytes": (i64, [vp, i32]),
+    "ovg_depth_frames": (i32, [C.POINTER(DepthParams), vp]),
 }
 
 
