@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the OmniVGGT aggregator hot path on MI355X (contract: see the task prompt).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--views S] [--dtype bf16|f16|f32] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--views S] [--dtype bf16|f16|f32] [--dump-outputs DIR] [--full]
         (N > 1 without a launcher around it: the script starts its own N ranks -- self_launch -- and returns their exit code)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -12,12 +12,21 @@ Default workload at every N: 64 views, 518^2, images-only, bf16 -- BASELINE.json
 north star's scaling statement ("frames/sec at 1/2/4/8 GPUs ... on 64-view 518^2 synthetic input";
 SURVEY.md section 8d: "Config 4 ... also run G=1,2,4 for the scaling curve"), so `python bench.py --gpus N`
 for N=1,2,4,8 IS that strong-scaling curve ("scaling": "strong": total work fixed, views sharded over the
-ranks).  N > 1: the timed exchange form is the head-parallel all-to-all (sharding.py); the JSON line also
-carries `comm`: the un-overlapped cost of the exchange per layer (collectives issued alone), the compute-only
-step (same kernels, no collective) and exposed_comm_ms = step - compute-only, plus `second_form`: the same
-measurement with the north star's K/V all-gather form (`--shard-mode` picks which one is primary).
+ranks).  N > 1: the timed exchange form is the head-parallel all-to-all (sharding.py; `--shard-mode` picks it).
 
-At N=1 the same JSON line carries
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes the outputs of
+the last one (--dump-outputs), and prints the JSON line: `value`, `ms_per_step`, `config`, `roofline` (the live
+per-launch timing of the global attention inside the timed steps, plus the committed profiles/traffic.json
+figure when it matches the attention sources).  Everything else the benchmark measures or checks runs only with
+--full, after the headline measurement, and adds its own fields to the same line.
+
+With --full at N > 1 the JSON line also carries `preflight` (before anything is timed: both exchange forms on
+the bench's own input, compared, and the attention launch against several CU budgets), `comm`: the
+un-overlapped cost of the exchange per layer (collectives issued alone), the compute-only step (same kernels,
+no collective) and exposed_comm_ms = step - compute-only, plus `second_form`: the same measurement with the
+north star's K/V all-gather form.
+
+With --full at N=1 the same JSON line carries
   `secondary`    the 8-view configs[1] measurement (frames/s + roofline of the same kernel on that shape);
   `parity`       the timed 16-bit forward cross-checked against the parity-proven f32 mode of the SAME library on
                  the SAME inputs, per sampled layer, at 8 and at 64 views (max-rel and rms-rel) -- the headline
@@ -27,6 +36,9 @@ At N=1 the same JSON line carries
   `cpu_baseline` the oracle (CPU restatement of the reference) timed on the host: one frame block + one global
                  block + one DINO block at the REAL 64-view shapes, extrapolated x24, plus a complete
                  2-view forward.
+  `e2e`          the whole OmniVGGT.forward (aggregator + camera head + both DPT heads) at the timed view count, and at
+                 8 views next to `secondary`.
+The --no-* options drop single items of --full.
 --views S overrides the view count; --aux adds depth + camera tokens on every view (configs[2]).
 --dump-outputs DIR writes what the last timed step returned (a fixed, seeded sample of every layer's tokens, and
 patch_start_idx) as DIR/<name>.npy; the inputs and weights are seeded, so two builds can be compared output for output.
@@ -34,8 +46,8 @@ patch_start_idx) as DIR/<name>.npy; the inputs and weights are seeded, so two bu
 N > 1 robustness: every rank runs a watchdog thread (--watchdog-s): a rank that makes no progress for that long dumps the
 stacks of all its threads to stderr, tagged with its rank and the stage it was in, rank 0 prints the JSON line with what has
 been measured so far plus a `watchdog` record, and the process exits -- a hung collective yields a diagnosable record instead
-of a silent timeout. Before anything is timed, both exchange forms run one step each on the same input and are compared
-(`preflight`); a form that disagrees with the other by more than 5e-2 is not used as the primary.
+of a silent timeout. With --full, a form that disagrees with the other in the pre-flight by more than 5e-2 is not used as the
+primary.
 
 Prints ONE JSON line on rank 0.
 """
@@ -222,13 +234,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--views", type=int, default=0, help="total views S (default 64 at every N)")
     ap.add_argument("--dtype", default="bf16", choices=list(DT))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the f32-mode cross-check of the timed outputs (N=1)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the 8-view secondary measurement (N=1)")
-    ap.add_argument("--torch-heads", action="store_true", help="with --e2e: run the DPT heads as f32 PyTorch modules instead of the HIP kernels")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement also run everything else the benchmark measures or "
+                    "checks: N=1 secondary, parity, e2e, cpu_baseline; N>1 preflight, comm, second_form (the --no-* options drop single items)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (N=1)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the f32-mode cross-check of the timed outputs (N=1)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the 8-view secondary measurement (N=1)")
+    ap.add_argument("--torch-heads", action="store_true", help="with --full: run the DPT heads of the end-to-end measurement as f32 PyTorch modules instead of the HIP kernels")
     ap.add_argument("--e2e-views", type=int, default=0, help="view count of the end-to-end measurement (default: the timed view count, and 8 views next to the secondary)")
-    ap.add_argument("--e2e", action="store_true", help="(default since round 5; kept for old command lines) also time the whole OmniVGGT.forward")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end measurement (aggregator + camera head + both DPT heads; N = 1)")
+    ap.add_argument("--e2e", action="store_true", help="(kept for old command lines) the end-to-end measurement is part of --full")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end measurement (aggregator + camera head + both DPT heads; N = 1)")
     ap.add_argument("--attn-variant", type=int, default=0)
     ap.add_argument("--gemm-tile", type=int, default=0, help="force OVG_TILE_* on the block GEMMs (A/B runs)")
     ap.add_argument("--aux", action="store_true", help="depth + camera tokens on every view (BASELINE configs[2] with --views 16)")
@@ -236,7 +250,7 @@ def main():
                     help="N > 1: torch.distributed backend (nccl = RCCL; gloo only for debugging, e.g. several ranks on one GPU)")
     ap.add_argument("--shard-mode", default="auto", choices=["auto", "heads", "allgather"],
                     help="N > 1: exchange form of the global attention that `value` is measured with (sharding.ViewSharding)")
-    ap.add_argument("--no-second-form", action="store_true", help="N > 1: do not also measure the other exchange form")
+    ap.add_argument("--no-second-form", action="store_true", help="N > 1, with --full: do not also measure the other exchange form")
     ap.add_argument("--watchdog-s", type=float, default=float(os.environ.get("OVG_BENCH_WATCHDOG_S", "420")),
                     help="abort (with thread stacks, rank-tagged, and a partial JSON line) after this many seconds without progress; 0 = off")
     ap.add_argument("--partial-aux", action="store_true", help="cameras on the even views, depth on the second half of the views "
@@ -273,9 +287,9 @@ def main():
         import torch.distributed as dist
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         if args.backend == "nccl":
-            # what RCCL actually sets up (channel counts) goes to a per-rank file that rank 0 parses into comm.rccl_channels_observed;
-            # a job that configured NCCL_DEBUG itself keeps its own settings (and the field reports that)
-            if "NCCL_DEBUG" not in os.environ:
+            # with --full, what RCCL actually sets up (channel counts) goes to a per-rank file that rank 0 parses into
+            # comm.rccl_channels_observed; a job that configured NCCL_DEBUG itself keeps its own settings (and the field reports that)
+            if args.full and "NCCL_DEBUG" not in os.environ:
                 os.environ["NCCL_DEBUG"] = "INFO"
                 os.environ.setdefault("NCCL_DEBUG_SUBSYS", "INIT,ENV")
                 os.environ["NCCL_DEBUG_FILE"] = RCCL_LOG % rank
@@ -394,7 +408,7 @@ def main():
                          # softmax pass failed its check and re-ran with the lazy-rescale body (max over ranks); 0 = the fast path always paid
                          "fallback_workgroups": fallbacks if args.dtype == "bf16" else None},
         }
-        if shard is not None:
+        if shard is not None and args.full:
             res["comm"] = comm_report(step, S, steps, dt / steps * 1e3)
         torch.cuda.empty_cache()
         return res
@@ -434,7 +448,7 @@ def main():
         return rep
 
     S = args.views or 64
-    if shard is not None:
+    if shard is not None and args.full:
         # PRE-FLIGHT, before anything is timed (round-2 review: the exchange code had never met RCCL at N > 1): one forward
         # in each exchange form the shapes admit, on the bench's own input, compared across forms (MAX over ranks). Under the
         # watchdog, with rank-tagged stage lines on stderr. If the forms disagree the all-gather form -- two plain
@@ -464,7 +478,7 @@ def main():
     if "comm" in primary:
         result["comm"] = primary["comm"]
 
-    if shard is not None and not args.no_second_form:
+    if shard is not None and args.full and not args.no_second_form:
         # the other exchange form on the same workload (never part of `value`): the north star names the K/V all-gather.
         # Host-side failures of this block are recorded, not raised -- the primary number above must reach the JSON line;
         # a HUNG collective is the watchdog's business (it prints the partial line and exits).
@@ -487,7 +501,7 @@ def main():
         else:
             result["second_form"] = {"skipped": "the %s form is not available for S=%d, world=%d, dtype=%s (or failed the pre-flight)" % (other, S, world, args.dtype)}
 
-    if world == 1 and S != 8 and not args.views and not args.no_secondary:
+    if args.full and world == 1 and S != 8 and not args.views and not args.no_secondary:
         wd.stage("secondary: 8 views")
         sec = measure(8, 10, 3)                                      # BASELINE configs[1] on the same process
         result["secondary"] = {"frames_per_s": sec["value"], "ms_per_step": sec["ms_per_step"], "config": sec["config"],
@@ -512,10 +526,10 @@ def main():
                                                             "traffic not reported" % (str(traffic.get("attention_source_digest"))[:12], current[:12]))
             except Exception as e:
                 result["roofline"]["traffic_source"] = "profiles/traffic.json unreadable: %r" % (e,)
-        if args.dtype != "f32" and not args.no_parity:
+        if args.full and args.dtype != "f32" and not args.no_parity:
             wd.stage("parity block (f32 mode of the same library on the same inputs)")
             result["parity"] = parity_block(agg, dev, args, sorted({8, S}) if not (args.views or args.aux or args.partial_aux) else [S])
-        if not args.no_e2e:
+        if args.full and not args.no_e2e:
             # SURVEY 8d "report aggregator-only and end-to-end separately": the whole OmniVGGT.forward (aggregator + camera head + the two DPT
             # heads, all on the HIP kernels; `--torch-heads` forces PyTorch's) with the step protocol of the headline -- 2 warm-ups, then
             # timed forwards between synchronisations -- at the timed view count and, next to the secondary, at 8 views
@@ -546,7 +560,7 @@ def main():
                     result["secondary"]["e2e"] = e2e_measure(8, 5)
             except Exception as e:  # never let the heads hide the hot-path number
                 result["e2e_error"] = repr(e)[:200]
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             wd.stage("cpu baseline (host cores)")
             wd.timeout = max(wd.timeout, 1800.0)       # CPU work: minutes on a loaded host are not a hang
             result["cpu_baseline"] = cpu_baseline(sd)
