@@ -55,7 +55,9 @@ extern "C" {
  *     the 512-row attention launches (ovg_attn_plan_out: q_tile == tail_q_tile == 512, splits = key ranges of the tail rows, partials sized
  *     for the tail rows) when the caller passes a split workspace
  * 12: + point-cloud extraction (ovg_percentile, ovg_point_filter and their *_workspace_bytes queries)
- * 13: + input preprocessing (ovg_resample_frames, ovg_depth_frames, ovg_resample_workspace_bytes) */
+ * 13: + input preprocessing (ovg_resample_frames, ovg_depth_frames, ovg_resample_workspace_bytes)
+ *     + voxel-grid decimation (ovg_voxel_downsample, ovg_voxel_downsample_workspace_bytes): entries added, nothing existing changed,
+ *       so the number stays; a binding looks the two symbols up by name and reports a library that predates them */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -550,6 +552,40 @@ typedef struct {
 } ovg_point_filter_params;
 int64_t ovg_point_filter_workspace_bytes(int64_t n);
 int ovg_point_filter(const ovg_point_filter_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Voxel-grid decimation of a point cloud (added under ABI 13): one point per occupied cell of a regular grid, chosen by an exact rule
+ * that tests/voxelgrid_twin.py restates in numpy float32 bit for bit.
+ *   points [n][3] f32; conf [n] f32 (optional); colors [n][3] u8 (optional, with out_colors); voxel: DEVICE f32 scalar, the cell edge.
+ *   1. a point is valid when its three coordinates are finite; invalid points are never kept;
+ *   2. origin = component-wise minimum of the valid points (integer min of order-preserving keys: exact, independent of order);
+ *   3. cell c = floor((p - origin) / voxel) per axis: one f32 subtraction, one correctly rounded f32 division, a floor. A valid point
+ *      with any c > 2^21 - 1 raises OVG_VG_OVERFLOW; a voxel that is not a positive finite number raises OVG_VG_BAD_VOXEL; a call that
+ *      raised either keeps nothing. The cell key is the three 21-bit indices packed into 63 bits;
+ *   4. inside a cell the largest conf wins (compared through the order-preserving u32 map, -0 as +0, NaN lowest), ties and calls
+ *      without conf go to the smallest input index;
+ *   5. the winners leave in input order: out_points [M'][3] / out_colors [M'][3] are copies, out_index [M'] int64 (optional) the input
+ *      positions; entries at positions >= capacity are dropped.
+ *   stage OVG_VG_COUNT: table + winners + keep bytes + per-workgroup counts and their scan into ws; out_count[0] = M',
+ *   out_count[1] = the OVG_VG_* flags raised (two int64, device). stage OVG_VG_SCATTER: reads what COUNT left in ws.
+ *   Table: open addressing, linear probing, 2n (>= 1024) slots of 16 bytes {u64 key, u64 best}; a slot is claimed by a 64-bit
+ *   compare-and-swap of its key, the winner is one 64-bit max of (conf key << 32) | ~index. Max and min do not depend on arrival
+ *   order, so two runs give identical bytes. No float atomics.
+ *   ws: >= ovg_voxel_downsample_workspace_bytes(n) bytes (256 + 32 n for the table + the point filter's n keep bytes and counts),
+ *   16-byte aligned; the query returns -1 for n <= 0 or n >= 2^32, the entry OVG_E_ARG.
+ * ------------------------------------------------------------------ */
+enum { OVG_VG_COUNT = 1, OVG_VG_SCATTER = 2 };
+enum { OVG_VG_OVERFLOW = 1, OVG_VG_BAD_VOXEL = 2 };
+typedef struct {
+  const float* points; const float* conf; const uint8_t* colors; const float* voxel;
+  int64_t n;
+  int32_t stage; int32_t pad;
+  int64_t capacity;
+  float* out_points; uint8_t* out_colors; int64_t* out_index; int64_t* out_count;
+  void* ws; int64_t ws_bytes;
+} ovg_voxel_downsample_params;
+int64_t ovg_voxel_downsample_workspace_bytes(int64_t n);
+int ovg_voxel_downsample(const ovg_voxel_downsample_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

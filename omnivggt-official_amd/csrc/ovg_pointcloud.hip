@@ -1,6 +1,8 @@
 // Point-cloud extraction (visual_util.py:113-236, the selection core of predictions_to_glb): exact numpy-2 linear percentiles by radix
 // select (ovg_percentile) and the confidence / background filter with an order-preserving compaction (ovg_point_filter).
 // Every kernel is HBM bound: the selection reads each key three times and the filter reads conf / image twice; no launch waits on the host.
+// Voxel-grid decimation of a selected cloud (ovg_voxel_downsample) shares the filter's count / scan / scatter; its hash stage is bound
+// by random 64-bit atomics, not by bandwidth.
 #include "ovg_common.h"
 
 // the percentile's lerp and the scene-scale norm restate numpy's f32 / f64 operation sequence: no fused multiply-adds anywhere in this
@@ -294,9 +296,11 @@ __global__ __launch_bounds__(1024) void pf_scan(PfWs ws, int64_t nblk, int64_t* 
   if (threadIdx.x == 0) *out_count = (int64_t)carry;
 }
 
-// order-preserving scatter: pixel i of the tile lands at offset[block] + (kept pixels before it in the tile); pixel order inside a
-// tile is j-major (j * 256 + thread), so the rank is the count of the earlier (j, wave) groups plus the lanes below in the ballot
-__global__ __launch_bounds__(kThreads) void pf_scatter(ovg_point_filter_params p, PfWs ws) {
+// order-preserving scatter: entry i of the tile lands at offset[block] + (kept entries before it in the tile); the order inside a
+// tile is j-major (j * 256 + thread), so the rank is the count of the earlier (j, wave) groups plus the lanes below in the ballot.
+// emit(i, pos) copies entry i to output position pos (< capacity); every thread of the workgroup calls this once
+template <class Emit>
+OVG_DEV void scatter_tile(const uint8_t* keep, int64_t n, const int64_t* offsets, int64_t capacity, Emit emit) {
   constexpr int J = kTile / kThreads;
   __shared__ uint32_t cnt[J * (kThreads / 64)];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -305,7 +309,7 @@ __global__ __launch_bounds__(kThreads) void pf_scatter(ovg_point_filter_params p
 #pragma unroll
   for (int j = 0; j < J; ++j) {
     const int64_t i = base + (int64_t)j * kThreads + threadIdx.x;
-    const bool k = i < p.n && ws.keep[i];
+    const bool k = i < n && keep[i];
     bits |= (uint32_t)k << j;
     const uint64_t bal = __ballot(k);
     if (lane == 0) cnt[j * (kThreads / 64) + wave] = __popcll(bal);
@@ -316,7 +320,7 @@ __global__ __launch_bounds__(kThreads) void pf_scatter(ovg_point_filter_params p
     cnt[lane] = (uint32_t)(wave_incl_scan(v) - v);
   }
   __syncthreads();
-  const int64_t off = ws.offsets[blockIdx.x];
+  const int64_t off = offsets[blockIdx.x];
   const uint64_t below = (1ull << lane) - 1ull;
 #pragma unroll
   for (int j = 0; j < J; ++j) {
@@ -325,7 +329,13 @@ __global__ __launch_bounds__(kThreads) void pf_scatter(ovg_point_filter_params p
     if (!k) continue;
     const int64_t i = base + (int64_t)j * kThreads + threadIdx.x;
     const int64_t pos = off + cnt[j * (kThreads / 64) + wave] + __popcll(bal & below);
-    if (pos >= p.capacity) continue;
+    if (pos >= capacity) continue;
+    emit(i, pos);
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void pf_scatter(ovg_point_filter_params p, PfWs ws) {
+  scatter_tile(ws.keep, p.n, ws.offsets, p.capacity, [&](int64_t i, int64_t pos) {
     const float* src = p.points + i * 3;
     float* dst = p.out_points + pos * 3;
     dst[0] = src[0];
@@ -338,7 +348,163 @@ __global__ __launch_bounds__(kThreads) void pf_scatter(ovg_point_filter_params p
     col[1] = (uint8_t)g;
     col[2] = (uint8_t)b;
     if (p.out_index) p.out_index[pos] = p.index_base + i;
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// voxel-grid decimation: one point per occupied cell of a grid of edge *voxel anchored at the minimum of the finite points; the
+// winner of a cell is the largest conf (NaN lowest), ties to the smallest index; the winners leave in input order.
+// Open-addressing table of (key, best) pairs: the 63-bit cell key claims a slot by a 64-bit compare-and-swap, then one 64-bit max of
+// (conf order key << 32) | ~index picks the winner. Max and min do not depend on arrival order: two runs give the same bytes.
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr uint64_t kVgEmpty = ~0ull;                // no cell key has bit 63
+constexpr float kVgMaxCell = 2097151.0f;            // 2^21 - 1
+constexpr int64_t kVgMinSlots = 1024;
+
+struct VgHead { uint32_t origin[3]; uint32_t flags; };     // origin as order keys (integer min is exact and order-free)
+struct VgSlot { uint64_t key, best; };                      // one 16-byte slot: the claim and the max touch the same line
+struct VgWs { VgHead* head; VgSlot* table; int64_t nslots; PfWs pf; };
+
+int64_t vg_slots(int64_t n) { return 2 * n < kVgMinSlots ? kVgMinSlots : 2 * n; }      // load factor <= 1/2
+int64_t vg_ws_bytes(int64_t n) { return 256 + round256(vg_slots(n) * (int64_t)sizeof(VgSlot)) + pf_ws_bytes(n); }
+VgWs vg_ws(const ovg_voxel_downsample_params* p) {
+  uint8_t* b = static_cast<uint8_t*>(p->ws);
+  const int64_t ns = vg_slots(p->n), nb = pf_blocks(p->n);
+  uint8_t* k = b + 256 + round256(ns * (int64_t)sizeof(VgSlot));
+  return {reinterpret_cast<VgHead*>(b), reinterpret_cast<VgSlot*>(b + 256), ns,
+          {k, reinterpret_cast<int64_t*>(k + round256(p->n)), reinterpret_cast<int64_t*>(k + round256(p->n) + round256(nb * 8))}};
+}
+
+OVG_DEV bool finite_f32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
+
+__global__ __launch_bounds__(kThreads) void vg_init(VgWs ws, int64_t n) {
+  const int64_t t0 = (int64_t)blockIdx.x * kThreads + threadIdx.x, step = (int64_t)gridDim.x * kThreads;
+  u32x4* tab = reinterpret_cast<u32x4*>(ws.table);
+  const u32x4 empty = {0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u};
+  for (int64_t i = t0; i < ws.nslots; i += step) tab[i] = empty;
+  u32x4* keep = reinterpret_cast<u32x4*>(ws.pf.keep);            // the keep bytes are rounded up to 256: whole 16-byte stores
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  for (int64_t i = t0; i < (n + 15) / 16; i += step) keep[i] = zero;
+  if (t0 == 0) *ws.head = {{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, 0u};
+}
+
+__global__ __launch_bounds__(kThreads) void vg_origin(ovg_voxel_downsample_params p, VgWs ws) {
+  __shared__ uint32_t red[3][kThreads / 64];
+  uint32_t m[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * kThreads) {
+    const float x = p.points[3 * i], y = p.points[3 * i + 1], z = p.points[3 * i + 2];
+    if (finite_f32(x) && finite_f32(y) && finite_f32(z)) {
+      m[0] = min(m[0], order_key(x));
+      m[1] = min(m[1], order_key(y));
+      m[2] = min(m[2], order_key(z));
+    }
   }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    for (int d = 32; d > 0; d >>= 1) m[k] = min(m[k], (uint32_t)__shfl_down(m[k], d, 64));
+    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = m[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    uint32_t v = red[threadIdx.x][0];
+    for (int w = 1; w < kThreads / 64; ++w) v = min(v, red[threadIdx.x][w]);
+    if (v != 0xFFFFFFFFu) __hip_atomic_fetch_min(&ws.head->origin[threadIdx.x], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+OVG_DEV uint64_t vg_mix(uint64_t h) {                // murmur3's 64-bit finaliser
+  h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
+  return h;
+}
+
+__global__ __launch_bounds__(kThreads) void vg_insert(ovg_voxel_downsample_params p, VgWs ws) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= p.n) return;
+  const float v = *p.voxel;
+  if (!(v > 0.0f) || !finite_f32(v)) {
+    if (i == 0) __hip_atomic_fetch_or(&ws.head->flags, (uint32_t)OVG_VG_BAD_VOXEL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  const float x = p.points[3 * i], y = p.points[3 * i + 1], z = p.points[3 * i + 2];
+  if (!(finite_f32(x) && finite_f32(y) && finite_f32(z))) return;
+  // np.floor((p - origin) / v) in float32: one subtraction, one correctly rounded division, a floor (p >= origin, so c >= 0)
+  const float cx = floorf(__fdiv_rn(__fsub_rn(x, key_value(ws.head->origin[0])), v));
+  const float cy = floorf(__fdiv_rn(__fsub_rn(y, key_value(ws.head->origin[1])), v));
+  const float cz = floorf(__fdiv_rn(__fsub_rn(z, key_value(ws.head->origin[2])), v));
+  const bool over = !(cx <= kVgMaxCell && cy <= kVgMaxCell && cz <= kVgMaxCell);       // also an extent that overflowed to inf
+  if (over) {
+    if (!(__hip_atomic_load(&ws.head->flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & OVG_VG_OVERFLOW))
+      __hip_atomic_fetch_or(&ws.head->flags, (uint32_t)OVG_VG_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  const uint64_t key = ((uint64_t)(uint32_t)cx << 42) | ((uint64_t)(uint32_t)cy << 21) | (uint64_t)(uint32_t)cz;
+  uint32_t ck = 0;                                    // NaN conf is the lowest value; -0 counts as +0, as numpy compares them
+  if (p.conf) {
+    const float c = p.conf[i];
+    if (c == c) ck = order_key(c + 0.0f);
+  }
+  const uint64_t word = ((uint64_t)ck << 32) | (uint32_t)~(uint32_t)i;                  // larger conf first, then the smaller index
+  int64_t s = (int64_t)__umul64hi(vg_mix(key), (uint64_t)ws.nslots);
+  for (int64_t t = 0; t < ws.nslots; ++t) {          // at most n of the >= 2n slots are ever claimed: the walk ends at a free one
+    VgSlot* slot = ws.table + s;
+    uint64_t k = __hip_atomic_load(&slot->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == kVgEmpty) {
+      uint64_t expect = kVgEmpty;
+      k = __hip_atomic_compare_exchange_strong(&slot->key, &expect, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? key : expect;
+    }
+    if (k == key) {
+      // best only grows: a point that already loses to what is visible needs no atomic (most points, once a cell holds many)
+      if (__hip_atomic_load(&slot->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < word)
+        __hip_atomic_fetch_max(&slot->best, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+    s = s + 1 == ws.nslots ? 0 : s + 1;
+  }
+}
+
+// every claimed slot names its cell's winner; nothing is kept from a call that raised a flag
+__global__ __launch_bounds__(kThreads) void vg_mark(VgWs ws, int64_t n) {
+  if (ws.head->flags) return;
+  for (int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x; s < ws.nslots; s += (int64_t)gridDim.x * kThreads) {
+    const u32x4 e = reinterpret_cast<const u32x4*>(ws.table)[s];
+    if ((e[0] & e[1]) == 0xFFFFFFFFu) continue;
+    const int64_t i = (int64_t)(uint32_t)~e[2];
+    if (i < n) ws.pf.keep[i] = 1;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void vg_count(VgWs ws, int64_t n, int64_t* out_count) {
+  __shared__ int64_t red[kThreads / 64];
+  const int64_t base = (int64_t)blockIdx.x * kTile;
+  int64_t cnt = 0;
+#pragma unroll 4
+  for (int j = 0; j < kTile / kThreads; ++j) {
+    const int64_t i = base + (int64_t)j * kThreads + threadIdx.x;
+    if (i < n) cnt += ws.pf.keep[i];
+  }
+  const int64_t t = block_sum(cnt, red);
+  if (threadIdx.x == 0) {
+    ws.pf.counts[blockIdx.x] = t;
+    if (blockIdx.x == 0) out_count[1] = (int64_t)ws.head->flags;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void vg_scatter(ovg_voxel_downsample_params p, VgWs ws) {
+  scatter_tile(ws.pf.keep, p.n, ws.pf.offsets, p.capacity, [&](int64_t i, int64_t pos) {
+    const float* src = p.points + i * 3;
+    float* dst = p.out_points + pos * 3;
+    dst[0] = src[0];
+    dst[1] = src[1];
+    dst[2] = src[2];
+    if (p.colors) {
+      const uint8_t* cs = p.colors + i * 3;
+      uint8_t* col = p.out_colors + pos * 3;
+      col[0] = cs[0];
+      col[1] = cs[1];
+      col[2] = cs[2];
+    }
+    if (p.out_index) p.out_index[pos] = i;
+  });
 }
 
 bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
@@ -429,6 +595,38 @@ extern "C" int ovg_point_filter(const ovg_point_filter_params* p, void* stream) 
   }
   if ((p->stage & OVG_PF_SCATTER) && p->capacity > 0) {
     OVG_LAUNCH(pf_scatter, dim3((unsigned)nblk), dim3(kThreads), 0, st, *p, ws);
+    OVG_CHECK_LAUNCH();
+  }
+  return OVG_OK;
+}
+
+extern "C" int64_t ovg_voxel_downsample_workspace_bytes(int64_t n) { return n <= 0 || n >= (1ll << 32) ? -1 : vg_ws_bytes(n); }
+
+extern "C" int ovg_voxel_downsample(const ovg_voxel_downsample_params* p, void* stream) {
+  if (!p || !p->points || !p->voxel || !p->ws || p->n <= 0 || p->n >= (1ll << 32)) return OVG_E_ARG;
+  if (p->stage < 1 || p->stage > (OVG_VG_COUNT | OVG_VG_SCATTER)) return OVG_E_ARG;
+  if ((p->stage & OVG_VG_COUNT) && !p->out_count) return OVG_E_ARG;
+  if ((p->stage & OVG_VG_SCATTER) && (!p->out_points || p->capacity < 0 || (p->colors != nullptr) != (p->out_colors != nullptr))) return OVG_E_ARG;
+  if (!al(p->ws, 16) || p->ws_bytes < vg_ws_bytes(p->n)) return OVG_E_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const VgWs ws = vg_ws(p);
+  const int64_t nblk = pf_blocks(p->n);
+  if (p->stage & OVG_VG_COUNT) {
+    OVG_LAUNCH(vg_init, dim3(grid_for(ws.nslots, kThreads * 4, 4096)), dim3(kThreads), 0, st, ws, p->n);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(vg_origin, dim3(grid_for(p->n, kThreads * 4, 2048)), dim3(kThreads), 0, st, *p, ws);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(vg_insert, dim3((unsigned)((p->n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, *p, ws);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(vg_mark, dim3(grid_for(ws.nslots, kThreads * 4, 4096)), dim3(kThreads), 0, st, ws, p->n);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(vg_count, dim3((unsigned)nblk), dim3(kThreads), 0, st, ws, p->n, p->out_count);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(pf_scan, dim3(1), dim3(1024), 0, st, ws.pf, nblk, p->out_count);
+    OVG_CHECK_LAUNCH();
+  }
+  if ((p->stage & OVG_VG_SCATTER) && p->capacity > 0) {
+    OVG_LAUNCH(vg_scatter, dim3((unsigned)nblk), dim3(kThreads), 0, st, *p, ws);
     OVG_CHECK_LAUNCH();
   }
   return OVG_OK;

@@ -196,6 +196,15 @@ class PointFilterParams(C.Structure):
                 ("out_points", vp), ("out_colors", vp), ("out_index", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
+VG_COUNT, VG_SCATTER = 1, 2
+VG_OVERFLOW, VG_BAD_VOXEL = 1, 2
+
+
+class VoxelDownsampleParams(C.Structure):
+    _fields_ = [("points", vp), ("conf", vp), ("colors", vp), ("voxel", vp), ("n", i64), ("stage", i32), ("pad", i32), ("capacity", i64),
+                ("out_points", vp), ("out_colors", vp), ("out_index", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -260,6 +269,9 @@ SYMBOLS = {
     "ovg_resample_frames": (i32, [C.POINTER(ResampleParams), vp]),
     "ovg_resample_workspace_bytes": (i64, [vp, i32]),
     "ovg_depth_frames": (i32, [C.POINTER(DepthParams), vp]),
+    # added under ABI 13 without a new number: load() reports a library that predates them by name
+    "ovg_voxel_downsample": (i32, [C.POINTER(VoxelDownsampleParams), vp]),
+    "ovg_voxel_downsample_workspace_bytes": (i64, [i64]),
 }
 
 
@@ -289,7 +301,10 @@ def load(build_if_missing=True):
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)      # AttributeError here == ABI mismatch, fail loudly
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:       # ABI mismatch, fail loudly (entries may be added without a new ABI number: a stale library lacks them)
+            raise OvgError("%s lacks %s: the library predates this binding; rebuild it with __graft_entry__.build()" % (LIB_PATH, name)) from None
         fn.restype = res
         fn.argtypes = args
     if lib.ovg_abi_version() != ABI_VERSION:

@@ -594,3 +594,38 @@ def point_filter(stage, conf, images, points, hw, ws, threshold=None, mask=None,
     p.out_points, p.out_colors, p.out_index, p.out_count = L.ptr(out_points), L.ptr(out_colors), L.ptr(out_index), L.ptr(out_count)
     p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
     L.call("ovg_point_filter", p, _stream())
+
+
+def voxel_downsample_workspace_bytes(n):
+    b = L.load().ovg_voxel_downsample_workspace_bytes(int(n))
+    if b < 0:
+        raise L.OvgError("ovg_voxel_downsample_workspace_bytes: unsupported (n=%d)" % n)
+    return int(b)
+
+
+def voxel_downsample(stage, points, voxel, ws, conf=None, colors=None, out_count=None, capacity=0, out_points=None, out_colors=None,
+                     out_index=None):
+    """ovg_voxel_downsample on contiguous device tensors: points f32 [n, 3], voxel a 0-d / 1-element f32 device tensor, conf f32 [n] or
+    None, colors u8 [n, 3] or None. stage L.VG_COUNT writes (M', flags) to the two int64 of out_count; L.VG_SCATTER writes the first
+    `capacity` winners (in input order) to out_points / out_colors / out_index from what the COUNT stage left in ws."""
+    _chk_dev(points, voxel, ws, conf, colors, out_count, out_points, out_colors, out_index)
+    for t in (points, voxel, conf):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise L.OvgError("voxel_downsample: points / voxel / conf must be contiguous f32 tensors")
+    n = points.numel() // 3
+    if points.numel() != 3 * n or voxel.numel() != 1 or (conf is not None and conf.numel() != n) or \
+            (colors is not None and (colors.dtype != torch.uint8 or not colors.is_contiguous() or colors.numel() != 3 * n)):
+        raise L.OvgError("voxel_downsample: points / colors must hold 3 values per point, conf one, voxel exactly one")
+    if stage & L.VG_SCATTER:
+        outs = ((out_points, torch.float32, 3), (out_colors, torch.uint8, 3), (out_index, torch.int64, 1))
+        for t, dt, k in outs:
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < k * capacity):
+                raise L.OvgError("voxel_downsample: output buffers must be contiguous and hold `capacity` entries")
+    if out_count is not None and (out_count.dtype != torch.int64 or out_count.numel() < 2 or not out_count.is_contiguous()):
+        raise L.OvgError("voxel_downsample: out_count must be a contiguous int64 device tensor of two elements")
+    p = L.VoxelDownsampleParams()
+    p.points, p.conf, p.colors, p.voxel, p.n, p.stage = L.ptr(points), L.ptr(conf), L.ptr(colors), L.ptr(voxel), n, int(stage)
+    p.capacity = int(capacity)
+    p.out_points, p.out_colors, p.out_index, p.out_count = L.ptr(out_points), L.ptr(out_colors), L.ptr(out_index), L.ptr(out_count)
+    p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
+    L.call("ovg_voxel_downsample", p, _stream())

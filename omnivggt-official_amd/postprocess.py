@@ -105,12 +105,12 @@ class PointCloud:
     """Result of predictions_to_point_cloud. points (M,3) f32, colors (M,3) u8 and indices (M,) int64 (flat pixel index into the
     batch element's S x H x W maps, or None) are device tensors; conf_threshold (the f32 percentile, 0 when conf_thres == 0) and
     scene_scale (f32) are 0-d device tensors; transform is the (4,4) float64 numpy alignment; extrinsic (S',3,4) the selected
-    frames' cameras on the device."""
-    __slots__ = ("points", "colors", "conf_threshold", "scene_scale", "transform", "extrinsic", "indices")
+    frames' cameras on the device; conf (M,) f32 the points' confidence after the sky-mask rule (device, or None when not asked for)."""
+    __slots__ = ("points", "colors", "conf_threshold", "scene_scale", "transform", "extrinsic", "indices", "conf")
 
-    def __init__(self, points, colors, conf_threshold, scene_scale, transform, extrinsic, indices=None):
+    def __init__(self, points, colors, conf_threshold, scene_scale, transform, extrinsic, indices=None, conf=None):
         self.points, self.colors, self.conf_threshold, self.scene_scale = points, colors, conf_threshold, scene_scale
-        self.transform, self.extrinsic, self.indices = transform, extrinsic, indices
+        self.transform, self.extrinsic, self.indices, self.conf = transform, extrinsic, indices, conf
 
     def __len__(self):
         return int(self.points.shape[0])
@@ -134,7 +134,8 @@ def scene_alignment(extrinsic0):
 
 
 def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="all", mask_black_bg=False, mask_white_bg=False,
-                               prediction_mode="Predicted Pointmap", sky_mask=None, min_conf=1e-5, batch_index=0, return_indices=False):
+                               prediction_mode="Predicted Pointmap", sky_mask=None, min_conf=1e-5, batch_index=0, return_indices=False,
+                               return_conf=False):
     """The point cloud of visual_util.predictions_to_glb (:77-267) on the device, for the dict OmniVGGT.forward returns (batch dimension
     included; batch_index=0 is what the reference's select_first_batch keeps).
 
@@ -148,6 +149,7 @@ def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="a
     (sky_mask > 0.1) before the frame filter, as in the reference (mask resizing and the ONNX sky model are not part of this).
     scene_scale is ||P95 - P5|| of the kept, untransformed vertices; transform is inv(E0) @ diag(1,-1,-1,1) @ R_y(180) with E0 the
     first selected camera, which the writers apply (the vertices themselves are copied untransformed).
+    return_conf: PointCloud.conf holds the kept pixels' confidence after the sky-mask rule (what voxel_downsample ranks by).
 
     One divergence: an empty selection returns M = 0 (scene_scale 1); the reference substitutes one white point at (1, 0, 0).
     Exactly one device -> host synchronisation: reading M (with the first selected camera) to size the result. CPU tensors raise
@@ -225,13 +227,87 @@ def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="a
     transform = scene_alignment(host[1:13].reshape(3, 4))
     out_pts = torch.empty(M, 3, device=dev, dtype=torch.float32)
     out_col = torch.empty(M, 3, device=dev, dtype=torch.uint8)
-    out_idx = torch.empty(M, device=dev, dtype=torch.int64) if return_indices else None
+    out_idx = torch.empty(M, device=dev, dtype=torch.int64) if return_indices or return_conf else None
     if M:
         ops.point_filter(L.PF_SCATTER, capacity=M, out_points=out_pts, out_colors=out_col, out_index=out_idx, **args)
         _, scale = ops.percentile(out_pts, M, 3, 1, 3, [5.0, 95.0], norm=True)
     else:
         scale = torch.ones((), device=dev, dtype=torch.float32)
-    return PointCloud(out_pts, out_col, conf_threshold, scale, transform, extrinsic, out_idx)
+    out_conf = None
+    if return_conf:
+        local = out_idx - base if base else out_idx
+        out_conf = cf[local] if mk is None else cf[local] * (mk[local] > 0.1).to(torch.float32)      # the kernels' rule: inf * 0 is NaN
+    return PointCloud(out_pts, out_col, conf_threshold, scale, transform, extrinsic, out_idx if return_indices else None, out_conf)
+
+
+def voxel_downsample(cloud, voxel_size=None, rel_size=None, conf=None):
+    """Voxel-grid decimation of a PointCloud on the device (ovg_voxel_downsample): one point per occupied cell of a regular grid.
+
+    Exactly one of voxel_size (the cell edge in the cloud's units: a positive float or a 0-d f32 device tensor) and rel_size (a positive
+    float; the edge is f32(rel_size) * cloud.scene_scale, one f32 multiply on the device, no host copy) must be given. The rule is
+    exact (tests/voxelgrid_twin.py restates it in numpy): points with a non-finite coordinate are dropped; the grid starts at the
+    component-wise minimum of the others; cell = floor((p - origin) / edge) in f32; inside a cell the point with the largest `conf`
+    wins (an optional (M,) f32 device tensor, e.g. cloud.conf of predictions_to_point_cloud(return_conf=True); NaN ranks lowest), ties
+    and calls without conf go to the earliest point; the winners keep their input order. Two calls give identical bytes.
+
+    The result carries the winners' points and colors, `indices` composed with the input cloud's when it has them (so they still name
+    pixels of the prediction maps; positions in the input cloud otherwise) and `conf` gathered from the argument (or from cloud.conf).
+    transform, extrinsic, conf_threshold and scene_scale are passed through unchanged: scene_scale still describes the full selection.
+    write_ply / write_glb accept the result as they are.
+
+    Exactly one device -> host synchronisation (the count and the kernel's flags in one copy). A grid of more than 2^21 cells along an
+    axis, or an edge that is not positive on the device, raises ValueError. An empty cloud returns an empty cloud without a launch.
+    CPU tensors raise OvgError: there is no CPU fallback."""
+    import math
+    L = ops.L
+    if (voxel_size is None) == (rel_size is None):
+        raise ValueError("voxel_downsample: give exactly one of voxel_size and rel_size")
+    given = voxel_size if rel_size is None else rel_size
+    if isinstance(given, torch.Tensor):
+        if rel_size is not None or given.numel() != 1:
+            raise ValueError("voxel_downsample: rel_size must be a float, voxel_size a float or a one-element tensor")
+    else:
+        given = float(given)
+        if not (given > 0.0 and math.isfinite(given)):
+            raise ValueError("voxel_downsample: the size must be positive and finite, got %r" % given)
+    pts, col = cloud.points, cloud.colors
+    for t in (pts, col, conf, given if isinstance(given, torch.Tensor) else None):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise L.OvgError("voxel_downsample needs HIP device tensors: there is no CPU fallback")
+    M = int(pts.shape[0])
+    if conf is not None and tuple(conf.shape) != (M,):
+        raise ValueError("voxel_downsample: conf must be (M,) = (%d,), got %r" % (M, tuple(conf.shape)))
+    src_conf = conf if conf is not None else cloud.conf
+    if M == 0:
+        return PointCloud(pts, col, cloud.conf_threshold, cloud.scene_scale, cloud.transform, cloud.extrinsic, cloud.indices, src_conf)
+    dev = pts.device
+    pts = pts.reshape(M, 3).float().contiguous()
+    col = col.reshape(M, 3).contiguous()
+    rank = None if conf is None else conf.float().contiguous()
+    if isinstance(given, torch.Tensor):
+        voxel = given.detach().to(torch.float32).reshape(())
+    else:
+        voxel = torch.full((), given, device=dev, dtype=torch.float32)
+        if rel_size is not None:
+            voxel = voxel * cloud.scene_scale.to(torch.float32).reshape(())
+    ws = torch.empty(ops.voxel_downsample_workspace_bytes(M), device=dev, dtype=torch.uint8)
+    count = torch.empty(2, device=dev, dtype=torch.int64)
+    args = dict(points=pts, voxel=voxel, ws=ws, conf=rank, colors=col)
+    ops.voxel_downsample(L.VG_COUNT, out_count=count, **args)
+    kept, flags = (int(v) for v in count.cpu().tolist())                 # the one synchronisation
+    if flags:
+        ok = torch.isfinite(pts).all(dim=1)
+        extent = (pts[ok].max(dim=0).values - pts[ok].min(dim=0).values).tolist() if bool(ok.any()) else []
+        what = "is not a positive finite number" if flags & L.VG_BAD_VOXEL else "gives more than 2^21 cells along an axis"
+        raise ValueError("voxel_downsample: voxel size %r %s (extent of the cloud %r)" % (float(voxel), what, extent))
+    out_pts = torch.empty(kept, 3, device=dev, dtype=torch.float32)
+    out_col = torch.empty(kept, 3, device=dev, dtype=torch.uint8)
+    out_idx = torch.empty(kept, device=dev, dtype=torch.int64)
+    if kept:
+        ops.voxel_downsample(L.VG_SCATTER, capacity=kept, out_points=out_pts, out_colors=out_col, out_index=out_idx, **args)
+    indices = out_idx if cloud.indices is None else cloud.indices[out_idx]
+    return PointCloud(out_pts, out_col, cloud.conf_threshold, cloud.scene_scale, cloud.transform, cloud.extrinsic, indices,
+                      None if src_conf is None else src_conf[out_idx])
 
 
 def _host_cloud(cloud):
@@ -260,12 +336,37 @@ def write_ply(path, cloud, apply_transform=True):
         fh.write(rec.tobytes())
 
 
-def write_glb(path, cloud):
+CAMERA_COLORS = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240),
+                 (240, 50, 230))
+_FRUSTUM_FACES = (0, 1, 2, 0, 2, 3, 0, 3, 4, 0, 4, 1, 1, 3, 2, 1, 4, 3)    # four sides from the apex, two triangles of the base
+
+
+def camera_frusta(extrinsic, height):
+    """(S, 5, 3) float64 vertices of one four-sided pyramid per camera-from-world (3,4) extrinsic: vertex 0 the apex at the camera
+    centre -R^T t, vertices 1..4 the square base at distance `height` along the camera's +z axis, its corners height / 2 away from
+    the axis on the diagonals of the image plane (the reference's cone of radius 0.05 and height 0.1 scene scales turned by 45 degrees,
+    visual_util.py:270-318, has the same proportions)."""
+    import numpy as np
+    e = np.asarray(extrinsic, dtype=np.float64).reshape(-1, 3, 4)
+    Rt = e[:, :, :3].transpose(0, 2, 1)                                   # world-from-camera rotations
+    centre = -np.einsum("sij,sj->si", Rt, e[:, :, 3])
+    a = height / 2.0 / np.sqrt(2.0)
+    local = np.array([[0.0, 0.0, 0.0], [a, a, height], [-a, a, height], [-a, -a, height], [a, -a, height]])
+    return centre[:, None, :] + np.einsum("sij,vj->svi", Rt, local)
+
+
+def write_glb(path, cloud, cameras=False, camera_scale=0.05):
     """glTF 2.0 binary of the cloud: one POINTS primitive with POSITION (f32 VEC3, with the min / max the spec requires) and COLOR_0
     (normalized u8 VEC4, alpha 255), under one node whose `matrix` is cloud.transform (column-major, as glTF stores it). The vertices
     stay untransformed, as in the reference's file: trimesh's Scene.apply_transform moves the scene graph, not the vertex buffer. This
     follows the reference file's structure; it was not compared byte-wise with trimesh's export (trimesh is not a dependency here).
-    An empty cloud writes a node without a mesh."""
+    An empty cloud writes a node without a mesh.
+
+    cameras=True adds one TRIANGLES primitive per camera of cloud.extrinsic to the same mesh, so under the same aligned node: a
+    four-sided pyramid (camera_frusta) with its apex at the camera centre, opening along the camera's +z axis, of height
+    camera_scale * cloud.scene_scale, in one flat colour per camera from CAMERA_COLORS (cycled), double-sided. This follows the
+    reference's placement and size rule (visual_util.py:270-318); the reference builds its cones with trimesh, so the files are not
+    compared byte-wise. With cameras=False the file is what it was without the argument."""
     import json
     import struct
     import numpy as np
@@ -287,6 +388,31 @@ def write_glb(path, cloud):
         gltf["accessors"] = [{"bufferView": 0, "componentType": 5126, "count": M, "type": "VEC3",
                               "min": [float(v) for v in pts.min(axis=0)], "max": [float(v) for v in pts.max(axis=0)]},
                              {"bufferView": 1, "componentType": 5121, "normalized": True, "count": M, "type": "VEC4"}]
+    if cameras:
+        ext = cloud.extrinsic
+        ext = ext.detach().cpu().numpy() if isinstance(ext, torch.Tensor) else np.asarray(ext)
+        verts = camera_frusta(ext, float(camera_scale) * float(cloud.scene_scale)).astype("<f4")
+        S = len(verts)
+        if S:
+            binary += b"\0" * (-len(binary) % 4)
+            rgba = np.array([CAMERA_COLORS[i % len(CAMERA_COLORS)] + (255,) for i in range(S)], np.uint8)
+            parts = [verts.tobytes(), np.repeat(rgba[:, None, :], 5, axis=1).tobytes(), np.tile(np.array(_FRUSTUM_FACES, "<u2"), S).tobytes()]
+            views, accs = gltf.setdefault("bufferViews", []), gltf.setdefault("accessors", [])
+            prims = gltf.setdefault("meshes", [{"primitives": []}])[0]["primitives"]
+            v0 = len(views)
+            for part, target in zip(parts, (34962, 34962, 34963)):
+                views.append({"buffer": 0, "byteOffset": len(binary), "byteLength": len(part), "target": target})
+                binary += part
+            gltf["materials"] = [{"doubleSided": True}]
+            for i in range(S):
+                a0 = len(accs)
+                accs += [{"bufferView": v0, "byteOffset": 60 * i, "componentType": 5126, "count": 5, "type": "VEC3",
+                          "min": [float(v) for v in verts[i].min(axis=0)], "max": [float(v) for v in verts[i].max(axis=0)]},
+                         {"bufferView": v0 + 1, "byteOffset": 20 * i, "componentType": 5121, "normalized": True, "count": 5, "type": "VEC4"},
+                         {"bufferView": v0 + 2, "byteOffset": 36 * i, "componentType": 5123, "count": 18, "type": "SCALAR"}]
+                prims.append({"attributes": {"POSITION": a0, "COLOR_0": a0 + 1}, "indices": a0 + 2, "mode": 4, "material": 0})
+            node["mesh"] = 0
+            gltf["buffers"] = [{"byteLength": len(binary)}]
     js = json.dumps(gltf, separators=(",", ":")).encode("utf-8")
     js += b" " * (-len(js) % 4)
     binary += b"\0" * (-len(binary) % 4)
