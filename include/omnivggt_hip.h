@@ -57,7 +57,8 @@ extern "C" {
  * 12: + point-cloud extraction (ovg_percentile, ovg_point_filter and their *_workspace_bytes queries)
  * 13: + input preprocessing (ovg_resample_frames, ovg_depth_frames, ovg_resample_workspace_bytes)
  *     + voxel-grid decimation (ovg_voxel_downsample, ovg_voxel_downsample_workspace_bytes): entries added, nothing existing changed,
- *       so the number stays; a binding looks the two symbols up by name and reports a library that predates them */
+ *       so the number stays; a binding looks the two symbols up by name and reports a library that predates them
+ *     + point-cloud rendering (ovg_render_points, ovg_render_workspace_bytes): added the same way, looked up by name */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -586,6 +587,45 @@ typedef struct {
 } ovg_voxel_downsample_params;
 int64_t ovg_voxel_downsample_workspace_bytes(int64_t n);
 int ovg_voxel_downsample(const ovg_voxel_downsample_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Point-cloud rendering (added under ABI 13): z-buffered square splats of a coloured cloud into V pinhole views, by an exact rule that
+ * tests/render_twin.py restates in numpy float32 bit for bit.
+ *   points [n][3] f32, colors [n][3] u8 (both may be NULL when n == 0), n < 2^32; cams [V][16] f32 on the device, per view the
+ *   world-to-camera rotation row-major (9), the translation (3), fx, fy, cx, cy: ovg_unproject's `cam` row in the other direction.
+ *   Every step is one f32 operation rounded on its own (no fused multiply-add):
+ *   1. xc = ((R00 x + R01 y) + R02 z) + tx, likewise yc, zc;
+ *   2. the point is skipped for this view unless xc, yc, zc are finite and zc > near;
+ *   3. u = floor((fx (xc / zc) + cx) + 0.5), w = floor((fy (yc / zc) + cy) + 0.5): correctly rounded divisions, pixel centres at
+ *      integer coordinates (ovg_unproject's convention);
+ *   4. skipped unless -radius <= u <= W - 1 + radius and -radius <= w <= H - 1 + radius (compared in f32: NaN fails);
+ *   5. key = (bits(zc) << 32) | i: zc is positive and finite, so its bit pattern orders like its value; ~0 means "empty";
+ *   6. every pixel (u + dx, w + dy), |dx|, |dy| <= radius, inside the image takes min(stored key, key): one 64-bit unsigned atomic
+ *      min. The nearest point wins, equal depths go to the smallest index, and the result does not depend on arrival order;
+ *   7. a non-empty pixel resolves to rgb = colors[key & 0xffffffff], depth = the float whose bits are key >> 32, index = key &
+ *      0xffffffff; an empty one to the background colour, depth 0 and index -1.
+ *   Three launches (fill, splat, resolve); nothing is allocated and nothing is read back: every size is known before the call.
+ *   flags: OVG_RENDER_NO_PREREAD drops the plain read of the pixel in front of the atomic (which skips the atomic when the stored key
+ *   is already smaller; stored keys only decrease, so a stale read is merely conservative). The images are the same either way.
+ *   ws: >= ovg_render_workspace_bytes(V, H, W) bytes (the u64 z-buffer, 8 V H W rounded up to 16), 16-byte aligned; the query returns
+ *   -1 for V, H, W <= 0 or V H W >= 2^31. out_rgb [V][H][W][3] u8; out_depth [V][H][W] f32 and out_index [V][H][W] int64 are optional.
+ *   OVG_E_ARG: NULL params / cams / ws / out_rgb (points / colors with n > 0), n < 0 or >= 2^32, bad V, H, W, radius outside
+ *   [0, OVG_RENDER_MAX_RADIUS], a near plane that is not positive and finite, unknown flags, a misaligned or undersized workspace.
+ * ------------------------------------------------------------------ */
+enum { OVG_RENDER_MAX_RADIUS = 8 };
+enum { OVG_RENDER_NO_PREREAD = 1 };
+typedef struct {
+  const float* points; const uint8_t* colors; int64_t n;
+  const float* cams;
+  int32_t V; int32_t H; int32_t W; int32_t radius;
+  float near;
+  uint8_t background[3]; uint8_t pad0;
+  int32_t flags; int32_t pad1;
+  void* ws; int64_t ws_bytes;
+  uint8_t* out_rgb; float* out_depth; int64_t* out_index;
+} ovg_render_params;
+int64_t ovg_render_workspace_bytes(int32_t V, int32_t H, int32_t W);
+int ovg_render_points(const ovg_render_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

@@ -205,6 +205,16 @@ class VoxelDownsampleParams(C.Structure):
                 ("out_points", vp), ("out_colors", vp), ("out_index", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
+RENDER_MAX_RADIUS = 8
+RENDER_NO_PREREAD = 1
+
+
+class RenderParams(C.Structure):
+    _fields_ = [("points", vp), ("colors", vp), ("n", i64), ("cams", vp), ("V", i32), ("H", i32), ("W", i32), ("radius", i32),
+                ("near", f32), ("background", C.c_uint8 * 3), ("pad0", C.c_uint8), ("flags", i32), ("pad1", i32),
+                ("ws", vp), ("ws_bytes", i64), ("out_rgb", vp), ("out_depth", vp), ("out_index", vp)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -272,6 +282,8 @@ SYMBOLS = {
     # added under ABI 13 without a new number: load() reports a library that predates them by name
     "ovg_voxel_downsample": (i32, [C.POINTER(VoxelDownsampleParams), vp]),
     "ovg_voxel_downsample_workspace_bytes": (i64, [i64]),
+    "ovg_render_points": (i32, [C.POINTER(RenderParams), vp]),
+    "ovg_render_workspace_bytes": (i64, [i32, i32, i32]),
 }
 
 

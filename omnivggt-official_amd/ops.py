@@ -629,3 +629,41 @@ def voxel_downsample(stage, points, voxel, ws, conf=None, colors=None, out_count
     p.out_points, p.out_colors, p.out_index, p.out_count = L.ptr(out_points), L.ptr(out_colors), L.ptr(out_index), L.ptr(out_count)
     p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
     L.call("ovg_voxel_downsample", p, _stream())
+
+
+def render_workspace_bytes(V, H, W):
+    for v in (V, H, W):
+        if not -(1 << 31) <= int(v) < (1 << 31):
+            raise L.OvgError("ovg_render_workspace_bytes: unsupported (V=%d, H=%d, W=%d)" % (V, H, W))
+    b = L.load().ovg_render_workspace_bytes(int(V), int(H), int(W))
+    if b < 0:
+        raise L.OvgError("ovg_render_workspace_bytes: unsupported (V=%d, H=%d, W=%d)" % (V, H, W))
+    return int(b)
+
+
+def render_points(points, colors, cams, H, W, radius=1, near=1e-3, background=(255, 255, 255), depth=True, index=False, ws=None,
+                  flags=0):
+    """ovg_render_points on contiguous device tensors: points f32 [n, 3], colors u8 [n, 3], cams f32 [V, 16] (world-to-camera rotation
+    row-major, translation, fx, fy, cx, cy). -> (rgb u8 [V, H, W, 3], depth f32 [V, H, W] or None, index int64 [V, H, W] or None),
+    allocated here; ws: an optional uint8 device tensor of at least render_workspace_bytes(V, H, W) bytes. Nothing is read back."""
+    _chk_dev(points, colors, cams, ws)
+    if points.dtype != torch.float32 or cams.dtype != torch.float32 or colors.dtype != torch.uint8 or \
+            not (points.is_contiguous() and colors.is_contiguous() and cams.is_contiguous()):
+        raise L.OvgError("render_points: points / cams must be contiguous f32 tensors, colors a contiguous u8 tensor")
+    n, V = points.numel() // 3, cams.numel() // 16
+    if points.numel() != 3 * n or colors.numel() != 3 * n or cams.numel() != 16 * V:
+        raise L.OvgError("render_points: points / colors must hold 3 values per point, cams 16 per view")
+    need = render_workspace_bytes(V, H, W)
+    if ws is None or nbytes(ws) < need:
+        ws = torch.empty(need, device=cams.device, dtype=torch.uint8)
+    rgb = torch.empty(V, H, W, 3, device=cams.device, dtype=torch.uint8)
+    dep = torch.empty(V, H, W, device=cams.device, dtype=torch.float32) if depth else None
+    idx = torch.empty(V, H, W, device=cams.device, dtype=torch.int64) if index else None
+    p = L.RenderParams()
+    p.points, p.colors, p.n, p.cams = L.ptr(points) if n else None, L.ptr(colors) if n else None, n, L.ptr(cams)
+    p.V, p.H, p.W, p.radius, p.near, p.flags = V, int(H), int(W), int(radius), float(near), int(flags)
+    for k in range(3):
+        p.background[k] = int(background[k])
+    p.ws, p.ws_bytes, p.out_rgb, p.out_depth, p.out_index = L.ptr(ws), nbytes(ws), L.ptr(rgb), L.ptr(dep), L.ptr(idx)
+    L.call("ovg_render_points", p, _stream())
+    return rgb, dep, idx

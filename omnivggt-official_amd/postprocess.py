@@ -422,3 +422,139 @@ def write_glb(path, cloud, cameras=False, camera_scale=0.05):
     with open(path, "wb") as fh:
         fh.write(struct.pack("<III", 0x46546C67, 2, 12 + len(chunks)))
         fh.write(chunks)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Headless rendering of a PointCloud (what inference.py hands to viser_wrapper, as images)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class RenderResult:
+    """Result of render_point_cloud: rgb (V,H,W,3) u8, depth (V,H,W) f32 or None, index (V,H,W) int64 or None, device tensors."""
+    __slots__ = ("rgb", "depth", "index")
+
+    def __init__(self, rgb, depth=None, index=None):
+        self.rgb, self.depth, self.index = rgb, depth, index
+
+
+def render_point_cloud(cloud, extrinsic, intrinsic, size, point_radius=1, near=1e-3, background=(255, 255, 255), return_depth=True,
+                       return_index=False):
+    """Draw a PointCloud from V pinhole cameras into 8-bit images on the device (ovg_render_points): every point becomes a square of
+    (2 point_radius + 1)^2 pixels around its rounded projection, the nearest point of a pixel wins, equal depths go to the earliest
+    point. The rule is exact (tests/render_twin.py restates it in numpy float32) and two calls give identical bytes.
+
+    extrinsic: (V,3,4) (or one (3,4)) world-to-camera in the frame of cloud.points -- the untransformed frame predictions["extrinsic"]
+    lives in, not the aligned frame of cloud.transform. intrinsic: (V,3,3), or one (3,3) for all views; fx, fy, cx, cy are read, skew
+    is ignored. Both may be device tensors, numpy arrays or lists; they are rounded to f32 and packed on the device. size: (H, W).
+    Pixel centres sit at integer coordinates (the convention of unproject_depth_map_to_point_map), points with camera depth <= near
+    or a non-finite camera coordinate are not drawn, pixels no point reaches take `background`, depth 0 and index -1.
+
+    -> RenderResult(rgb (V,H,W,3) u8, depth (V,H,W) f32 camera z of the winning point or None, index (V,H,W) int64 or None).
+    index names POSITIONS IN `cloud` (rows of cloud.points), also when the cloud carries `indices`: cloud.indices[index] (where
+    index >= 0) maps on to the pixels of the prediction maps.
+
+    No device -> host synchronisation: every size is known before the launches. An empty cloud returns background images. CPU
+    clouds raise OvgError (there is no CPU fallback); a bad size, point_radius, near or background raises ValueError."""
+    import math
+    import numpy as np
+    L = ops.L
+    try:
+        H, W = (int(v) for v in size)
+        ok = (H, W) == tuple(size) and H > 0 and W > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("render_point_cloud: size must be (H, W), two positive integers, got %r" % (size,))
+    if isinstance(point_radius, bool) or not isinstance(point_radius, (int, np.integer)) or not 0 <= point_radius <= L.RENDER_MAX_RADIUS:
+        raise ValueError("render_point_cloud: point_radius must be an integer in [0, %d], got %r" % (L.RENDER_MAX_RADIUS, point_radius))
+    try:
+        near32 = float(np.float32(near))
+    except (TypeError, ValueError):
+        near32 = float("nan")
+    if not (near32 > 0.0 and math.isfinite(near32)):
+        raise ValueError("render_point_cloud: near must be positive and finite in float32, got %r" % (near,))
+    try:
+        bg = tuple(int(v) for v in background)
+        ok = len(bg) == 3 and all(0 <= v <= 255 for v in bg) and bg == tuple(background)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("render_point_cloud: background must be three integers in [0, 255], got %r" % (background,))
+    ext, intr = torch.as_tensor(extrinsic).detach(), torch.as_tensor(intrinsic).detach()
+    if ext.dim() == 2:
+        ext = ext[None]
+    if ext.dim() != 3 or tuple(ext.shape[1:]) != (3, 4) or ext.shape[0] == 0:
+        raise ValueError("render_point_cloud: extrinsic must be (V, 3, 4), got %r" % (tuple(ext.shape),))
+    V = int(ext.shape[0])
+    if tuple(intr.shape) not in ((3, 3), (V, 3, 3)):
+        raise ValueError("render_point_cloud: intrinsic must be (3, 3) or (V, 3, 3) = (%d, 3, 3), got %r" % (V, tuple(intr.shape)))
+    if V * H * W >= 1 << 31:
+        raise ValueError("render_point_cloud: V * H * W = %d pixels is 2^31 or more; render fewer views per call" % (V * H * W))
+    pts, col = cloud.points, cloud.colors
+    if not (isinstance(pts, torch.Tensor) and pts.is_cuda and isinstance(col, torch.Tensor) and col.is_cuda):
+        raise L.OvgError("render_point_cloud needs HIP device tensors: there is no CPU fallback")
+    M = int(pts.shape[0])
+    if M >= 1 << 32:
+        raise ValueError("render_point_cloud: the cloud has 2^32 points or more")
+    dev = pts.device
+    ext = ext.to(device=dev, dtype=torch.float32)
+    intr = intr.to(device=dev, dtype=torch.float32).expand(V, 3, 3)
+    cams = torch.cat([ext[:, :, :3].reshape(V, 9), ext[:, :, 3], intr[:, 0, 0:1], intr[:, 1, 1:2], intr[:, 0, 2:3], intr[:, 1, 2:3]],
+                     dim=1).contiguous()
+    rgb, depth, index = ops.render_points(pts.reshape(M, 3).float().contiguous(), col.reshape(M, 3).contiguous(), cams, H, W,
+                                          radius=int(point_radius), near=near32, background=bg, depth=return_depth, index=return_index)
+    return RenderResult(rgb, depth, index)
+
+
+def orbit_cameras(extrinsic0, centre, n, axis=None):
+    """n world-to-camera (3,4) extrinsics on a circle: camera k is camera 0 moved rigidly by a rotation of 2 pi k / n about the line
+    through `centre` along `axis` -- E_k = E_0 T(centre) R_axis(-theta_k) T(-centre) in 4x4 matrices, so E_0 comes back for k = 0,
+    every camera keeps its distance to `centre` and sees `centre` at the same place in its image. axis: a world direction, by
+    default camera 0's up direction (minus the second row of its rotation: image y points down). Host only: float64 numpy in,
+    (n, 3, 4) float64 numpy out; device tensors are copied to the host."""
+    import numpy as np
+
+    def host(a):
+        return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+
+    e0 = np.eye(4)
+    e0[:3, :4] = host(extrinsic0).reshape(3, 4)
+    c = host(centre).reshape(3)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("orbit_cameras: n must be a positive integer, got %r" % (n,))
+    a = -e0[1, :3] if axis is None else host(axis).reshape(3)
+    norm = float(np.linalg.norm(a))
+    if not (norm > 0.0 and np.isfinite(norm)):
+        raise ValueError("orbit_cameras: the axis must be a finite non-zero vector, got %r" % (a.tolist(),))
+    a = a / norm
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    t_in, t_out = np.eye(4), np.eye(4)
+    t_in[:3, 3], t_out[:3, 3] = -c, c
+    out = np.empty((int(n), 3, 4))
+    for k in range(int(n)):
+        th = -2.0 * np.pi * k / int(n)
+        rot = np.eye(4)
+        rot[:3, :3] = np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)      # Rodrigues
+        out[k] = (e0 @ t_out @ rot @ t_in)[:3]
+    return out
+
+
+def cloud_centre(cloud):
+    """(3,) f32 device tensor: the per-axis median of cloud.points (ovg_percentile with q = 50: numpy's linear percentile, exact and
+    deterministic), a robust centre for orbit_cameras. A NaN coordinate anywhere makes that axis NaN, as in numpy."""
+    pts = cloud.points
+    if not (isinstance(pts, torch.Tensor) and pts.is_cuda):
+        raise ops.L.OvgError("cloud_centre needs HIP device tensors: there is no CPU fallback")
+    M = int(pts.shape[0])
+    if M == 0:
+        raise ValueError("cloud_centre of an empty cloud")
+    return ops.percentile(pts.reshape(M, 3).float().contiguous(), M, 3, 1, 3, [50.0]).reshape(3)
+
+
+def write_png(path, image):
+    """One (H, W, 3) u8 image (a device or host tensor, or an array) as an 8-bit RGB PNG, through Pillow."""
+    import numpy as np
+    from PIL import Image
+    a = image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("write_png: expected one (H, W, 3) uint8 image, got %s %r" % (a.dtype, a.shape))
+    Image.fromarray(np.ascontiguousarray(a)).save(path, format="PNG")
