@@ -58,7 +58,8 @@ extern "C" {
  * 13: + input preprocessing (ovg_resample_frames, ovg_depth_frames, ovg_resample_workspace_bytes)
  *     + voxel-grid decimation (ovg_voxel_downsample, ovg_voxel_downsample_workspace_bytes): entries added, nothing existing changed,
  *       so the number stays; a binding looks the two symbols up by name and reports a library that predates them
- *     + point-cloud rendering (ovg_render_points, ovg_render_workspace_bytes): added the same way, looked up by name */
+ *     + point-cloud rendering (ovg_render_points, ovg_render_workspace_bytes): added the same way, looked up by name
+ *     + multi-view depth consistency (ovg_multiview_consistency, ovg_consistency_workspace_bytes): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -626,6 +627,51 @@ typedef struct {
 } ovg_render_params;
 int64_t ovg_render_workspace_bytes(int32_t V, int32_t H, int32_t W);
 int ovg_render_points(const ovg_render_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Multi-view depth consistency (added under ABI 13): for every pixel of S point maps, the number of OTHER views that confirm it, look
+ * through it, or cannot see it, by an exact rule that tests/consistency_twin.py restates in numpy float32 bit for bit.
+ *   points [S][H][W][3] f32 world points (a point map, or un-projected depth); cams [S][16] f32 on the device, packed exactly as for
+ *   ovg_render_points (world-to-camera rotation row-major, translation, fx, fy, cx, cy); valid [S][H][W] u8, optional (NULL: all valid).
+ *   Every step is one f32 operation rounded on its own (no fused multiply-add):
+ *   1. own depth z[j][q] = ((c6 x + c7 y) + c8 z) + c11 with c = cams[j], (x, y, z) = points[j][q]. Pixel (j, q) is USABLE when
+ *      valid[j][q] != 0 (if given), z[j][q] is finite and z[j][q] > near (a non-finite coordinate makes z non-finite);
+ *   2. for a usable source pixel (i, p) and every other view j != i: the camera coordinates xc, yc, zc of points[i][p] in view j, the
+ *      finiteness / zc > near test and the pixel u = floor((fx (xc / zc) + cx) + 0.5), w likewise: rules 1-3 of ovg_render_points.
+ *      The pair is skipped unless 0 <= u <= W - 1 and 0 <= w <= H - 1 (compared in f32: NaN fails) and (j, (w, u)) is usable;
+ *   3. d = z[j][(w, u)], band = tol * d, diff = zc - d. Exactly one of: |diff| <= band -> SUPPORT; diff < -band -> VIOLATION (view j
+ *      sees a surface behind the point along that ray: it looks through the point); diff > band -> OCCLUDED (the point is hidden
+ *      from view j: no evidence either way);
+ *   4. support / violations / occluded [src_count][H][W] int16: the number of views j in each class for the source views src_first ..
+ *      src_first + src_count - 1 (row 0 of the outputs is view src_first). A source pixel that is not usable has all three 0; pairs
+ *      skipped in step 2 count nowhere. occluded may be NULL.
+ *   Nearest-pixel lookup only: no bilinear depth, no neighbourhood search, no averaging of depths across views.
+ *   Two launches: the maps z (unusable pixels as NaN) into ws, then one thread per source pixel with the targets in a loop, counters
+ *   in registers, plain stores. No atomics, nothing allocated, nothing read back; two calls give identical bytes. All S views are
+ *   targets whatever the source range; OVG_MVC_KEEP_MAP skips the first launch (ws still holds the maps of an earlier call with the
+ *   same points, cams, valid, near and shape: a large job cut into source ranges computes them once).
+ *   tile: the 256 source pixels of a workgroup as width x height (OVG_MVC_TILE_DEFAULT is the measured best);
+ *   OVG_MVC_ROTATE_TARGETS lets each source view start with the target behind it instead of all walking 0 .. S - 1. Both change
+ *   speed only, never a result.
+ *   ws: >= ovg_consistency_workspace_bytes(S, H, W) bytes (4 S H W rounded up to 16), 16-byte aligned; the query returns -1 for
+ *   S, H, W <= 0, S > OVG_MVC_MAX_VIEWS (int16 counts) or S H W >= 2^31.
+ *   OVG_E_ARG: NULL params / points / cams / ws / support / violations, bad S, H, W, a source range outside [0, S) or empty, tol
+ *   negative or not finite, a near plane that is not positive and finite, unknown tile / flags, a misaligned or undersized workspace.
+ * ------------------------------------------------------------------ */
+enum { OVG_MVC_MAX_VIEWS = 32767 };
+enum { OVG_MVC_TILE_DEFAULT = 0, OVG_MVC_TILE_256x1 = 1, OVG_MVC_TILE_16x16 = 2, OVG_MVC_TILE_8x32 = 3, OVG_MVC_TILE_32x8 = 4 };
+enum { OVG_MVC_ROTATE_TARGETS = 1, OVG_MVC_KEEP_MAP = 2 };
+typedef struct {
+  const float* points; const float* cams; const uint8_t* valid;
+  int32_t S; int32_t H; int32_t W;
+  int32_t src_first; int32_t src_count;
+  float tol; float near;
+  int32_t tile; int32_t flags; int32_t pad;
+  void* ws; int64_t ws_bytes;
+  int16_t* support; int16_t* violations; int16_t* occluded;
+} ovg_consistency_params;
+int64_t ovg_consistency_workspace_bytes(int32_t S, int32_t H, int32_t W);
+int ovg_multiview_consistency(const ovg_consistency_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

@@ -1,18 +1,17 @@
 // Point-cloud rendering (ovg_render_points): z-buffered square splats of a coloured cloud into V pinhole views, the headless stand-in
 // for the reference's interactive viewer (inference.py: viser_wrapper). Three launches: fill the u64 z-buffer with ~0, splat (one
 // 64-bit unsigned atomic min per covered pixel), resolve to rgb / depth / index. The splat is bound by its atomics, not by arithmetic.
-#include "ovg_common.h"
+#include "ovg_project.h"
 
-// the projection restates tests/render_twin.py's numpy float32 expression operation for operation: no fused multiply-adds in this
-// unit. The pragma covers the code below; build.py also compiles the unit with -ffp-contract=off (as for ovg_pointcloud.hip)
+// the projection (ovg_project.h, shared with ovg_consistency.hip) restates tests/render_twin.py's numpy float32 expression operation
+// for operation: no fused multiply-adds in this unit. The pragma covers the code below; build.py also compiles the unit with
+// -ffp-contract=off (as for ovg_pointcloud.hip)
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr uint64_t kEmpty = ~0ull;                  // bits(zc) of a finite positive float never reach 0xFFFFFFFF
-
-OVG_DEV bool finite_f32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
 
 int64_t rd_pixels(int64_t V, int64_t H, int64_t W) { return V * H * W; }
 int64_t rd_ws_bytes(int64_t V, int64_t H, int64_t W) { return (rd_pixels(V, H, W) * 8 + 15) / 16 * 16; }
@@ -38,13 +37,8 @@ __global__ __launch_bounds__(kThreads) void rd_splat(const float* __restrict__ p
   const float lo = (float)-r, hi_u = (float)(W - 1 + r), hi_w = (float)(H - 1 + r);    // small integers: exact in f32
   const int64_t hw = (int64_t)H * W;
   for (int32_t v = 0; v < V; ++v) {
-    const float* c = cams + 16 * (int64_t)v;
-    const float xc = ((c[0] * x + c[1] * y) + c[2] * z) + c[9];
-    const float yc = ((c[3] * x + c[4] * y) + c[5] * z) + c[10];
-    const float zc = ((c[6] * x + c[7] * y) + c[8] * z) + c[11];
-    if (!(finite_f32(xc) && finite_f32(yc) && finite_f32(zc) && zc > near)) continue;
-    const float u = floorf((c[12] * __fdiv_rn(xc, zc) + c[14]) + 0.5f);
-    const float w = floorf((c[13] * __fdiv_rn(yc, zc) + c[15]) + 0.5f);
+    float zc, u, w;
+    if (!project_point(cams + 16 * (int64_t)v, x, y, z, near, zc, u, w)) continue;
     if (!(u >= lo && u <= hi_u && w >= lo && w <= hi_w)) continue;         // NaN fails; past this line the conversions are in range
     const int32_t px = (int32_t)u, py = (int32_t)w;
     const uint64_t key = ((uint64_t)__float_as_uint(zc) << 32) | (uint32_t)i;

@@ -215,6 +215,17 @@ class RenderParams(C.Structure):
                 ("ws", vp), ("ws_bytes", i64), ("out_rgb", vp), ("out_depth", vp), ("out_index", vp)]
 
 
+MVC_MAX_VIEWS = 32767
+MVC_TILE_DEFAULT, MVC_TILE_256x1, MVC_TILE_16x16, MVC_TILE_8x32, MVC_TILE_32x8 = 0, 1, 2, 3, 4
+MVC_ROTATE_TARGETS, MVC_KEEP_MAP = 1, 2
+
+
+class ConsistencyParams(C.Structure):
+    _fields_ = [("points", vp), ("cams", vp), ("valid", vp), ("S", i32), ("H", i32), ("W", i32), ("src_first", i32), ("src_count", i32),
+                ("tol", f32), ("near", f32), ("tile", i32), ("flags", i32), ("pad", i32), ("ws", vp), ("ws_bytes", i64),
+                ("support", vp), ("violations", vp), ("occluded", vp)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -284,6 +295,8 @@ SYMBOLS = {
     "ovg_voxel_downsample_workspace_bytes": (i64, [i64]),
     "ovg_render_points": (i32, [C.POINTER(RenderParams), vp]),
     "ovg_render_workspace_bytes": (i64, [i32, i32, i32]),
+    "ovg_multiview_consistency": (i32, [C.POINTER(ConsistencyParams), vp]),
+    "ovg_consistency_workspace_bytes": (i64, [i32, i32, i32]),
 }
 
 

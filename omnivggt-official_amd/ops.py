@@ -667,3 +667,47 @@ def render_points(points, colors, cams, H, W, radius=1, near=1e-3, background=(2
     p.ws, p.ws_bytes, p.out_rgb, p.out_depth, p.out_index = L.ptr(ws), nbytes(ws), L.ptr(rgb), L.ptr(dep), L.ptr(idx)
     L.call("ovg_render_points", p, _stream())
     return rgb, dep, idx
+
+
+def consistency_workspace_bytes(S, H, W):
+    for v in (S, H, W):
+        if not -(1 << 31) <= int(v) < (1 << 31):
+            raise L.OvgError("ovg_consistency_workspace_bytes: unsupported (S=%d, H=%d, W=%d)" % (S, H, W))
+    b = L.load().ovg_consistency_workspace_bytes(int(S), int(H), int(W))
+    if b < 0:
+        raise L.OvgError("ovg_consistency_workspace_bytes: unsupported (S=%d, H=%d, W=%d)" % (S, H, W))
+    return int(b)
+
+
+def multiview_consistency(points, cams, tol, near=1e-3, valid=None, src_first=0, src_count=None, occluded=False, ws=None,
+                          tile=L.MVC_TILE_DEFAULT, flags=0):
+    """ovg_multiview_consistency on contiguous device tensors: points f32 [S, H, W, 3], cams f32 [S, 16] (packed as for render_points),
+    valid u8 [S, H, W] or None. -> (support, violations, occluded or None), int16 [src_count, H, W] for the source views src_first ..
+    src_first + src_count - 1 (all S by default), allocated here; ws: an optional uint8 device tensor of at least
+    consistency_workspace_bytes(S, H, W) bytes (with L.MVC_KEEP_MAP in flags: the one an earlier call on the same inputs filled).
+    Nothing is read back."""
+    _chk_dev(points, cams, valid, ws)
+    if points.dtype != torch.float32 or cams.dtype != torch.float32 or not (points.is_contiguous() and cams.is_contiguous()):
+        raise L.OvgError("multiview_consistency: points / cams must be contiguous f32 tensors")
+    if points.dim() != 4 or points.shape[3] != 3 or cams.numel() != 16 * points.shape[0]:
+        raise L.OvgError("multiview_consistency: points must be [S, H, W, 3], cams hold 16 values per view")
+    S, H, W = (int(v) for v in points.shape[:3])
+    if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or tuple(valid.shape) != (S, H, W)):
+        raise L.OvgError("multiview_consistency: valid must be a contiguous u8 tensor [S, H, W]")
+    n = S - src_first if src_count is None else int(src_count)
+    if not (0 <= src_first < S and 0 < n <= S - src_first):
+        raise L.OvgError("multiview_consistency: source views %d .. %d outside [0, %d)" % (src_first, src_first + n - 1, S))
+    need = consistency_workspace_bytes(S, H, W)
+    if ws is None or nbytes(ws) < need:
+        if flags & L.MVC_KEEP_MAP:
+            raise L.OvgError("multiview_consistency: MVC_KEEP_MAP needs the workspace of the call that computed the maps")
+        ws = torch.empty(need, device=points.device, dtype=torch.uint8)
+    sup = torch.empty(n, H, W, device=points.device, dtype=torch.int16)
+    vio = torch.empty(n, H, W, device=points.device, dtype=torch.int16)
+    occ = torch.empty(n, H, W, device=points.device, dtype=torch.int16) if occluded else None
+    p = L.ConsistencyParams()
+    p.points, p.cams, p.valid, p.S, p.H, p.W = L.ptr(points), L.ptr(cams), L.ptr(valid), S, H, W
+    p.src_first, p.src_count, p.tol, p.near, p.tile, p.flags = int(src_first), n, float(tol), float(near), int(tile), int(flags)
+    p.ws, p.ws_bytes, p.support, p.violations, p.occluded = L.ptr(ws), nbytes(ws), L.ptr(sup), L.ptr(vio), L.ptr(occ)
+    L.call("ovg_multiview_consistency", p, _stream())
+    return sup, vio, occ

@@ -133,9 +133,40 @@ def scene_alignment(extrinsic0):
     return np.linalg.inv(e) @ np.diag([1.0, -1.0, -1.0, 1.0]) @ np.diag([-1.0, 1.0, -1.0, 1.0])
 
 
+def _prediction_geometry(predictions, prediction_mode, b, images, want_intrinsic=False):
+    """The maps and cameras predictions_to_point_cloud and prediction_consistency work on, for batch element b of the dict
+    OmniVGGT.forward returns (images: its `images` with the batch dimension): "Pointmap" modes take world_points / world_points_conf
+    (world_points_from_depth / depth_conf when the dict has no world_points), other modes world_points_from_depth / depth_conf, decoded
+    from pose_enc and un-projected here on the device when absent. -> (points, confidence tensor WITH its batch dimension or None,
+    extrinsic (S,3,4), intrinsic (S,3,3) or None when not asked for)."""
+    H, W = images.shape[-2], images.shape[-1]
+    extrinsic = predictions["extrinsic"][b] if "extrinsic" in predictions else None
+    intrinsic = predictions["intrinsic"][b] if want_intrinsic and "intrinsic" in predictions else None
+    if "Pointmap" in prediction_mode and "world_points" in predictions:
+        pts, conf = predictions["world_points"][b], predictions.get("world_points_conf")
+    elif "world_points_from_depth" in predictions:
+        pts, conf = predictions["world_points_from_depth"][b], predictions.get("depth_conf")
+    else:
+        sub = {"depth": predictions["depth"][b:b + 1], "pose_enc": predictions["pose_enc"][b:b + 1], "images": images[b:b + 1]}
+        get_world_points_from_depth(sub)
+        pts, conf = sub["world_points_from_depth"][0], predictions.get("depth_conf")
+        if extrinsic is None:
+            extrinsic = sub["extrinsic"][0]
+        if want_intrinsic and intrinsic is None:
+            intrinsic = sub["intrinsic"][0]
+    if extrinsic is None or (want_intrinsic and intrinsic is None):
+        if "pose_enc" not in predictions:
+            raise ValueError("predictions carry neither `extrinsic`%s nor `pose_enc`: the cameras are needed"
+                             % (" / `intrinsic`" if want_intrinsic else ""))
+        ext, intr = pose_encoding_to_extri_intri(predictions["pose_enc"][b:b + 1], (H, W))
+        extrinsic = ext[0] if extrinsic is None else extrinsic
+        intrinsic = intr[0] if want_intrinsic and intrinsic is None else intrinsic
+    return pts, conf, extrinsic, intrinsic
+
+
 def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="all", mask_black_bg=False, mask_white_bg=False,
                                prediction_mode="Predicted Pointmap", sky_mask=None, min_conf=1e-5, batch_index=0, return_indices=False,
-                               return_conf=False):
+                               return_conf=False, keep_mask=None):
     """The point cloud of visual_util.predictions_to_glb (:77-267) on the device, for the dict OmniVGGT.forward returns (batch dimension
     included; batch_index=0 is what the reference's select_first_batch keeps).
 
@@ -150,6 +181,10 @@ def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="a
     scene_scale is ||P95 - P5|| of the kept, untransformed vertices; transform is inv(E0) @ diag(1,-1,-1,1) @ R_y(180) with E0 the
     first selected camera, which the writers apply (the vertices themselves are copied untransformed).
     return_conf: PointCloud.conf holds the kept pixels' confidence after the sky-mask rule (what voxel_downsample ranks by).
+    keep_mask: an (S, H, W) bool device tensor (e.g. consistency_mask(...)); pixels where it is False are dropped. Unlike sky_mask it
+    does not enter the percentile: the threshold is computed first, on the same values as without it, then the dropped pixels take
+    confidence -inf for the filter launches (conf >= threshold and conf > min_conf fails for -inf, also when conf_thres == 0).
+    return_conf still reports the original confidences; scene_scale is computed on the kept points. None takes the path without it.
 
     One divergence: an empty selection returns M = 0 (scene_scale 1); the reference substitutes one white point at (1, 0, 0).
     Exactly one device -> host synchronisation: reading M (with the first selected camera) to size the result. CPU tensors raise
@@ -169,23 +204,14 @@ def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="a
     S, H, W = images.shape[1], images.shape[-2], images.shape[-1]
     if sky_mask is not None and tuple(sky_mask.shape) != (S, H, W):
         raise ValueError("sky_mask must be (S, H, W) = %r at the map size, got %r" % ((S, H, W), tuple(sky_mask.shape)))
+    if keep_mask is not None:
+        if not isinstance(keep_mask, torch.Tensor) or keep_mask.dtype != torch.bool or tuple(keep_mask.shape) != (S, H, W):
+            raise ValueError("keep_mask must be a bool tensor (S, H, W) = %r at the map size" % ((S, H, W),))
     if not images.is_cuda:
         raise L.OvgError("predictions_to_point_cloud needs HIP device tensors: there is no CPU fallback")
-    extrinsic = predictions["extrinsic"][b] if "extrinsic" in predictions else None
-    if "Pointmap" in prediction_mode and "world_points" in predictions:
-        pts, conf = predictions["world_points"][b], predictions.get("world_points_conf")
-    elif "world_points_from_depth" in predictions:
-        pts, conf = predictions["world_points_from_depth"][b], predictions.get("depth_conf")
-    else:
-        sub = {"depth": predictions["depth"][b:b + 1], "pose_enc": predictions["pose_enc"][b:b + 1], "images": images[b:b + 1]}
-        get_world_points_from_depth(sub)
-        pts, conf = sub["world_points_from_depth"][0], predictions.get("depth_conf")
-        if extrinsic is None:
-            extrinsic = sub["extrinsic"][0]
-    if extrinsic is None:
-        if "pose_enc" not in predictions:
-            raise ValueError("predictions carry neither `extrinsic` nor `pose_enc`: the scene alignment needs the cameras")
-        extrinsic = pose_encoding_to_extri_intri(predictions["pose_enc"][b:b + 1], (H, W))[0][0]
+    if keep_mask is not None and not keep_mask.is_cuda:
+        raise L.OvgError("predictions_to_point_cloud needs HIP device tensors: there is no CPU fallback")
+    pts, conf, extrinsic, _ = _prediction_geometry(predictions, prediction_mode, b, images)
     conf = torch.ones(S, H, W, device=images.device, dtype=torch.float32) if conf is None else conf[b]
     for t in (pts, conf, extrinsic):
         if not t.is_cuda:
@@ -205,6 +231,7 @@ def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="a
         sl = slice(frame, frame + 1)
         pts, conf, img, extrinsic = pts[sl], conf[sl], img[sl], extrinsic[sl]
         mask = None if mask is None else mask[sl]
+        keep_mask = None if keep_mask is None else keep_mask[sl]
         base = frame * H * W
     n, hw = conf.numel(), H * W
     dev = conf.device
@@ -219,7 +246,9 @@ def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="a
     flags = (L.PF_BLACK_BG if mask_black_bg else 0) | (L.PF_WHITE_BG if mask_white_bg else 0)
     ws = torch.empty(ops.point_filter_workspace_bytes(n), device=dev, dtype=torch.uint8)
     count = torch.empty(1, device=dev, dtype=torch.int64)
-    args = dict(conf=cf, images=img, points=pts, hw=hw, ws=ws, threshold=thr, mask=mk, min_conf=min_conf, flags=flags, index_base=base)
+    # the threshold above saw the confidences as they are; only the filter launches see the dropped pixels at -inf
+    cf_filter = cf if keep_mask is None else torch.where(keep_mask.reshape(-1), cf, cf.new_full((), float("-inf")))
+    args = dict(conf=cf_filter, images=img, points=pts, hw=hw, ws=ws, threshold=thr, mask=mk, min_conf=min_conf, flags=flags, index_base=base)
     ops.point_filter(L.PF_COUNT, out_count=count, **args)
     # the one synchronisation: the cloud size and the first selected camera in one copy (int64 counts are exact in float64 below 2^53)
     host = torch.cat([count.double(), extrinsic[0].reshape(-1).double()]).cpu().numpy()
@@ -239,6 +268,114 @@ def predictions_to_point_cloud(predictions, conf_thres=50.0, filter_by_frames="a
         out_conf = cf[local] if mk is None else cf[local] * (mk[local] > 0.1).to(torch.float32)      # the kernels' rule: inf * 0 is NaN
     return PointCloud(out_pts, out_col, conf_threshold, scale, transform, extrinsic, out_idx if return_indices else None, out_conf)
 
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Multi-view depth consistency: which pixels do the other views agree with (ovg_multiview_consistency)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class ConsistencyResult:
+    """Result of multiview_consistency: support, violations (S,H,W) int16 device tensors ((1,H,W) for frame=k), occluded likewise or
+    None. Per pixel, the number of other views that confirm it / look through it / cannot see it."""
+    __slots__ = ("support", "violations", "occluded")
+
+    def __init__(self, support, violations, occluded=None):
+        self.support, self.violations, self.occluded = support, violations, occluded
+
+
+def _pack_cams(extrinsic, intrinsic, V, dev):
+    """(V,16) f32 rows as ovg_render_points reads them: rotation row-major, translation, fx, fy, cx, cy; inputs rounded to f32 first."""
+    ext = extrinsic.to(device=dev, dtype=torch.float32)
+    intr = intrinsic.to(device=dev, dtype=torch.float32).expand(V, 3, 3)
+    return torch.cat([ext[:, :, :3].reshape(V, 9), ext[:, :, 3], intr[:, 0, 0:1], intr[:, 1, 1:2], intr[:, 0, 2:3], intr[:, 1, 2:3]],
+                     dim=1).contiguous()
+
+
+def multiview_consistency(points, extrinsic, intrinsic, valid=None, rel_tol=0.02, near=1e-3, frame=None, return_occluded=False):
+    """Geometric consistency of S point maps with their S cameras on the device (ovg_multiview_consistency): every pixel's 3-D point
+    is projected into each other view (the projection of render_point_cloud, nearest pixel) and its depth zc there is compared with
+    the depth d that view holds along the ray. |zc - d| <= rel_tol * d counts as support, zc < d - rel_tol * d as a violation (the
+    other view sees a surface behind the point: it looks through it -- a floater), zc > d + rel_tol * d as occluded (no evidence).
+    Pairs that leave the frame, fall behind the camera or nearer than `near`, or hit an unusable pixel count nowhere. The rule is
+    exact (tests/consistency_twin.py restates it in numpy float32) and two calls give identical bytes. Nearest-pixel lookup only: no
+    bilinear depth, no neighbourhood search, no averaging of depths across views.
+
+    points: (S,H,W,3) f32 device tensor, world points in the frame of `extrinsic` (world_points, or world_points_from_depth).
+    extrinsic (S,3,4) world-to-camera, intrinsic (S,3,3) or one (3,3): device tensors, numpy arrays or lists, rounded to f32 and
+    packed as render_point_cloud packs them. valid: optional (S,H,W) bool / u8 tensor; pixels where it is 0 are neither sources nor
+    targets. frame=k computes source view k only (all views stay targets): the cheap form for filter_by_frames.
+    rel_tol = 0.02 is the knee measured on ground-truth depth of a real four-view scene (tests/golden/real/infinigen_294: support
+    >= 1 for 83 % of the valid pixels, a violation for 1.5 %; halving it loses a fifth of the support, doubling it gains nothing),
+    not on predictions of a trained checkpoint: predicted depth is noisier, so treat it as a lower bound.
+
+    -> ConsistencyResult(support, violations, occluded or None). No device -> host synchronisation. CPU tensors raise OvgError (there
+    is no CPU fallback); bad shapes, frame, rel_tol or near raise ValueError."""
+    import math
+    import numpy as np
+    L = ops.L
+    if not isinstance(points, torch.Tensor) or points.dim() != 4 or points.shape[3] != 3 or 0 in points.shape:
+        raise ValueError("multiview_consistency: points must be a (S, H, W, 3) tensor")
+    S, H, W = (int(v) for v in points.shape[:3])
+    if S > L.MVC_MAX_VIEWS or S * H * W >= 1 << 31:
+        raise ValueError("multiview_consistency: S = %d views of %d x %d exceed S <= %d, S * H * W < 2^31" % (S, H, W, L.MVC_MAX_VIEWS))
+    ext, intr = torch.as_tensor(extrinsic).detach(), torch.as_tensor(intrinsic).detach()
+    if tuple(ext.shape) != (S, 3, 4):
+        raise ValueError("multiview_consistency: extrinsic must be (S, 3, 4) = (%d, 3, 4), got %r" % (S, tuple(ext.shape)))
+    if tuple(intr.shape) not in ((3, 3), (S, 3, 3)):
+        raise ValueError("multiview_consistency: intrinsic must be (3, 3) or (S, 3, 3) = (%d, 3, 3), got %r" % (S, tuple(intr.shape)))
+    if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (S, H, W)
+                              or valid.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError("multiview_consistency: valid must be a bool / uint8 tensor (S, H, W) = %r" % ((S, H, W),))
+    try:
+        with np.errstate(over="ignore"):
+            tol32, near32 = float(np.float32(rel_tol)), float(np.float32(near))
+    except (TypeError, ValueError):
+        tol32 = near32 = float("nan")
+    if not (tol32 >= 0.0 and math.isfinite(tol32)):
+        raise ValueError("multiview_consistency: rel_tol must be non-negative and finite in float32, got %r" % (rel_tol,))
+    if not (near32 > 0.0 and math.isfinite(near32)):
+        raise ValueError("multiview_consistency: near must be positive and finite in float32, got %r" % (near,))
+    if frame is not None and (isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not -S <= frame < S):
+        raise ValueError("multiview_consistency: frame %r out of range for %d views" % (frame, S))
+    if not points.is_cuda or (valid is not None and not valid.is_cuda):
+        raise L.OvgError("multiview_consistency needs HIP device tensors: there is no CPU fallback")
+    dev = points.device
+    cams = _pack_cams(ext, intr, S, dev)
+    if valid is not None:
+        valid = (valid.to(torch.uint8) if valid.dtype == torch.bool else valid).contiguous()
+    first, count = (0, S) if frame is None else (int(frame) % S, 1)
+    sup, vio, occ = ops.multiview_consistency(points.float().contiguous(), cams, tol32, near=near32, valid=valid, src_first=first,
+                                              src_count=count, occluded=return_occluded)
+    return ConsistencyResult(sup, vio, occ)
+
+
+def prediction_consistency(predictions, prediction_mode="Predicted Pointmap", batch_index=0, valid=None, **kw):
+    """multiview_consistency of the dict OmniVGGT.forward returns: the points by the same choices predictions_to_point_cloud makes for
+    `prediction_mode` (world_points, or world_points_from_depth, decoding pose_enc and un-projecting on the device when the dict
+    lacks them), the cameras from `extrinsic` / `intrinsic` of the dict, else decoded from pose_enc. **kw: rel_tol, near, frame,
+    return_occluded. -> ConsistencyResult; consistency_mask(result) is the keep_mask of predictions_to_point_cloud."""
+    if not isinstance(predictions, dict):
+        raise ValueError("predictions must be a dictionary")
+    images = predictions["images"]
+    if images.dim() == 4:
+        images = images.unsqueeze(0)
+    B = images.shape[0]
+    if not isinstance(batch_index, int) or not 0 <= batch_index < B:
+        raise ValueError("batch_index %r out of range for a batch of %d" % (batch_index, B))
+    if not images.is_cuda:
+        raise ops.L.OvgError("prediction_consistency needs HIP device tensors: there is no CPU fallback")
+    S, H, W = images.shape[1], images.shape[-2], images.shape[-1]
+    pts, _, extrinsic, intrinsic = _prediction_geometry(predictions, prediction_mode, batch_index, images, want_intrinsic=True)
+    return multiview_consistency(pts.reshape(S, H, W, 3), extrinsic, intrinsic, valid=valid, **kw)
+
+
+def consistency_mask(result, min_support=1, max_violations=0):
+    """(S,H,W) bool: pixels that at least `min_support` other views confirm and at most `max_violations` look through."""
+    return (result.support >= min_support) & (result.violations <= max_violations)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Voxel-grid decimation and the PLY / GLB writers
+# ---------------------------------------------------------------------------------------------------------------------------------
 
 def voxel_downsample(cloud, voxel_size=None, rel_size=None, conf=None):
     """Voxel-grid decimation of a PointCloud on the device (ovg_voxel_downsample): one point per occupied cell of a regular grid.
@@ -496,10 +633,7 @@ def render_point_cloud(cloud, extrinsic, intrinsic, size, point_radius=1, near=1
     if M >= 1 << 32:
         raise ValueError("render_point_cloud: the cloud has 2^32 points or more")
     dev = pts.device
-    ext = ext.to(device=dev, dtype=torch.float32)
-    intr = intr.to(device=dev, dtype=torch.float32).expand(V, 3, 3)
-    cams = torch.cat([ext[:, :, :3].reshape(V, 9), ext[:, :, 3], intr[:, 0, 0:1], intr[:, 1, 1:2], intr[:, 0, 2:3], intr[:, 1, 2:3]],
-                     dim=1).contiguous()
+    cams = _pack_cams(ext, intr, V, dev)
     rgb, depth, index = ops.render_points(pts.reshape(M, 3).float().contiguous(), col.reshape(M, 3).contiguous(), cams, H, W,
                                           radius=int(point_radius), near=near32, background=bg, depth=return_depth, index=return_index)
     return RenderResult(rgb, depth, index)
