@@ -251,13 +251,14 @@ def attn_merge(a, lse_a, b, lse_b, dtype, out=None):
     return ret
 
 
-def pack_weights(src, dtype, k_pad=None):
-    """f32 [rows, k] (any trailing dims flattened) -> dtype [rows, k_pad] on the device, zero padded."""
+def pack_weights(src, dtype, k_pad=None, out=None):
+    """f32 [rows, k] (any trailing dims flattened) -> dtype [rows, k_pad] on the device, zero padded (out: optional caller storage, row stride allowed)."""
     _chk_dev(src)
     s2 = src.detach().reshape(src.shape[0], -1).float().contiguous()
     rows, k = s2.shape
     k_pad = k if k_pad is None else k_pad
-    out = empty_like_dtype((rows, k_pad), dtype, src.device)
+    if out is None:
+        out = empty_like_dtype((rows, k_pad), dtype, src.device)
     o_hi, o_lo = hi_lo(out)
     p = L.PackWeightsParams(L.ptr(s2), s2.stride(0), L.ptr(o_hi), o_hi.stride(0), rows, k, k_pad, L.dtype_code(dtype), L.ptr(o_lo))
     L.call("ovg_pack_weights", p, _stream())
@@ -286,11 +287,20 @@ def heads_to_tokens(x, n, dtype, out=None):
     return out
 
 
-def im2col_rgb(images, dtype, k_pad=640, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+def copy_rows(x, y):
+    """y[r, :n] = x[r, :n] for f32 row-strided views x, y [rows, n] (ovg_copy_rows)."""
+    _chk_dev(x, y)
+    p = L.CopyRowsParams(L.ptr(x), x.stride(0), L.ptr(y), y.stride(0), x.shape[0], x.shape[1])
+    L.call("ovg_copy_rows", p, _stream())
+    return y
+
+
+def im2col_rgb(images, dtype, k_pad=640, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), out=None):
     """images f32 [V,3,H,W] -> [V*gh*gw, k_pad] normalised patches."""
     _chk_dev(images)
     V, Cc, Hp, Wp = images.shape
-    out = empty_like_dtype((V * (Hp // 14) * (Wp // 14), k_pad), dtype, images.device)
+    if out is None:            # caller storage must be dense [V*gh*gw, k_pad]
+        out = empty_like_dtype((V * (Hp // 14) * (Wp // 14), k_pad), dtype, images.device)
     o_hi, o_lo = hi_lo(out)
     p = L.Im2colParams()
     p.img, p.out, p.k_pad, p.V, p.C, p.Hpx, p.Wpx = L.ptr(images), L.ptr(o_hi), k_pad, V, Cc, Hp, Wp
@@ -314,11 +324,12 @@ def depth_stats(depth, mask):
     return stats
 
 
-def im2col_depth(depth, mask, stats, views_per_batch, dtype, k_pad=448):
+def im2col_depth(depth, mask, stats, views_per_batch, dtype, k_pad=448, out=None):
     """depth, mask f32 [V,H,W]; stats f64 [B,2] -> [V*gh*gw, k_pad] (channels: normalised depth, mask)."""
     _chk_dev(depth, mask, stats)
     V, Hp, Wp = depth.shape
-    out = empty_like_dtype((V * (Hp // 14) * (Wp // 14), k_pad), dtype, depth.device)
+    if out is None:
+        out = empty_like_dtype((V * (Hp // 14) * (Wp // 14), k_pad), dtype, depth.device)
     o_hi, o_lo = hi_lo(out)
     p = L.Im2colParams()
     p.img, p.img2, p.out, p.k_pad, p.V, p.C, p.Hpx, p.Wpx = L.ptr(depth), L.ptr(mask), L.ptr(o_hi), k_pad, V, 2, Hp, Wp
@@ -357,18 +368,19 @@ def probe_mfma(a_frag, b_frag, dtype_code):
 # ---------------------------------------------------------------------------------------------
 # DPT head entries (NHWC activations, 16-bit modes)
 # ---------------------------------------------------------------------------------------------
-def head_layernorm(x, weight, bias, eps, dtype, views, tokens_per_view=1374, n_special=5):
+def head_layernorm(x, weight, bias, eps, dtype, views, tokens_per_view=1374, n_special=5, out=None):
     """x: f32 aggregator output [views*tokens_per_view, 2048] (row stride allowed) -> [views*(tokens_per_view-n_special), 2048]."""
     _chk_dev(x, weight, bias)
     p0 = tokens_per_view - n_special
-    out = torch.empty(views * p0, 2048, device=x.device, dtype=dtype)
+    if out is None:
+        out = torch.empty(views * p0, 2048, device=x.device, dtype=dtype)
     p = L.HeadLayerNormParams(L.ptr(x), x.stride(0), L.ptr(out), out.stride(0), L.ptr(weight), L.ptr(bias),
                               views * p0, p0, tokens_per_view, n_special, eps, L.dtype_code(dtype))
     L.call("ovg_head_layernorm", p, _stream())
     return out
 
 
-def conv(x, w, bias, dtype, cout, ksize=1, stride=1, upshuffle=0, relu=False, add1=None, add2=None, pos=None, out_f32=False):
+def conv(x, w, bias, dtype, cout, ksize=1, stride=1, upshuffle=0, relu=False, add1=None, add2=None, pos=None, out_f32=False, out=None):
     """NHWC convolution. x [n,H,W,Cin] dtype (contiguous), w [w_rows, k*k*Cin] dtype (taps-major), bias f32 [cout] or None.
     upshuffle = s: ConvTranspose2d(kernel = stride = s) -> [n, H*s, W*s, cout]. pos = (pos_x [OW,cout/2], pos_y [OH,cout/2])."""
     _chk_dev(x, w, bias, add1, add2)
@@ -376,7 +388,8 @@ def conv(x, w, bias, dtype, cout, ksize=1, stride=1, upshuffle=0, relu=False, ad
     pad = ksize // 2
     OH, OW = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
     s = upshuffle if upshuffle > 1 else 1
-    out = torch.empty(n, OH * s, OW * s, cout, device=x.device, dtype=torch.float32 if out_f32 else dtype)
+    if out is None:            # caller storage: [n, OH*s, OW*s, cout] with a pixel stride >= cout
+        out = torch.empty(n, OH * s, OW * s, cout, device=x.device, dtype=torch.float32 if out_f32 else dtype)
     p = L.ConvParams()
     p.x, p.ldx, p.w, p.bias, p.y, p.ldy = L.ptr(x), x.stride(2), L.ptr(w), L.ptr(bias), L.ptr(out), out.stride(2)
     if add1 is not None:
@@ -391,11 +404,12 @@ def conv(x, w, bias, dtype, cout, ksize=1, stride=1, upshuffle=0, relu=False, ad
     return out
 
 
-def upsample(x, OH, OW, dtype, pos=None):
+def upsample(x, OH, OW, dtype, pos=None, out=None):
     """Bilinear align_corners=True resize of NHWC x [n,H,W,C] -> [n,OH,OW,C] (+ UV position embedding tables)."""
     _chk_dev(x)
     n, H, W, c = x.shape
-    out = torch.empty(n, OH, OW, c, device=x.device, dtype=dtype)
+    if out is None:
+        out = torch.empty(n, OH, OW, c, device=x.device, dtype=dtype)
     p = L.UpsampleParams()
     p.x, p.ldx, p.y, p.ldy = L.ptr(x), x.stride(2), L.ptr(out), out.stride(2)
     if pos is not None:
@@ -421,14 +435,14 @@ def dpt_tail_supported(x, dtype, OH=None, OW=None):
     return True
 
 
-def dpt_tail(x, OH, OW, dtype, pos, w1, b1, w2, b2, activation):
+def dpt_tail(x, OH, OW, dtype, pos, w1, b1, w2, b2, activation, out=None):
     """x [n,H,W,128] dtype -> upsample to (OH, OW) + pos -> conv3x3(128->32)+ReLU -> conv1x1 -> activation: (val [n,OH,OW,od-1], conf [n,OH,OW]).
     w1 [>=32, 9*128] dtype taps-major (the zero-padded matrix of the ovg_conv form is fine)."""
     _chk_dev(x, w1, b1, w2, b2)
     n, H, W, c = x.shape
     od = w2.shape[0]
-    val = torch.empty(n, OH, OW, od - 1, device=x.device, dtype=torch.float32)
-    conf = torch.empty(n, OH, OW, device=x.device, dtype=torch.float32)
+    val, conf = out if out is not None else (torch.empty(n, OH, OW, od - 1, device=x.device, dtype=torch.float32),
+                                             torch.empty(n, OH, OW, device=x.device, dtype=torch.float32))      # caller storage must be dense
     p = L.DptTailParams()
     p.x, p.ldx, p.w1, p.ldw1, p.b1, p.w2, p.b2, p.val, p.conf = L.ptr(x), x.stride(2), L.ptr(w1), w1.stride(0), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(val), L.ptr(conf)
     if pos is not None:
@@ -438,13 +452,13 @@ def dpt_tail(x, OH, OW, dtype, pos, w1, b1, w2, b2, activation):
     return val, conf
 
 
-def dpt_out(h, w2, b2, activation):
+def dpt_out(h, w2, b2, activation, out=None):
     """h f32 [n,H,W,32] (post-ReLU) -> (val [n,H,W,out_dim-1], conf [n,H,W]); activation 'exp' | 'inv_log'."""
     _chk_dev(h, w2, b2)
     n, H, W, _ = h.shape
     od = w2.shape[0]
-    val = torch.empty(n, H, W, od - 1, device=h.device, dtype=torch.float32)
-    conf = torch.empty(n, H, W, device=h.device, dtype=torch.float32)
+    val, conf = out if out is not None else (torch.empty(n, H, W, od - 1, device=h.device, dtype=torch.float32),
+                                             torch.empty(n, H, W, device=h.device, dtype=torch.float32))
     p = L.DptOutParams(L.ptr(h), L.ptr(w2), L.ptr(b2), L.ptr(val), L.ptr(conf), n * H * W, od, 0 if activation == "exp" else 1)
     L.call("ovg_dpt_out", p, _stream())
     return val, conf
@@ -457,7 +471,7 @@ def camera_head_workspace_bytes(S, dtype):
     return int(n)
 
 
-def camera_head(tokens, W, dtype, iters=4, ws=None):
+def camera_head(tokens, W, dtype, iters=4, ws=None, out=None):
     """Whole CameraHead.forward (camera_head.py:84-154) of one batch element in one call.
     tokens: f32 [S, 2048] view of the camera tokens (row stride allowed, e.g. out[-1][b, :, 0]); W: packed weights
     (heads_hip.HipCameraHead._pack: GEMM matrices in `dtype`, everything else f32); -> [iters, S, 9] f32."""
@@ -468,7 +482,8 @@ def camera_head(tokens, W, dtype, iters=4, ws=None):
     need = camera_head_workspace_bytes(S, dtype)
     if ws is None or ws.numel() * ws.element_size() < need:
         ws = torch.empty(need, device=tokens.device, dtype=torch.uint8)
-    out = torch.empty(iters, S, 9, device=tokens.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(iters, S, 9, device=tokens.device, dtype=torch.float32)
     p = L.CameraHeadParams()
     p.tokens, p.ld_tokens, p.S, p.iters, p.dtype = L.ptr(tokens), tokens.stride(0), S, iters, L.dtype_code(dtype)
     p.trunk_depth, p.dim, p.heads = len(W["blocks"]), 2048, W["heads"]

@@ -128,6 +128,10 @@ def test_linear(quick):
             if N == 1024:
                 ops.linear(xd, wd, bd, dt, epilogue=L.EPI_RES, out=out[:, :N], res=resd[:, N:], gamma=gamma.to(DEV), inject=inj.to(DEV), inj_period=per)
                 report("linear_res_inject_%s_%dx%dx%d" % (name, M, N, K), out[:, :N], ref2, 2e-5 if name != "f32" else 2e-6)
+            tail_clean = float(out[:, N:].abs().max()) == 0.0         # the launches above own out[:, :N] of a 2N-wide buffer only
+            results.append({"name": "linear_res_%s_%dx%dx%d.row_gap_untouched" % (name, M, N, K), "ok": bool(tail_clean), "rel": 0.0})
+            if not tail_clean:
+                print("[FAIL] linear RES wrote past column N of its output rows")
         # PATCH epilogue: M = 2 views * 100 patches -> rows (v*105 + 5 + t)
         p0, p1 = 100, 105
         M, N, K = 2 * p0, 1024, 640
@@ -139,9 +143,13 @@ def test_linear(quick):
         ref = torch.zeros(2 * p1, N)
         for v in range(2):
             ref[v * p1 + 5: v * p1 + 5 + p0] = base[v * p0:(v + 1) * p0] + table[1:]
-        out = torch.zeros(2 * p1, N, device=DEV)
-        ops.linear(x.to(DEV), w.to(DEV), bias.to(DEV), dt, epilogue=L.EPI_PATCH, out=out, table=table.to(DEV), p0=p0, p1=p1, row_off=5)
-        report("linear_patch_%s" % name, out, ref, 2e-5 if name != "f32" else 2e-6)
+        out = torch.zeros(2 * p1, 2 * N, device=DEV)
+        ops.linear(x.to(DEV), w.to(DEV), bias.to(DEV), dt, epilogue=L.EPI_PATCH, out=out[:, :N], table=table.to(DEV), p0=p0, p1=p1, row_off=5)
+        report("linear_patch_%s" % name, out[:, :N], ref, 2e-5 if name != "f32" else 2e-6)
+        tail_clean = float(out[:, N:].abs().max()) == 0.0
+        results.append({"name": "linear_patch_%s.row_gap_untouched" % name, "ok": bool(tail_clean), "rel": 0.0})
+        if not tail_clean:
+            print("[FAIL] linear PATCH wrote past column N of its output rows")
 
 
 def qkv_reference(x, w, bias, seq, qk_norm, rope, tokens_per_view, grid_w):
@@ -189,7 +197,9 @@ def test_qkv(quick):
                 report("qkv_%s_%s_%s.q" % (name, mode, vn), q[:, :seq], qr.reshape(BH, seq, 64), tol)
                 report("qkv_%s_%s_%s.k" % (name, mode, vn), k[:, :seq], kr.reshape(BH, seq, 64), tol)
                 report("qkv_%s_%s_%s.vt" % (name, mode, vn), ops.get_vt(vt)[:, :, :seq], vr.reshape(BH, seq, 64).transpose(1, 2), tol)
-                pad_clean = float(q[:, seq:].abs().max()) == 0.0 and float(ops.get_vt(vt)[:, :, seq:].abs().max()) == 0.0
+                pad_clean = (q.shape[1] == seq or float(q[:, seq:].abs().max()) == 0.0) and \
+                    (k.shape[1] == seq or (float(k[:, seq:].abs().max()) == 0.0 and float(ops.get_vt(vt)[:, :, seq:].abs().max()) == 0.0))
+                results.append({"name": "qkv_%s_%s_%s.padding_untouched" % (name, mode, vn), "ok": bool(pad_clean), "rel": 0.0})
                 if not pad_clean:
                     print("[FAIL] qkv padding was written")
             if quick:
@@ -616,7 +626,9 @@ def test_embed():
     for name, dt in DT.items():
         out = ops.im2col_rgb(img.to(DEV), dt)
         report("im2col_rgb_%s" % name, out[:, :588], cols, 1e-2 if name == "bf16" else (1e-3 if name == "f16" else 1e-6))
-        if float(out[:, 588:].abs().max()) != 0:
+        pad_zero = float(out[:, 588:].abs().max()) == 0
+        results.append({"name": "im2col_rgb_%s.pad_zero" % name, "ok": bool(pad_zero), "rel": 0.0})
+        if not pad_zero:
             print("[FAIL] im2col pad not zero")
     depth = 0.5 + 5 * torch.rand(V, Hp, Hp, generator=g)
     mask = (torch.rand(V, Hp, Hp, generator=g) > 0.2).float()
