@@ -59,7 +59,8 @@ extern "C" {
  *     + voxel-grid decimation (ovg_voxel_downsample, ovg_voxel_downsample_workspace_bytes): entries added, nothing existing changed,
  *       so the number stays; a binding looks the two symbols up by name and reports a library that predates them
  *     + point-cloud rendering (ovg_render_points, ovg_render_workspace_bytes): added the same way, looked up by name
- *     + multi-view depth consistency (ovg_multiview_consistency, ovg_consistency_workspace_bytes): added the same way */
+ *     + multi-view depth consistency (ovg_multiview_consistency, ovg_consistency_workspace_bytes): added the same way
+ *     + nearest-neighbour search between point clouds (ovg_nearest_neighbours, ovg_nn_workspace_bytes): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -672,6 +673,40 @@ typedef struct {
 } ovg_consistency_params;
 int64_t ovg_consistency_workspace_bytes(int32_t S, int32_t H, int32_t W);
 int ovg_multiview_consistency(const ovg_consistency_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Nearest-neighbour search between two point clouds (added under ABI 13): for every query point the nearest reference point, by an
+ * exact rule that tests/nn_twin.py restates in numpy float32 bit for bit.
+ *   query [nq][3] f32, reference [nr][3] f32; query_valid [nq] u8 and reference_valid [nr] u8 are optional (NULL: all valid).
+ *   Every step is one f32 operation rounded on its own (no fused multiply-add):
+ *   1. a point is USABLE when its three coordinates are finite and its valid byte (if given) is non-zero;
+ *   2. for a usable query q and a usable reference r: dx = q.x - r.x, dy = q.y - r.y, dz = q.z - r.z, d = (dx dx + dy dy) + dz dz.
+ *      d is +0, positive or +inf (an overflow is still a candidate), so its bit pattern orders like its value;
+ *   3. with OVG_NN_EXCLUDE_SAME_INDEX (nq == nr: a search inside one cloud) reference j == i is no candidate of query i;
+ *   4. index[i] = the j that minimises (bits(d), j) over the candidates: the nearest reference, equal distances go to the LOWEST
+ *      index; sqdist[i] = that d. An unusable query, or one without a candidate, has index -1 and sqdist +inf.
+ *   Brute force, nq nr pairs at about 11 vector operations each: a grid of (query tiles of OVG_NN_QUERY_TILE) x (splits of the
+ *   reference tiles of OVG_NN_REFERENCE_TILE), the queries in registers, the reference tile in LDS. One split stores index / sqdist
+ *   directly (one launch); several merge the packed (bits(d) << 32) | j with a 64-bit unsigned atomic min in ws and a last launch
+ *   decodes it (three launches). splits = 0 chooses enough workgroups to fill the chip when there are few query tiles; a value
+ *   above the number of reference tiles is clamped. The result never depends on splits. Nothing is allocated or read back.
+ *   ws: >= ovg_nn_workspace_bytes(nq, nr) bytes (the u64 keys, 8 nq rounded up to 16), 16-byte aligned; the query returns -1 for
+ *   nq, nr <= 0 or >= 2^31. index [nq] int32, sqdist [nq] f32.
+ *   OVG_E_ARG: NULL params / query / reference / ws / index / sqdist, bad nq / nr, unknown flags, OVG_NN_EXCLUDE_SAME_INDEX with
+ *   nq != nr, splits < 0, a pointer that is not 4-byte aligned, a misaligned or undersized workspace.
+ * ------------------------------------------------------------------ */
+enum { OVG_NN_QUERY_TILE = 512, OVG_NN_REFERENCE_TILE = 512 };
+enum { OVG_NN_EXCLUDE_SAME_INDEX = 1 };
+typedef struct {
+  const float* query; const float* reference;
+  const uint8_t* query_valid; const uint8_t* reference_valid;
+  int64_t nq; int64_t nr;
+  int32_t flags; int32_t splits;
+  void* ws; int64_t ws_bytes;
+  int32_t* index; float* sqdist;
+} ovg_nn_params;
+int64_t ovg_nn_workspace_bytes(int64_t nq, int64_t nr);
+int ovg_nearest_neighbours(const ovg_nn_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

@@ -226,6 +226,15 @@ class ConsistencyParams(C.Structure):
                 ("support", vp), ("violations", vp), ("occluded", vp)]
 
 
+NN_QUERY_TILE, NN_REFERENCE_TILE = 512, 512                  # queries per workgroup, references per LDS tile (tests place shapes around them)
+NN_EXCLUDE_SAME_INDEX = 1
+
+
+class NnParams(C.Structure):
+    _fields_ = [("query", vp), ("reference", vp), ("query_valid", vp), ("reference_valid", vp), ("nq", i64), ("nr", i64),
+                ("flags", i32), ("splits", i32), ("ws", vp), ("ws_bytes", i64), ("index", vp), ("sqdist", vp)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -297,6 +306,8 @@ SYMBOLS = {
     "ovg_render_workspace_bytes": (i64, [i32, i32, i32]),
     "ovg_multiview_consistency": (i32, [C.POINTER(ConsistencyParams), vp]),
     "ovg_consistency_workspace_bytes": (i64, [i32, i32, i32]),
+    "ovg_nearest_neighbours": (i32, [C.POINTER(NnParams), vp]),
+    "ovg_nn_workspace_bytes": (i64, [i64, i64]),
 }
 
 

@@ -726,3 +726,48 @@ def multiview_consistency(points, cams, tol, near=1e-3, valid=None, src_first=0,
     p.ws, p.ws_bytes, p.support, p.violations, p.occluded = L.ptr(ws), nbytes(ws), L.ptr(sup), L.ptr(vio), L.ptr(occ)
     L.call("ovg_multiview_consistency", p, _stream())
     return sup, vio, occ
+
+
+def nn_workspace_bytes(nq, nr):
+    for v in (nq, nr):
+        if not -(1 << 63) <= int(v) < (1 << 63):
+            raise L.OvgError("ovg_nn_workspace_bytes: unsupported (nq=%d, nr=%d)" % (nq, nr))
+    b = L.load().ovg_nn_workspace_bytes(int(nq), int(nr))
+    if b < 0:
+        raise L.OvgError("ovg_nn_workspace_bytes: unsupported (nq=%d, nr=%d)" % (nq, nr))
+    return int(b)
+
+
+def nearest_neighbours(query, reference, query_valid=None, reference_valid=None, exclude_self=False, splits=0, ws=None, index=None,
+                       sqdist=None):
+    """ovg_nearest_neighbours on contiguous device tensors: query f32 [nq, 3], reference f32 [nr, 3], query_valid / reference_valid
+    u8 [nq] / [nr] or None. -> (index int32 [nq], sqdist f32 [nq]): for every query the nearest usable reference (lowest index on
+    ties; with exclude_self, nq == nr and reference i is skipped for query i), -1 / +inf where there is none. splits: 0 lets the
+    library choose, any other value gives the same bytes; ws: an optional uint8 device tensor of at least nn_workspace_bytes(nq, nr)
+    bytes; index / sqdist: optional outputs to write into. Nothing is read back."""
+    _chk_dev(query, reference, query_valid, reference_valid, ws, index, sqdist)
+    for t, name in ((query, "query"), (reference, "reference")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
+            raise L.OvgError("nearest_neighbours: %s must be a contiguous f32 tensor [n, 3]" % name)
+    nq, nr = int(query.shape[0]), int(reference.shape[0])
+    for v, n, name in ((query_valid, nq, "query_valid"), (reference_valid, nr, "reference_valid")):
+        if v is not None and (v.dtype != torch.uint8 or not v.is_contiguous() or tuple(v.shape) != (n,)):
+            raise L.OvgError("nearest_neighbours: %s must be a contiguous u8 tensor [%d]" % (name, n))
+    if exclude_self and nq != nr:
+        raise L.OvgError("nearest_neighbours: exclude_self needs nq == nr (got %d, %d)" % (nq, nr))
+    need = nn_workspace_bytes(nq, nr)
+    if ws is None or nbytes(ws) < need:
+        ws = torch.empty(need, device=query.device, dtype=torch.uint8)
+    if index is None:
+        index = torch.empty(nq, device=query.device, dtype=torch.int32)
+    if sqdist is None:
+        sqdist = torch.empty(nq, device=query.device, dtype=torch.float32)
+    if index.dtype != torch.int32 or sqdist.dtype != torch.float32 or index.numel() != nq or sqdist.numel() != nq or \
+            not (index.is_contiguous() and sqdist.is_contiguous()):
+        raise L.OvgError("nearest_neighbours: index / sqdist must be contiguous int32 / f32 tensors [%d]" % nq)
+    p = L.NnParams()
+    p.query, p.reference, p.query_valid, p.reference_valid = L.ptr(query), L.ptr(reference), L.ptr(query_valid), L.ptr(reference_valid)
+    p.nq, p.nr, p.flags, p.splits = nq, nr, L.NN_EXCLUDE_SAME_INDEX if exclude_self else 0, int(splits)
+    p.ws, p.ws_bytes, p.index, p.sqdist = L.ptr(ws), nbytes(ws), L.ptr(index), L.ptr(sqdist)
+    L.call("ovg_nearest_neighbours", p, _stream())
+    return index, sqdist

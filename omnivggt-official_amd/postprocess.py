@@ -374,6 +374,153 @@ def consistency_mask(result, min_support=1, max_violations=0):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# Nearest neighbours between clouds: mutual matches and cloud-to-cloud distances (ovg_nearest_neighbours)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class NNResult:
+    """Result of nearest_neighbours: index int32 (the nearest reference point, -1 where there is none) and sqdist float32 (the squared
+    distance to it, +inf where there is none), device tensors shaped like the query without its last dimension."""
+    __slots__ = ("index", "sqdist")
+
+    def __init__(self, index, sqdist):
+        self.index, self.sqdist = index, sqdist
+
+
+def _nn_points(x, name):
+    if isinstance(x, PointCloud):
+        x = x.points
+    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != 3 or x.dtype != torch.float32:
+        raise ValueError("%s must be a float32 tensor (..., 3) or a PointCloud" % name)
+    if x.numel() // 3 >= 1 << 31:
+        raise ValueError("%s holds %d points: the search takes fewer than 2^31" % (name, x.numel() // 3))
+    return x
+
+
+def _nn_valid(v, lead, name):
+    if v is None:
+        return None
+    if not isinstance(v, torch.Tensor) or tuple(v.shape) != tuple(lead) or v.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("%s must be a bool / uint8 tensor shaped %r" % (name, tuple(lead)))
+    return v
+
+
+def nearest_neighbours(query, reference, query_valid=None, reference_valid=None, exclude_self=False):
+    """For every query point its nearest reference point, searched exhaustively on the device (ovg_nearest_neighbours): no k-d tree, no
+    copy to the host. The rule is exact (tests/nn_twin.py restates it in numpy float32): d = (dx dx + dy dy) + dz dz in float32 without
+    fused multiply-adds, the smallest d wins and equal distances go to the LOWEST reference index, so two calls, and any tiling of
+    the launch, give identical bytes. A point is usable when its coordinates are finite and its valid entry (if given) is non-zero;
+    an unusable query, or a query without a usable reference, gets index -1 and sqdist +inf. A distance that overflows float32 to
+    +inf still matches.
+
+    query, reference: float32 device tensors (..., 3), or PointClouds (their points); flattened for the search. query_valid /
+    reference_valid: optional bool / uint8 tensors shaped like the points without the last dimension. exclude_self=True searches
+    inside one cloud: query and reference must hold the same number of points and reference i is no candidate of query i (each
+    point's nearest OTHER point: the distance that isolates floaters).
+
+    -> NNResult(index int32, sqdist float32) shaped like the query's leading dimensions. No device -> host synchronisation. CPU
+    tensors raise OvgError (there is no CPU fallback); bad shapes or dtypes raise ValueError."""
+    q, r = _nn_points(query, "query"), _nn_points(reference, "reference")
+    lead = tuple(q.shape[:-1])
+    qv, rv = _nn_valid(query_valid, lead, "query_valid"), _nn_valid(reference_valid, tuple(r.shape[:-1]), "reference_valid")
+    nq, nr = q.numel() // 3, r.numel() // 3
+    if exclude_self and nq != nr:
+        raise ValueError("exclude_self searches inside one cloud: query and reference must hold the same number of points (%d, %d)" % (nq, nr))
+    if not all(t is None or t.is_cuda for t in (q, r, qv, rv)):
+        raise ops.L.OvgError("nearest_neighbours needs HIP device tensors: there is no CPU fallback")
+    if nq == 0 or nr == 0:
+        return NNResult(torch.full(lead, -1, device=q.device, dtype=torch.int32),
+                        torch.full(lead, float("inf"), device=q.device, dtype=torch.float32))
+    u8 = lambda v: None if v is None else (v.to(torch.uint8) if v.dtype == torch.bool else v).reshape(-1).contiguous()
+    idx, sq = ops.nearest_neighbours(q.reshape(nq, 3).contiguous(), r.reshape(nr, 3).contiguous(), u8(qv), u8(rv),
+                                     exclude_self=bool(exclude_self))
+    return NNResult(idx.reshape(lead), sq.reshape(lead))
+
+
+def reciprocal_matches(P1, P2, valid1=None, valid2=None):
+    """Mutual nearest neighbours of two point sets on the device: the contract of the reference's find_reciprocal_matches
+    (omnivggt/utils/geometry.py, two scipy k-d trees on the host) as two searches and one gather.
+    -> (reciprocal_in_P2 bool [n2], nn2_in_P1 int32 [n2], count): nn2_in_P1[j] is the point of P1 nearest to P2[j] (-1 where there is
+    none), reciprocal_in_P2[j] is True when P2[j] is in turn the point of P2 nearest to P1[nn2_in_P1[j]], count is the 0-d int64
+    device tensor of their number. A -1 neighbour is never reciprocal. Ties follow nearest_neighbours (lowest index), so the result
+    is deterministic where a k-d tree's is not. P1, P2: float32 (..., 3) device tensors or PointClouds, flattened; valid1 / valid2 as
+    in nearest_neighbours. Nothing is read back."""
+    nn1_in_P2 = nearest_neighbours(P1, P2, valid1, valid2).index.reshape(-1)
+    nn2_in_P1 = nearest_neighbours(P2, P1, valid2, valid1).index.reshape(-1)
+    n2 = nn2_in_P1.numel()
+    if nn1_in_P2.numel() == 0:
+        rec = torch.zeros(n2, device=nn2_in_P1.device, dtype=torch.bool)
+    else:
+        back = nn1_in_P2[nn2_in_P1.clamp_min(0).long()]
+        rec = (nn2_in_P1 >= 0) & (back == torch.arange(n2, device=back.device, dtype=torch.int32))
+    return rec, nn2_in_P1, rec.sum()
+
+
+class CloudDistance:
+    """Result of cloud_distance (Python floats and ints). accuracy / accuracy_median: mean / median distance from the predicted points to
+    their nearest ground-truth point; completeness / completeness_median: the same from the ground truth to the prediction; chamfer:
+    (accuracy + completeness) / 2; n_pred / n_gt: how many points of each cloud found a neighbour and entered the figures. With a
+    threshold: precision (share of those predicted points within it), recall (share of those ground-truth points), fscore (their
+    harmonic mean, 0 when both are 0); None without."""
+    __slots__ = ("accuracy", "accuracy_median", "completeness", "completeness_median", "chamfer", "n_pred", "n_gt", "precision", "recall",
+                 "fscore", "threshold")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def __repr__(self):
+        return "CloudDistance(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+
+def _order_statistic_median(sq):
+    """Median of sqrt(sq) in float64 for a 1-D float32 device tensor (len >= 1) through percentile(): sqrt is monotonic, so the middle
+    distances are the roots of the middle squared distances, and percentile(., 50) of an odd number of values IS an order statistic
+    (no interpolation). An even count is made odd once with -inf in front (-> the lower middle value) and once with +inf behind (->
+    the upper one); the median is the mean of the two roots, as numpy.median has it. (Beyond 2^24 values the rank follows numpy's
+    float32 index rule, as percentile does.)"""
+    n = sq.numel()
+    if n % 2:
+        return percentile(sq, 50.0).double().sqrt()
+    if n == 2:                                                               # the padded forms below would interpolate towards their own +inf
+        return sq.double().sqrt().mean()
+    buf = torch.empty(n + 2, device=sq.device, dtype=torch.float32)
+    buf[0], buf[n + 1] = float("-inf"), float("inf")
+    buf[1:n + 1] = sq
+    lo, hi = percentile(buf[:n + 1], 50.0), percentile(buf[1:], 50.0)
+    return (lo.double().sqrt() + hi.double().sqrt()) / 2
+
+
+def cloud_distance(pred, gt, threshold=None):
+    """Accuracy, completeness, chamfer distance and F-score of a predicted cloud against a ground-truth cloud, the figures by which
+    reconstructions are scored, from two exact nearest-neighbour searches on the device (nearest_neighbours) instead of two k-d
+    trees on the host. Distances are sqrt(sqdist) in float64, means are float64 sums on the device, medians go through the exact
+    percentile(). Points without a neighbour (non-finite coordinates, or an empty other side) are left out of every figure and of
+    n_pred / n_gt; a side with no matched point reports nan. threshold: optional positive distance; precision = share of the matched
+    predicted points with distance < threshold, recall likewise for the ground truth, fscore = 2 P R / (P + R).
+    pred, gt: float32 (..., 3) device tensors or PointClouds. -> CloudDistance (one device -> host read at the end)."""
+    if threshold is not None and not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and threshold > 0):
+        raise ValueError("cloud_distance: threshold must be a positive number or None, got %r" % (threshold,))
+    sides = []
+    for a, b in ((pred, gt), (gt, pred)):
+        res = nearest_neighbours(a, b)
+        sq = res.sqdist.reshape(-1)[res.index.reshape(-1) >= 0]
+        n = int(sq.numel())
+        if n == 0:
+            sides.append((float("nan"), float("nan"), 0, float("nan")))
+            continue
+        d = sq.double().sqrt()
+        within = (d < float(threshold)).double().mean() if threshold is not None else d.new_zeros(())
+        vals = torch.stack([d.mean(), _order_statistic_median(sq), within]).tolist()
+        sides.append((vals[0], vals[1], n, vals[2]))
+    (acc, acc_med, n_pred, prec), (comp, comp_med, n_gt, rec) = sides
+    out = dict(accuracy=acc, accuracy_median=acc_med, completeness=comp, completeness_median=comp_med, chamfer=(acc + comp) / 2,
+               n_pred=n_pred, n_gt=n_gt, threshold=None if threshold is None else float(threshold))
+    if threshold is not None:
+        out.update(precision=prec, recall=rec, fscore=2 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0)
+    return CloudDistance(**out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # Voxel-grid decimation and the PLY / GLB writers
 # ---------------------------------------------------------------------------------------------------------------------------------
 
