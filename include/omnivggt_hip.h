@@ -125,8 +125,8 @@ enum { OVG_EPI_STORE = 0, OVG_EPI_GELU = 1, OVG_EPI_RES = 2, OVG_EPI_PATCH = 3 }
  * AUTO picks by shape (ovg_gemm.hip: choose_256). ABI 11: the round-5 lab selectors (4 = persistent 256 x 256, 8 = DMA-in-M flag) are gone --
  * any other value is OVG_E_ARG. */
 enum { OVG_TILE_AUTO = 0, OVG_TILE_128 = 1, OVG_TILE_256 = 2,
-       /* A/B flag, OR-ed onto any of the three: the same kernels with the r02 epilogue forms (erf_as GELU; per-lane 8- / 16-byte stores in
-        * the accumulator layout instead of whole lines staged through the idle LDS -- ovg_gemm.hip); -DOVG_AB_VARIANTS builds only */
+       /* retired selectors (the r02 epilogue forms of the A/B history; their kernels left the tree, measurements under profiles/): ovg_linear
+        * and ovg_qkv answer OVG_E_UNSUPPORTED to any tile with the OVG_TILE_R02_EPILOGUE bit set */
        OVG_TILE_R02_EPILOGUE = 16, OVG_TILE_128X = 17, OVG_TILE_256X = 18 };
 typedef struct {
   const void* x; int64_t ldx;

@@ -29,8 +29,8 @@ EXTRA_FLAGS = {"ovg_attn.hip": ["-fno-honor-nans"],
                "ovg_nn.hip": ["-ffp-contract=off"]}
 
 
-# attn16_kernel<bf16, QB, WAVES, MODE 0, OCC 2, VSUM false, DMA, X3 0>: the three launches of the bf16 plan (mangled-name fragment -> QB)
-PINNED_ATTENTION_KERNELS = {"IDF16bLi4ELi8ELi0ELi2ELb0ELi5ELi0E": 4, "IDF16bLi4ELi4ELi0ELi2ELb0ELi3ELi0E": 4, "IDF16bLi2ELi4ELi0ELi2ELb0ELi3ELi0E": 2}
+# attn16_kernel<bf16, QB, WAVES, MODE 0, RING, X3 0>: the three launches of the bf16 plan (mangled-name fragment -> QB)
+PINNED_ATTENTION_KERNELS = {"IDF16bLi4ELi8ELi0ELi5ELi0E": 4, "IDF16bLi4ELi4ELi0ELi3ELi0E": 4, "IDF16bLi2ELi4ELi0ELi3ELi0E": 2}
 
 
 # everything a pinned hot loop may contain besides scalar (s_*) instructions

@@ -329,13 +329,13 @@ Plan16 plan16(const ovg_attn_params& p, bool bf16, bool have_ws) {
     else v = (pad128 * 26 < pad256 * 25 && 2 * p.BH * (pad128 / 128) >= 15 * (int64_t)cus) ? 54 : 50;   // ... from 2.5 rounds of 3 x CUs slots on (8 views: 0.069 ms with 256-row, 0.072 with 128-row tiles)
   }
   pl.variant = v;
-  pl.bq = (v == 33 || v == 51 || v == 57 || v == 58 || v == 59) ? 512 : ((v == 8 || v == 25 || v == 19 || v == 54 || v == 55) ? 128 : 256);
+  pl.bq = v == 57 ? 512 : ((v == 54 || v == 55) ? 128 : 256);
   pl.total_tiles = total_key_tiles(p);
-  const int slots = (v == 33 || v == 51 || v == 57 || v == 58 || v == 59) ? cus : 2 * cus;
+  const int slots = v == 57 ? cus : 2 * cus;
   const int64_t units = p.BH * ((p.nq + pl.bq - 1) / pl.bq);
   int splits = 1;
   if (kvs > 1) splits = kvs;
-  else if (kvs == 0 && have_ws && (v == 21 || v == 6 || v == 50 || v == 52 || v == 54 || v == 55)) {   // two-workgroups-per-CU kernels (the 512-row ones have the tail split)
+  else if (kvs == 0 && have_ws && (v == 50 || v == 52 || v == 54 || v == 55)) {   // two-workgroups-per-CU kernels (the 512-row ones have the tail split)
     // Measured model (LDS-DMA kernels, profiles/r02_attention_splitkv_ab.txt second block): a launch of R = units / slots rounds runs at
     // eff(R) = 1 - 0.2035 / R^0.72 of the many-round rate of 1.33 PFLOP/s (0.835 at R = 1.34, 0.88-0.90 at 2.7, 0.94-0.95 at 5.4, 0.963 at
     // 10.75: measured at 8 / 16 / 32 / 64 views and on the per-rank launch of the 8-GPU run); a split costs ~1.5 key tiles per unit plus the
@@ -451,14 +451,13 @@ int64_t split_part_rows(const ovg_attn_params& p, int bq, int64_t row0, int64_t 
   return row0 == 0 ? p.nq_pad : (row1 - row0 + bq - 1) / bq * bq;
 }
 
-template <typename T, int QB, int WAVES, int MODE, int OCC = 2, bool VSUM = false, int DMA = 0, int X3 = 0>
-int launch_attn16(const ovg_attn_params& p, const Plan16& pl, hipStream_t st, int64_t row0 = 0, int64_t row1 = -1) {   // q rows [row0, row1) (default: all)
+template <typename T, int QB, int WAVES, int MODE, int RING, int X3 = 0>
+int launch_attn16(const ovg_attn_params& p, const Plan16& pl, hipStream_t st, int64_t row0, int64_t row1) {   // q rows [row0, row1)
   constexpr int BQ = 16 * QB * WAVES;
-  if (row1 < 0) row1 = p.nq;
   const int nqt = (int)((row1 - row0 + BQ - 1) / BQ);
   const int part_rows = (int)split_part_rows(p, BQ, row0, row1);
   const dim3 grid((unsigned)(p.BH * nqt * pl.splits)), block(64 * WAVES);
-  OVG_LAUNCH((attn16_kernel<T, QB, WAVES, MODE, OCC, VSUM, DMA, X3>), grid, block, 0, st, p, nqt, pl.total_tiles, pl.splits, pl.per_split, (int)row0, part_rows);
+  OVG_LAUNCH((attn16_kernel<T, QB, WAVES, MODE, RING, X3>), grid, block, 0, st, p, nqt, pl.total_tiles, pl.splits, pl.per_split, (int)row0, part_rows);
   OVG_CHECK_LAUNCH();
   if (pl.splits > 1) {
     const int64_t blocks = (p.BH * (row1 - row0) * 8 + 255) / 256;
@@ -469,23 +468,36 @@ int launch_attn16(const ovg_attn_params& p, const Plan16& pl, hipStream_t st, in
 }
 
 // variant (benchmark / test knob; numbers kept from the A/B logs under profiles/):
-//   0 = default: bf16 -> speculative kernel, q tile and split-KV factor from plan16; f16 -> lazy-rescale kernel; both LDS-DMA staged
-//   1 / 2   baseline kernel, QB = 1 / 2 (never split)
-//   6 / 8   attn16 lazy-rescale only (MODE 1), QB = 4 / 2
-//   21 / 25 attn16 speculative + verified fallback (MODE 0), QB = 4 / 2
-//   18 / 19 attn16 with the fallback forced (MODE 2, tests), QB = 4 / 2
-//   31 / 32 r02 experiments: row sums on the VALU / 8 waves x 32 rows at 4 waves per SIMD (both slower, kept for the A/B tool)
-//   33      8 waves x 64 rows = 512-row q tiles, 1 workgroup per CU, register-staged (the r02 default for launches of >= 8 rounds)
-//   50 / 51 / 54   LDS-DMA staging (3-slot ring, two tiles ahead, barrier per tile): speculative kernel with 256- / 512- / 128-row q tiles;
-//                  50 = the bf16 default for short launches
-//   52 / 55        LDS-DMA staging, lazy-rescale kernel, 256- / 128-row q tiles -- the f16 default (52 for nq >= 4096, else 55; a 512-row
-//                  8-wave form of the lazy-rescale body measured 4 % slower at 64 views: profiles/r02_attention_dma_ab.txt)
-//   53             LDS-DMA staging with the fallback forced (tests)
-//   57 / 58 / 59   as 51 with a workgroup barrier only every 2 / 3 / 4 tiles (ring of 5 / 7 / 9 slots): 57 = the bf16 default for launches of
-//                  >= 2.5 rounds of 512-row tiles; 56 = the 4-wave kernel with a 5-slot ring (80 KB: one workgroup per CU, A/B only)
+//   0 = default: bf16 -> speculative kernel, q tile and split-KV factor from plan16; f16 -> lazy-rescale kernel
+//   1              baseline kernel (attn_kernel above; never split)
+//   50 / 54        speculative kernel (3-slot ring, barrier per tile) with 256- / 128-row q tiles; 50 = the bf16 default for short launches
+//   52 / 55        lazy-rescale kernel, 256- / 128-row q tiles -- the f16 default (52 for nq >= 4096, else 55; a 512-row 8-wave form of the
+//                  lazy-rescale body measured 4 % slower at 64 views: profiles/r02_attention_dma_ab.txt)
+//   53             the 256-row speculative kernel with the fallback forced (tests)
+//   57             speculative kernel with 512-row q tiles, 8 waves, 5-slot ring (a workgroup barrier every 2 tiles): the bf16 default for
+//                  launches of >= 2.5 rounds of 512-row tiles
+//   71 - 74        plan knobs of the A/B tool and the tests (plan16)
+// Retired (the A/B history of rounds 1-4; OVG_E_UNSUPPORTED; removed by the commit "Retire the A/B-history kernel variants", measurements
+// under profiles/): 2, 6, 8, 18, 19, 21, 25, 31, 32, 33, 51, 56, 58, 59.
+bool retired_variant(int v) {
+  for (const int r : {2, 6, 8, 18, 19, 21, 25, 31, 32, 33, 51, 56, 58, 59})
+    if (v == r) return true;
+  return false;
+}
+
+// The shipped 16-bit launches by name: <T, q blocks per wave, waves, MODE, ring slots>
+using Launch16 = int (*)(const ovg_attn_params&, const Plan16&, hipStream_t, int64_t, int64_t);
+template <typename T> constexpr Launch16 spec512 = launch_attn16<T, 4, 8, 0, 5>;     // variant 57
+template <typename T> constexpr Launch16 spec256 = launch_attn16<T, 4, 4, 0, 3>;     // variant 50
+template <typename T> constexpr Launch16 spec128 = launch_attn16<T, 2, 4, 0, 3>;     // variant 54; the tail of a tail split
+template <typename T> constexpr Launch16 lazy256 = launch_attn16<T, 4, 4, 1, 3>;     // variant 52
+template <typename T> constexpr Launch16 lazy128 = launch_attn16<T, 2, 4, 1, 3>;     // variant 55
+template <typename T> constexpr Launch16 forced256 = launch_attn16<T, 4, 4, 2, 3>;   // variant 53
+
 template <typename T>
 int dispatch16(const ovg_attn_params& p, hipStream_t st) {
   constexpr bool kBf16 = std::is_same<T, bf16_t>::value;
+  if (retired_variant(p.variant)) return OVG_E_UNSUPPORTED;
   const Plan16 pl = plan16(p, kBf16, p.ws_part != nullptr && p.ws_lse != nullptr);
   if (pl.splits > 1 || pl.tail_splits > 1) {   // the partials go to caller memory: refuse a missing or undersized workspace instead of writing past it
     if (p.ws_part == nullptr || p.ws_lse == nullptr) return OVG_E_ARG;
@@ -493,72 +505,43 @@ int dispatch16(const ovg_attn_params& p, hipStream_t st) {
                                        : (int64_t)pl.tail_splits * p.BH * split_part_rows(p, pl.bq, pl.main_rows, p.nq);
     if (p.ws_part_bytes < rows * OVG_D * 4 || p.ws_lse_bytes < rows * 4) return OVG_E_ARG;
   }
+  // the main kernel of a launch with a tail: 512-row speculative (57), 256-row lazy-rescale (52, the f16 default) or 256-row speculative (50)
+  const Launch16 main_kernel = pl.variant == 57 ? spec512<T> : (pl.variant == 52 ? lazy256<T> : spec256<T>);
   if (pl.tail_splits > 1) {                         // key-split tail (plan16): full rounds unsplit, then the remaining rows cut along the keys + merge
-    const bool lazy = pl.variant == 52;             // f16 default: lazy-rescale body
-    const bool big = pl.variant == 57;              // 512-row tiles (round 6)
-    int rc = big ? launch_attn16<T, 4, 8, 0, 2, false, 5>(p, pl, st, 0, pl.main_rows)
-                 : (lazy ? launch_attn16<T, 4, 4, 1, 2, false, 3>(p, pl, st, 0, pl.main_rows) : launch_attn16<T, 4, 4, 0, 2, false, 3>(p, pl, st, 0, pl.main_rows));
+    const int rc = main_kernel(p, pl, st, 0, pl.main_rows);
     if (rc != OVG_OK) return rc;
     Plan16 tp = pl;
     tp.per_split = (pl.total_tiles + pl.tail_splits - 1) / pl.tail_splits;
     tp.splits = (pl.total_tiles + tp.per_split - 1) / tp.per_split;
-    return big ? launch_attn16<T, 4, 8, 0, 2, false, 5>(p, tp, st, pl.main_rows, p.nq)
-               : (lazy ? launch_attn16<T, 4, 4, 1, 2, false, 3>(p, tp, st, pl.main_rows, p.nq) : launch_attn16<T, 4, 4, 0, 2, false, 3>(p, tp, st, pl.main_rows, p.nq));
+    return main_kernel(p, tp, st, pl.main_rows, p.nq);
   }
   if (pl.tail_bq) {                                 // tail split (plan16): full rounds of big tiles, then the remaining rows as 128-row tiles
-    const int rc = pl.variant == 57 ? launch_attn16<T, 4, 8, 0, 2, false, 5>(p, pl, st, 0, pl.main_rows)
-                                    : launch_attn16<T, 4, 4, 0, 2, false, 3>(p, pl, st, 0, pl.main_rows);
-    return rc != OVG_OK ? rc : launch_attn16<T, 2, 4, 0, 2, false, 3>(p, pl, st, pl.main_rows, p.nq);
+    const int rc = main_kernel(p, pl, st, 0, pl.main_rows);
+    return rc != OVG_OK ? rc : spec128<T>(p, pl, st, pl.main_rows, p.nq);
   }
   switch (pl.variant) {
-    // the product's kernels: baseline (f32 parity path, in-process reference of the tests), the LDS-DMA kernels of the launch plan, and the
-    // forced-fallback form the tests use
-    case 1: return launch_attn<T, 1>(p, st);
-    case 50: return launch_attn16<T, 4, 4, 0, 2, false, 3>(p, pl, st);
-    case 52: return launch_attn16<T, 4, 4, 1, 2, false, 3>(p, pl, st);
-    case 53: return launch_attn16<T, 4, 4, 2, 2, false, 3>(p, pl, st);
-    case 54: return launch_attn16<T, 2, 4, 0, 2, false, 3>(p, pl, st);
-    case 55: return launch_attn16<T, 2, 4, 1, 2, false, 3>(p, pl, st);
-    case 57: return launch_attn16<T, 4, 8, 0, 2, false, 5>(p, pl, st);
-#ifdef OVG_AB_VARIANTS
-    // A/B history (rounds 1-4; numbers in the logs under profiles/): compiled only into tools/probes/build_alt.py ab=-DOVG_AB_VARIANTS builds --
-    // co-compiled template variants perturb each other's register allocation, and variant 32 spills
-    case 2: return launch_attn<T, 2>(p, st);
-    case 6: return launch_attn16<T, 4, 4, 1>(p, pl, st);
-    case 8: return launch_attn16<T, 2, 4, 1>(p, pl, st);
-    case 21: return launch_attn16<T, 4, 4, 0>(p, pl, st);
-    case 25: return launch_attn16<T, 2, 4, 0>(p, pl, st);
-    case 18: return launch_attn16<T, 4, 4, 2>(p, pl, st);
-    case 19: return launch_attn16<T, 2, 4, 2>(p, pl, st);
-    case 31: return launch_attn16<T, 4, 4, 0, 2, true>(p, pl, st);
-    case 32: return launch_attn16<T, 2, 8, 0, 4>(p, pl, st);
-    case 33: return launch_attn16<T, 4, 8, 0, 2>(p, pl, st);
-    case 51: return launch_attn16<T, 4, 8, 0, 2, false, 3>(p, pl, st);
-    case 56: return launch_attn16<T, 4, 4, 0, 2, false, 5>(p, pl, st);
-    case 58: return launch_attn16<T, 4, 8, 0, 2, false, 7>(p, pl, st);
-    case 59: return launch_attn16<T, 4, 8, 0, 2, false, 9>(p, pl, st);
+    case 1: return launch_attn<T, 1>(p, st);         // baseline: f32 parity path, in-process reference of the tests
+    case 50: return spec256<T>(p, pl, st, 0, p.nq);
+    case 52: return lazy256<T>(p, pl, st, 0, p.nq);
+    case 53: return forced256<T>(p, pl, st, 0, p.nq);
+    case 54: return spec128<T>(p, pl, st, 0, p.nq);
+    case 55: return lazy128<T>(p, pl, st, 0, p.nq);
+    case 57: return spec512<T>(p, pl, st, 0, p.nq);
     default: return OVG_E_ARG;
-#else
-    case 2: case 6: case 8: case 21: case 25: case 18: case 19: case 31: case 32: case 33: case 51: case 56: case 58: case 59:
-      return OVG_E_UNSUPPORTED;                      // A/B history: not in this build (OVG_AB_VARIANTS)
-    default: return OVG_E_ARG;
-#endif
   }
 }
 
 // split-f16 mode (OVG_F16X2): one launch of 256-row tiles -- 8 waves x 2 q blocks, lazy-rescale softmax, a 3-slot LDS-DMA ring of
 // [K hi | V^T hi | K lo | V^T lo] tiles (96 KB, one workgroup per CU), three f16 MFMAs per product
-#ifndef OVG_ATTN_X3_RING
-#define OVG_ATTN_X3_RING 3
-#endif
+constexpr int X3_RING = 3;
 int dispatch_x3(const ovg_attn_params& p, hipStream_t st) {
   Plan16 pl{};
   pl.variant = 90; pl.bq = 256; pl.splits = 1; pl.total_tiles = total_key_tiles(p); pl.per_split = pl.total_tiles;
   pl.main_rows = p.nq; pl.tail_bq = 0; pl.tail_splits = 0;
   // variant 92 (opt-in, round 6): the PV contraction without its P_lo x V_hi product -- +16 % (64 views: 28.1 -> 32.6 frames/s) at 3e-5 of the f32
   // mode at full depth, but 1.0e-4 on the camera token of the 64-view depth-1 parity case: NOT inside the mode's <= 1e-4 contract, so not the default
-  if (p.variant == 92) return launch_attn16<f16_t, 2, 8, 1, 2, true, OVG_ATTN_X3_RING, 2>(p, pl, st);
-  return launch_attn16<f16_t, 2, 8, 1, 2, true, OVG_ATTN_X3_RING, 3>(p, pl, st);
+  if (p.variant == 92) return launch_attn16<f16_t, 2, 8, 1, X3_RING, 2>(p, pl, st, 0, p.nq);
+  return launch_attn16<f16_t, 2, 8, 1, X3_RING, 3>(p, pl, st, 0, p.nq);
 }
 
 }  // namespace
@@ -577,7 +560,7 @@ extern "C" int ovg_flash_attn(const ovg_attn_params* p, void* stream) {
   if (p->fallback_count && (reinterpret_cast<uintptr_t>(p->fallback_count) & 3)) return OVG_E_ARG;
   if (p->kv_splits < 0 || p->kv_splits > OVG_MAX_SEG || p->cus < 0) return OVG_E_ARG;
   if ((p->ws_part && (reinterpret_cast<uintptr_t>(p->ws_part) & 15)) || (p->ws_lse && (reinterpret_cast<uintptr_t>(p->ws_lse) & 3))) return OVG_E_ARG;
-  if (p->kv_splits > 1 && (p->dtype == OVG_F32 || p->variant == 1 || p->variant == 2)) return OVG_E_UNSUPPORTED;   // the baseline kernel never splits
+  if (p->kv_splits > 1 && (p->dtype == OVG_F32 || p->variant == 1)) return OVG_E_UNSUPPORTED;   // the baseline kernel never splits
   if (p->ldo % 4 || p->kv_heads < 0 || p->out_bh_stride < 0 || (p->out_bh_stride > 0 && (p->ldo < OVG_D || p->out_bh_stride % 4))) return OVG_E_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   switch (p->dtype) {
@@ -602,8 +585,9 @@ extern "C" int ovg_attn_plan(const ovg_attn_params* p, ovg_attn_plan_out* out) {
   out->splits = 1; out->q_tile = 64; out->part_bytes = 0; out->lse_bytes = 0; out->main_rows = p->nq; out->tail_q_tile = 0;
   if (p->dtype == OVG_F16X2) { out->q_tile = 256; return OVG_OK; }
   if (p->dtype != OVG_BF16 && p->dtype != OVG_F16) return p->dtype == OVG_F32 ? OVG_OK : OVG_E_DTYPE;
+  if (retired_variant(p->variant)) return OVG_E_UNSUPPORTED;   // no plan for a kernel that cannot launch
   const Plan16 pl = plan16(*p, p->dtype == OVG_BF16, true);
-  if (pl.variant == 1 || pl.variant == 2) return OVG_OK;
+  if (pl.variant == 1) return OVG_OK;
   const int64_t nq_pad = p->nq_pad >= p->nq ? p->nq_pad : ((p->nq + BC - 1) / BC) * BC;
   out->splits = pl.splits; out->q_tile = pl.bq; out->main_rows = pl.main_rows; out->tail_q_tile = pl.tail_bq;
   if (pl.splits > 1) {

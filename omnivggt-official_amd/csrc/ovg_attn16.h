@@ -1,4 +1,4 @@
-// The tuned 16-bit flash-attention kernel (included by ovg_attn.hip): `attn16_kernel<T, QB, WAVES, MODE>`.
+// The tuned 16-bit flash-attention kernel (included by ovg_attn.hip): `attn16_kernel<T, QB, WAVES, MODE, RING, X3>`.
 //
 // Structure (kept from the measured iterations, see profiles/README.md):
 //  * "swapped" MFMA formulation (ovg_attn.hip header): S'^T = K Q^T with -m_ref in the MFMA C operand, so
@@ -8,10 +8,8 @@
 //    operand accumulates sum_k P (PMC on the previous kernel: VALU-active 52 % vs MFMA-busy 33 %);
 //  * __launch_bounds__(NT, 2): <= 256 VGPRs, VGPR-destination MFMAs (no v_accvgpr traffic); the file is
 //    compiled with -fno-honor-nans (no canonicalising v_max before fmaxf of MFMA results);
-//  * K / V^T tiles (64 keys) arrive by LDS-DMA (DMA = R > 0, every shipped launch): asm-issued global_load_lds_dwordx4
-//    into a ring of R = 2 B + 1 LDS slots, B + 1 tiles ahead, behind counted vmcnt waits, one workgroup barrier every
-//    B tiles (run_tiles below). DMA = 0 keeps the round-1 register-staged form (global loads of tile j+1 issued before
-//    the MFMAs of tile j, written to the other of two buffers after them, one barrier per tile) as A/B variants.
+//  * K / V^T tiles (64 keys) arrive by LDS-DMA: asm-issued global_load_lds_dwordx4 into a ring of RING = 2 B + 1 LDS
+//    slots, B + 1 tiles ahead, behind counted vmcnt waits, one workgroup barrier every B tiles (run_tiles below).
 //
 // Two softmax bodies share that structure (run_tiles<..., SM>):
 //  SM = 0  lazy-rescale online softmax: m_ref moves only when a row's tile max exceeds it by more than
@@ -33,9 +31,10 @@
 //   A/B data), so it is available (MODE 0 on f16) but not the default.
 // MODE 2 (tests): MODE 0 with the fallback forced.
 //
-// Measured dead ends, removed from the tree (logs under profiles/): LDS-DMA staging with natural-order V^T
-// (-2 %), 32-key half bodies (-1.5 %), one shared anchor per lane (-1 %), QB = 3 (-5 %), a single merged
-// rescale branch (-1 %), s_setprio around the MFMA clusters (+-0) or around the exp2/convert section (-4 %),
+// Measured dead ends, removed from the tree (logs under profiles/): the round-1 register-staged form (global loads of
+// tile j + 1 issued before the MFMAs of tile j, written to the other of two buffers after them, one barrier per tile),
+// row sums of the 16-bit kernels on the VALU, LDS-DMA staging with natural-order V^T (-2 %), 32-key half bodies
+// (-1.5 %), one shared anchor per lane (-1 %), QB = 3 (-5 %), a single merged rescale branch (-1 %), s_setprio around the MFMA clusters (+-0) or around the exp2/convert section (-4 %),
 // 2-wave workgroups (-40 %), an 8-wave ping-pong with the two waves of a SIMD forced into MFMA / VALU antiphase
 // by barriers (+-0 at S = 64, -17 % at S = 8; profiles/r01_probe_coexec.txt), and intra-wave software pipelining
 // of exp against MFMA (compiler-scheduled, sched_barrier-pinned and sched_group_barrier 1:2:1 forms: -15...-90 %).
@@ -100,18 +99,15 @@ OVG_DEV u32x4 pack2(const f32x4 a, const f32x4 b) {
 }
 
 // P tile -> (hi, lo) f16 fragments of the split-f16 mode: hi = f16(p), lo = f16(p - hi); p <= 2^8 (lazy rescale), no saturation needed.
-// OVG_ATTN_X3_SPLIT 1 (r05): 3 VALU per value pair instead of ~11 -- v_cvt_pk_f16_f32 for the hi pair, then v_fma_mixlo/mixhi_f16
-// compute f16(p * 1.0 - f32(hi half)) straight from the packed hi register (the f32 difference is exact, so the bits equal form 0's).
-#ifndef OVG_ATTN_X3_SPLIT
-#define OVG_ATTN_X3_SPLIT 1
-#endif
+// r05: 3 VALU per value pair instead of ~11 -- v_cvt_pk_f16_f32 for the hi pair, then v_fma_mixlo/mixhi_f16 compute
+// f16(p * 1.0 - f32(hi half)) straight from the packed hi register (the f32 difference is exact, so the bits equal those of the plain
+// static_cast form it replaced).
 // Products of the PV contraction of the split-f16 mode (template value X3 of the kernels; round 6, profiles/r06_f32x_pv_terms_ab.txt): 3 = P_hi V_lo
 // + P_lo V_hi + P_hi V_hi (the mode: 1.07e-5 of the f32 mode at layer 23 of 64 views, 28.1 frames/s); 2 = without P_lo V_hi (2.96e-5 there and
 // 32.6 frames/s, but 1.0e-4 on the camera token of the 64-view depth-1 parity case: opt-in through ovg_attn_params.variant 92, outside the
 // <= 1e-4 contract); P_hi V_hi alone measured 4.6e-5 / 35.2 frames/s and is not offered.
 template <bool WANT_LO = true>
 OVG_DEV void pack2_hilo(const f32x4 a, const f32x4 b, u32x4& hi, u32x4& lo) {
-#if OVG_ATTN_X3_SPLIT
   const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
   uint32_t h[4], l[4];
 #pragma unroll
@@ -127,26 +123,12 @@ OVG_DEV void pack2_hilo(const f32x4 a, const f32x4 b, u32x4& hi, u32x4& lo) {
   // the code (found in round 6: with the P_lo product removed in a lab build the convert landed directly in front of its MFMA -- garbage).
   if constexpr (WANT_LO) asm volatile("s_nop 1" : "+v"(hi), "+v"(lo));
   else asm volatile("s_nop 1" : "+v"(hi));
-#else
-  f16_t h[8], l[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    h[i] = static_cast<f16_t>(a[i]); l[i] = static_cast<f16_t>(a[i] - static_cast<float>(h[i]));
-    h[4 + i] = static_cast<f16_t>(b[i]); l[4 + i] = static_cast<f16_t>(b[i] - static_cast<float>(h[4 + i]));
-  }
-  __builtin_memcpy(&hi, h, 16);
-  __builtin_memcpy(&lo, l, 16);
-#endif
 }
 
-// lacc += sa + sb on the packed-f32 adder (r05, OVG_ATTN_X3_PKSUM 1): 4 v_pk_add_f32 per 8 values instead of 8 v_add_f32; the four registers
-// of lacc are lane-partial sums that are reduced once behind the loop, so only the ORDER of the f32 additions differs from form 0
-#ifndef OVG_ATTN_X3_PKSUM
-#define OVG_ATTN_X3_PKSUM 1
-#endif
+// lacc += sa + sb on the packed-f32 adder (r05): 4 v_pk_add_f32 per 8 values instead of 8 v_add_f32; the four registers of lacc are
+// lane-partial sums that are reduced once behind the loop, so only the ORDER of the f32 additions differs from `lacc += sa + sb`
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 OVG_DEV void rowsum_acc(f32x4& lacc, const f32x4 sa, const f32x4 sb) {
-#if OVG_ATTN_X3_PKSUM
   f32x2_t l0 = {lacc[0], lacc[1]}, l1 = {lacc[2], lacc[3]};
   const f32x2_t a0 = {sa[0], sa[1]}, a1 = {sa[2], sa[3]}, b0 = {sb[0], sb[1]}, b1 = {sb[2], sb[3]};
   asm("v_pk_add_f32 %0, %0, %1" : "+v"(l0) : "v"(a0));
@@ -154,16 +136,13 @@ OVG_DEV void rowsum_acc(f32x4& lacc, const f32x4 sa, const f32x4 sb) {
   asm("v_pk_add_f32 %0, %0, %1" : "+v"(l0) : "v"(b0));
   asm("v_pk_add_f32 %0, %0, %1" : "+v"(l1) : "v"(b1));
   lacc = f32x4{l0[0], l0[1], l1[0], l1[1]};
-#else
-  lacc += sa + sb;
-#endif
 }
 
 // One pass over all key tiles of all segments for the wave's QB x 16 query rows; leaves the un-normalised
 // O^T in o, the row sums in lacc (every register of lacc[qb] holds the full sum of row q0 + 16 qb + lane&15) and the
 // negated reference maximum in negm (P = exp2(s + negm)): log2 sum_k exp2(s) = log2(lacc) - negm.
 // (lds_dma16, the asm-issued LDS-DMA transfer the staging below uses, lives in ovg_common.h)
-// X3 (OVG_F16X2, the split-f16 parity mode; T = f16_t, SM = 0, VSUM, DMA): q, K and V^T are (hi, lo) plane pairs -- a ring slot holds
+// X3 (OVG_F16X2, the split-f16 parity mode; T = f16_t, SM = 0): q, K and V^T are (hi, lo) plane pairs -- a ring slot holds
 // [K hi | V^T hi | K lo | V^T lo] -- and both contractions run three MFMAs per product into the same f32 accumulator, small terms first:
 //   S = K_lo Q_hi + K_hi Q_lo + K_hi Q_hi,   O += V_lo P_hi + V_hi P_lo + V_hi P_hi,   P = (hi, lo) split of exp2(S - m) in registers;
 // the row sums are exact f32 sums of P on the VALU (the matrix pipe is the bound here: 104 MFMAs against ~100 VALU per tile at QB = 2).
@@ -172,12 +151,12 @@ OVG_DEV void rowsum_acc(f32x4& lacc, const f32x4 sa, const f32x4 sb) {
 // -0.6 ... -1.2 %, and a loop that issues QK^T of tile j + 1 inside the exp / split block of tile j (4-slot ring, 191 VGPRs, no spill,
 // MFMA / VALU interleaved by hipcc as intended) -2.2 ... -2.6 % -- the kernel issues 1400 TFLOP/s of f16 MFMAs, the same rate as the bf16
 // kernel with its row-sum MFMAs: neither VALU issue nor phase alignment of the two waves of a SIMD is what holds it there (section 5.1).
-template <typename T, int QB, int WAVES, int SM, bool VSUM = false, int DMA = 0, int X3 = 0>   // VSUM: row sums on the VALU (experiment, variant 31) instead of the ones-MFMA; DMA: 0 = register staging, R = 2 B + 1 (3, 5, 7, 9): K / V^T tiles by LDS-DMA into a ring of R slots, B + 1 tiles ahead, one workgroup barrier every B tiles
+template <typename T, int QB, int WAVES, int SM, int RING, int X3 = 0>   // RING = 2 B + 1 (3, 5, ...) LDS slots: K / V^T tiles arrive B + 1 tiles ahead, one workgroup barrier every B tiles
 OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int bh, const int q0, const int t_begin, const int total_tiles,
                        f32x4 (&o)[QB][4], f32x4 (&lacc)[QB], f32x4 (&negm)[QB]) {   // key tiles [t_begin, t_begin + total_tiles) of the flattened segment list
-  constexpr int NT = 64 * WAVES;
-  constexpr int RB = 128, KT_B = BC * RB, VT_B = OVG_D * RB, CPT = 512 / NT;
-  static_assert(!X3 || (DMA > 0 && VSUM && SM == 0 && std::is_same<T, f16_t>::value), "split-f16: f16 planes, LDS-DMA staging, lazy rescale, VALU row sums");
+  constexpr int RB = 128, KT_B = BC * RB, VT_B = OVG_D * RB;
+  static_assert(RING >= 3 && RING % 2 == 1, "ring = 2 * barrier period + 1");
+  static_assert(!X3 || (SM == 0 && std::is_same<T, f16_t>::value), "split-f16: f16 planes, lazy rescale (row sums on the VALU)");
   constexpr int PLANE_B = KT_B + VT_B;             // one plane of a ring slot: K tile + V^T tile
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -213,29 +192,16 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
   asm volatile("" : "+v"(ones));
 
   // ---- staging ------------------------------------------------------------------------------------------------------------
-  // Register path (DMA = false): global loads of tile j + 1 are issued before the MFMAs of tile j and written to the other LDS
-  // buffer after them (two buffers of K tile + V^T tile).  DMA path: both tiles go global -> LDS by LDS-DMA into a ring of three
-  // slots, TWO tiles ahead, no staging registers and no ds_write; every iteration issues exactly NDMA transfers per wave, so one
-  // counted s_waitcnt vmcnt(NDMA) before the barrier means "everything but the newest tile has landed".
+  // Both tiles go global -> LDS by LDS-DMA into a ring of RING slots, B + 1 tiles ahead, no staging registers and no ds_write; every
+  // iteration issues exactly NDMA transfers per wave, so one counted s_waitcnt vmcnt(NDMA) before the barrier means "everything but
+  // the newest tile has landed".
   //   lane l of a transfer -> LDS row l / 8, chunk position l % 8 of that row <- source chunk (l % 8) ^ swizzle(row), i.e. the LDS image
   //   is the XOR-swizzled tile the fragment reads expect (K rows = keys, V^T rows = features with the vt_pos16 key order).
-  //   Barrier period B = (DMA - 1) / 2: the waves only meet every B tiles (between barriers they drift apart by up to B tiles, so
+  //   Barrier period B = (RING - 1) / 2: the waves only meet every B tiles (between barriers they drift apart by up to B tiles, so
   //   their MFMA-heavy and exp-heavy phases stop coinciding). At the barrier after tile j - 1 (j = 0 mod B) the tiles j .. j + B - 1
   //   must have landed: with the transfers issued B + 1 tiles ahead that is "all but the newest tile" = vmcnt(NDMA). A slot is
   //   rewritten (tile j + B + 1 -> the slot of tile j - B) only after a barrier that follows the last read of tile j - B: R >= 2 B + 1.
-  constexpr int SLOT_B = (X3 ? 2 : 1) * PLANE_B, NDMA = (X3 ? 2 : 1) * 2 * (8 / WAVES), BARP = DMA ? (DMA - 1) / 2 : 1;
-  static_assert(DMA == 0 || (DMA == 2 * BARP + 1 && BARP >= 1), "ring = 2 * barrier period + 1");
-  u32x4 rk[DMA ? 1 : CPT], rv[DMA ? 1 : CPT];
-  int k_goff[CPT], v_row[CPT], v_coff[CPT], k_loff[CPT], v_loff[CPT];
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int c = tid + NT * i;
-    const int row = c >> 3, ch = c & 7;
-    k_goff[i] = c * 16;
-    k_loff[i] = swz_off<128>(row, ch);
-    v_row[i] = row; v_coff[i] = ch * 16;
-    v_loff[i] = swz_off<128>(row, ch);             // global V^T rows already hold the fragment order (vt_pos16)
-  }
+  constexpr int SLOT_B = (X3 ? 2 : 1) * PLANE_B, NDMA = (X3 ? 2 : 1) * 2 * (8 / WAVES), BARP = (RING - 1) / 2;
   int fseg = 0, ftile = t_begin;                   // split-KV: this pass starts t_begin tiles into the segment list
   int f_ntiles = (int)((p.seg[0].nk + BC - 1) / BC);
   while (ftile >= f_ntiles) { ftile -= f_ntiles; ++fseg; f_ntiles = (int)((p.seg[fseg].nk + BC - 1) / BC); }
@@ -265,24 +231,7 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
       }
     }
   };
-  auto fetch = [&]() {
-#pragma unroll
-    for (int i = 0; i < (DMA ? 1 : CPT); ++i) {
-      rk[i] = *reinterpret_cast<const u32x4*>(kptr + k_goff[i]);
-      rv[i] = *reinterpret_cast<const u32x4*>(vptr + v_row[i] * vstride + v_coff[i]);
-    }
-    next_tile();
-  };
-  auto stash = [&](int buf) {
-    unsigned char* kl = lds + buf * (KT_B + VT_B);
-    unsigned char* vl = kl + KT_B;
-#pragma unroll
-    for (int i = 0; i < (DMA ? 1 : CPT); ++i) {
-      *reinterpret_cast<u32x4*>(kl + k_loff[i]) = rk[i];
-      *reinterpret_cast<u32x4*>(vl + v_loff[i]) = rv[i];
-    }
-  };
-  // DMA path: per-lane source offsets of the wave's 8 / WAVES transfers per tile and the wave-uniform LDS destinations
+  // per-lane source offsets of the wave's 8 / WAVES transfers per tile and the wave-uniform LDS destinations
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
   int d_row[8 / WAVES], d_ch16[8 / WAVES];
@@ -315,16 +264,10 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
   const int frag_row = lr * 128;
   const int coff0 = ((0 + g) ^ sx) << 4, coff1 = ((4 + g) ^ sx) << 4;
 
-  if constexpr (DMA) {
 #pragma unroll
-    for (int t = 0; t < BARP + 1; ++t) dma_issue(t);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");     // tiles 0 .. B - 1 have landed (this wave's share), tile B may be in flight
-    __builtin_amdgcn_s_barrier();
-  } else {
-    fetch();
-    stash(0);
-    __syncthreads();
-  }
+  for (int t = 0; t < BARP + 1; ++t) dma_issue(t);
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");       // tiles 0 .. B - 1 have landed (this wave's share), tile B may be in flight
+  __builtin_amdgcn_s_barrier();
 
   // S'^T blocks s[kt][qb] (keys 16 kt .. 16 kt + 15) of the tile in LDS at kl, dead keys masked to -inf
   auto qk_tile = [&](const unsigned char* kl, f32x4 (&s)[4][QB], bool tail, int kv0) {
@@ -415,8 +358,7 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
       pf[qb] = pack2<T>(sa[qb], sb[qb]);
-      if constexpr (VSUM) lacc[qb] += sa[qb] + sb[qb];   // lane-partial sums (4 registers x 4 lanes per row), reduced once after the loop
-      else lacc[qb] = mma_c<T>(ones, pf[qb], lacc[qb]);
+      lacc[qb] = mma_c<T>(ones, pf[qb], lacc[qb]);
     }
     const int voff = ((4 * u + g) ^ sx) << 4;
 #pragma unroll
@@ -428,7 +370,7 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
   };
 
   if constexpr (SM == 2) {
-    // anchor: m_ref = row max over the first key tile (tile 0 is in LDS buffer 0 now)
+    // anchor: m_ref = row max over the first key tile (tile 0 is in ring slot 0 now)
     f32x4 s[4][QB];
     qk_tile(lds, s, (tile0 + 1) * BC > c_nk, tile0 * BC);
 #pragma unroll
@@ -452,7 +394,7 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
 #define PB_MFMA_ACC(acc, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
 #define PB_SPLIT(kt, qb) do { s[kt][qb][0] = t[kt][qb][0]; s[kt][qb][1] = t[kt][qb][1]; s[kt][qb][2] = t[kt][qb][2]; s[kt][qb][3] = t[kt][qb][3]; } while (0)
 #define PB_PACK(u, qb) pf[u][qb] = u32x4{pw[u][qb][0], pw[u][qb][1], pw[u][qb][2], pw[u][qb][3]}
-  constexpr bool PIPE = SM == 2 && (QB == 4 || QB == 2) && DMA > 0 && !VSUM && std::is_same<T, bf16_t>::value;
+  constexpr bool PIPE = SM == 2 && (QB == 4 || QB == 2) && std::is_same<T, bf16_t>::value;
   auto pipe_tile = [&](int slot) {
     if constexpr (PIPE) {
       const uint32_t kb = lds_base + slot * SLOT_B + frag_row;
@@ -480,17 +422,12 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
 #undef PB_PACK
 
   int since_barrier = 0;
-  int buf = 0;                                     // register path: LDS buffer of tile j; DMA path: ring slot of tile j
-  // the loop body as a generic lambda, instantiated twice -- the order-pinned body for the leading FULL tiles of a single-segment
-  // launch, the compiler-scheduled body for the rest (the masked last tile; every tile of a multi-segment launch) -- so that the
+  int buf = 0;                                     // ring slot of tile j
+  // the loop body as a generic lambda, instantiated twice -- the order-pinned body for the FULL tiles of a segment, the
+  // compiler-scheduled body for the rest (a segment's masked last tile; every tile of the kernels without a pinned body) -- so that the
   // hot loop holds ONE body (with both in one loop hipcc joins their register assignments with ~50 copies and spills O)
   auto tile_iter = [&](int j, auto use_pipe) {
-    const bool more = (j + 1) < total_tiles;
-    if constexpr (DMA) {
-      dma_issue(buf >= BARP ? buf - BARP : buf - BARP + DMA);   // tile j + B + 1 -> slot (j - B) % R
-    } else {
-      if (more) fetch();
-    }
+    dma_issue(buf >= BARP ? buf - BARP : buf - BARP + RING);   // tile j + B + 1 -> slot (j - B) % RING
     const unsigned char* kl = lds + buf * SLOT_B;
     const unsigned char* vl = kl + KT_B;
     const int kv0 = ctile * BC;
@@ -532,43 +469,30 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
       ctile = 0; ++cseg;
       if (cseg < p.nseg) { c_nk = (int)p.seg[cseg].nk; c_ntiles = (c_nk + BC - 1) / BC; }
     }
-    if constexpr (DMA) {
-      // every B tiles: all but the newest tile's transfers (this wave's share) have landed -> a bare barrier publishes the next B
-      // tiles and retires the last B. No __syncthreads (its fence drains vmcnt); the waves never write LDS themselves.
-      if (BARP == 1 || ++since_barrier == BARP) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
-        __builtin_amdgcn_s_barrier();
-        since_barrier = 0;
-      }
-      buf = buf == DMA - 1 ? 0 : buf + 1;
-    } else {
-      if (more) stash(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
+    // every B tiles: all but the newest tile's transfers (this wave's share) have landed -> a bare barrier publishes the next B
+    // tiles and retires the last B. No __syncthreads (its fence drains vmcnt); the waves never write LDS themselves.
+    if (BARP == 1 || ++since_barrier == BARP) {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
+      __builtin_amdgcn_s_barrier();
+      since_barrier = 0;
     }
+    buf = buf == RING - 1 ? 0 : buf + 1;
   };
   int j_all = 0;
-  // OVG_ATTN_PIPE_LOOP (A/B builds, tools/probes/build_alt.py): 2 (shipped) = the pinned body on every FULL tile of every segment,
-  // 1 = on the leading full tiles of single-segment launches only (the form of the first r04 passes), 0 = compiler-scheduled body everywhere.
+  // OVG_ATTN_PIPE_LOOP: 2 (shipped) = the pinned body on every FULL tile of every segment, 0 = compiler-scheduled body everywhere (what
+  // build.py falls back to when its check of the pinned hot loops fails). The first r04 passes pinned only the leading full tiles of
+  // single-segment launches (removed; profiles/r04_attn_ab_loop_forms.txt).
   // History of form 2 (profiles/r04_attn_ab_loop_forms.txt): its first build computed a WRONG speculative pass -- with the outer loop around
   // the two bodies hipcc rematerialised the constant all-ones operand of the row-sum MFMAs inside the hot loop (s_mov + v_mov_b64 directly
   // in front of the asm MFMA that reads it: a VALU-write -> MFMA-read hazard nobody pads for inline asm), every row sum was garbage, every
   // workgroup failed its verification and re-ran (688 of 688, 2.1x slower, results exact, all parity tests green: found by the fallback
-  // counter). With `ones` made opaque to the optimiser (above) the form is bit-identical to form 1 and +5.0 % on the 8-segment per-rank
+  // counter). With `ones` made opaque to the optimiser (above) the form is bit-identical to that earlier one and +5.0 % on the 8-segment per-rank
   // launch of the view-sharded run (-0.3 ... -0.4 % on single-segment launches: noise level).
   // tests/test_attn_body_generator.py::test_pinned_hot_loops_hold_no_compiler_copies guards the shipped kernels against such copies.
 #ifndef OVG_ATTN_PIPE_LOOP
 #define OVG_ATTN_PIPE_LOOP 2
 #endif
-#if OVG_ATTN_PIPE_LOOP == 1
-  if constexpr (PIPE) {
-    // full tiles in front of the first masked one: single segment, tiles tile0 .. ; tile t is full iff (t + 1) * BC <= nk
-    int n_full = p.nseg == 1 ? (int)(p.seg[0].nk / BC) - tile0 : 0;
-    n_full = n_full < total_tiles ? n_full : total_tiles;
-    for (; j_all < n_full; ++j_all) tile_iter(j_all, std::true_type{});
-    asm volatile("s_nop 15\n\ts_nop 15");     // asm MFMA results -> VALU / builtin readers behind the loop (hipcc does not see the hazard)
-  }
-#elif OVG_ATTN_PIPE_LOOP == 2
+#if OVG_ATTN_PIPE_LOOP == 2
   if constexpr (PIPE) {
     // Segment by segment (one segment on a single GPU; one per rank / source after a view-sharded exchange): the FULL tiles of the
     // segment in a loop of the pinned body, then its masked last tile, if any, through the compiler-scheduled body (one call per segment)
@@ -582,8 +506,8 @@ OVG_DEV void run_tiles(const ovg_attn_params& p, unsigned char* lds, const int b
   }
 #endif
   for (; j_all < total_tiles; ++j_all) tile_iter(j_all, std::false_type{});
-  if constexpr (DMA) __syncthreads();              // drain the tail transfers before the ring is reused (fallback pass) or the workgroup ends
-  if constexpr (VSUM) {
+  __syncthreads();                                 // drain the tail transfers before the ring is reused (fallback pass) or the workgroup ends
+  if constexpr (X3 != 0) {                         // split-f16: the lane-partial VALU row sums -> the full sum in every register
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
       const float t = quad16_sum(lacc[qb][0] + lacc[qb][1] + lacc[qb][2] + lacc[qb][3]);
@@ -631,11 +555,11 @@ OVG_DEV void write_out(const ovg_attn_params& p, const f32x4 (&o)[QB][4], const 
 }  // namespace attn16
 
 // MODE: 0 = speculative anchored softmax + verified fallback, 1 = lazy-rescale only, 2 = forced fallback (tests)
-template <typename T, int QB, int WAVES, int MODE, int OCC = 2, bool VSUM = false, int DMA = 0, int X3 = 0>   // OCC: minimum waves per SIMD the register allocation must allow; X3: split-f16 planes (run_tiles)
-__global__ __launch_bounds__(64 * WAVES, OCC) void attn16_kernel(ovg_attn_params p, int nqt, int total_tiles, int splits, int per_split, int q_row0, int part_rows) {   // q tiles [0, nqt) of the rows starting at q_row0; part_rows: rows per entry of the split workspace
+template <typename T, int QB, int WAVES, int MODE, int RING, int X3 = 0>   // RING: LDS slots of the K / V^T ring, X3: split-f16 planes (run_tiles)
+__global__ __launch_bounds__(64 * WAVES, 2) void attn16_kernel(ovg_attn_params p, int nqt, int total_tiles, int splits, int per_split, int q_row0, int part_rows) {   // q tiles [0, nqt) of the rows starting at q_row0; part_rows: rows per entry of the split workspace
   static_assert(sizeof(T) == 2, "16-bit types only");
   constexpr int RB = 128, KT_B = BC * RB, VT_B = OVG_D * RB, BQ = 16 * QB * WAVES;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[(DMA ? DMA : 2) * (X3 ? 2 : 1) * (KT_B + VT_B)];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[RING * (X3 ? 2 : 1) * (KT_B + VT_B)];
 
   const int tid = threadIdx.x, wave = tid >> 6;
   // logical id -> (batch entry, key split, q tile), q tile fastest: the workgroups that run side by side on an XCD share
@@ -649,10 +573,10 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn16_kernel(ovg_attn_params
 
   f32x4 o[QB][4], lacc[QB], negm[QB];
   if constexpr (MODE == 1) {
-    attn16::run_tiles<T, QB, WAVES, 0, VSUM, DMA, X3>(p, lds, bh, q0, t0, nt, o, lacc, negm);
+    attn16::run_tiles<T, QB, WAVES, 0, RING, X3>(p, lds, bh, q0, t0, nt, o, lacc, negm);
   } else {
     static_assert(!X3, "split-f16 runs the lazy-rescale body only");
-    attn16::run_tiles<T, QB, WAVES, 2, VSUM, DMA>(p, lds, bh, q0, t0, nt, o, lacc, negm);
+    attn16::run_tiles<T, QB, WAVES, 2, RING>(p, lds, bh, q0, t0, nt, o, lacc, negm);
     bool bad = MODE == 2;
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
@@ -667,7 +591,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn16_kernel(ovg_attn_params
       // the ARITHMETIC of an accepted speculative pass (no overflowed row sum, nothing non-finite); that the order-pinned instruction stream
       // itself is intact (no compiler copy inside an MFMA hazard window) is certified at BUILD time by build.check_pinned_attention_loops.
       if (p.fallback_count != nullptr && threadIdx.x == 0) atomicAdd(p.fallback_count, 1u);
-      attn16::run_tiles<T, QB, WAVES, 0, VSUM, DMA>(p, lds, bh, q0, t0, nt, o, lacc, negm);
+      attn16::run_tiles<T, QB, WAVES, 0, RING>(p, lds, bh, q0, t0, nt, o, lacc, negm);
     }
   }
 

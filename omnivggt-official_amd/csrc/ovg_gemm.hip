@@ -49,27 +49,13 @@ OVG_DEV void tl_mark(int) {}
 OVG_DEV void tl_stagger() {}
 #endif
 
-// exact-erf GELU (nn.GELU default, mlp.py:22).  f32 parity mode calls libm's erff; the 16-bit modes
-// use Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7, far below bf16/f16 resolution): PMC showed the
-// erff expansion (~40 VALU per element) cost as many VALU instructions as the whole fc1 main loop.
-OVG_DEV float erf_as(float x) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(ax * ax * -1.4426950408889634f);
-  return copysignf(fmaf(-p * t, e, 1.0f), x);
-}
-template <typename T> OVG_DEV float gelu_erf(float x) {
-  if constexpr (sizeof(T) == 4) return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-  else return 0.5f * x * (1.0f + erf_as(x * 0.70710678118654752440f));
-}
+// exact-erf GELU (nn.GELU default, mlp.py:22) of the f32 and split-f16 parity modes: libm's erff (~40 VALU per element; PMC showed it
+// costing as many VALU instructions as the whole fc1 main loop, hence the polynomial form below for the 16-bit modes)
+OVG_DEV float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 // Transcendental-free form for the 16-bit modes (r03): GELU(x) = x * Phi(x), Phi(x) = 1/2 + xc * R(xc^2), xc = clamp(x, -5, 5),
 // R a degree-12 minimax polynomial in u = 2 xc^2 / 25 - 1 (fitted against erf in double; evaluated in f32 Horner form the
-// error of GELU is <= 2.2e-6 absolute for |x| <= 12 and <= 3e-7 |x| beyond: two decimal orders below bf16 / f16 resolution,
-// the same class as erf_as). 17 plain VALU operations, 16 of them FMA / MUL that hipcc pairs into v_pk_fma_f32 / v_pk_mul_f32
+// error of GELU is <= 2.2e-6 absolute for |x| <= 12 and <= 3e-7 |x| beyond: two decimal orders below bf16 / f16 resolution).
+// 17 plain VALU operations, 16 of them FMA / MUL that hipcc pairs into v_pk_fma_f32 / v_pk_mul_f32
 // across neighbouring elements, no v_rcp / v_exp and none of the ~2 s_nop per element their result hazards cost
 // (ISA of the fc1 epilogue: 13.5 -> 9 issue slots per element).
 // One row block of a lane (16 values) at a time, Horner step by Horner step ACROSS the 8 register pairs: a v_pk_fma_f32 that
@@ -232,9 +218,9 @@ OVG_DEV void gemm_mainloop(const T* __restrict__ X, int64_t ldx, const T* __rest
 // Now: the per-column vectors (bias, gamma) are loaded ONCE per wave, the row loop bodies are branch-free (row
 // indices clamped for the loads, only the store is predicated), so the four residual / table loads of a row block
 // -- and, registers permitting, the next row block's -- are in flight together.
-template <typename T, int EPI, bool OUT_F32, int MT, bool INJECT, int XP = 0, bool X3 = false>   // XP = 1 (OVG_TILE_R02_EPILOGUE, A/B flag): the r02 erf_as GELU instead of the polynomial one; X3: split-f16 outputs (hi / lo planes), libm erff
-OVG_DEV void linear_epilogue_impl(const ovg_linear_params& p, const f32x4 (&acc)[4][MT], const int m_w0, const int n_w0, const int row_lim = -1) {
-  const int M = row_lim >= 0 ? row_lim : (int)p.M, N = (int)p.N;   // row_lim: rows >= it belong to somebody else (unused by the shipped kernels: -1)
+template <typename T, int EPI, bool OUT_F32, int MT, bool INJECT, bool X3 = false>   // X3: split-f16 outputs (hi / lo planes), libm erff
+OVG_DEV void linear_epilogue_impl(const ovg_linear_params& p, const f32x4 (&acc)[4][MT], const int m_w0, const int n_w0) {
+  const int M = (int)p.M, N = (int)p.N;
   const int lane = threadIdx.x & 63, g = lane >> 4, lr = lane & 15;
   const int ncol = n_w0 + 4 * g;                       // this lane's first column of n-block 0; block nt adds 16 nt
   f32x4 bias[4], gam[4];
@@ -309,25 +295,20 @@ OVG_DEV void linear_epilogue_impl(const ovg_linear_params& p, const f32x4 (&acc)
     for (int nt = 0; nt < 4; ++nt) {
       v[nt] = acc[nt][mt] + bias[nt];
       if constexpr (EPI == OVG_EPI_GELU) {
-        if constexpr (XP || sizeof(T) == 4 || X3) {  // f32 / split-f16 parity modes: libm erff; XP (A/B flag OVG_TILE_R02_EPILOGUE): the r02 erf_as form; else the polynomial form below
-          using GT = typename std::conditional<X3, float, T>::type;
-          v[nt][0] = gelu_erf<GT>(v[nt][0]); v[nt][1] = gelu_erf<GT>(v[nt][1]); v[nt][2] = gelu_erf<GT>(v[nt][2]); v[nt][3] = gelu_erf<GT>(v[nt][3]);
-        }
-        if constexpr (std::is_same<T, f16_t>::value && XP) {
-          // f16 range guard: the hidden activation is the one 16-bit tensor fed by an unnormalised f32 sum (DINOv2-style
-          // massive activations reach 1e3..1e4 after fc1); saturate at the largest finite f16 instead of storing +inf
-          // (inf * 0-weight = NaN in fc2). GELU is bounded below by -0.17, so only the upper side needs it.
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[nt][r] = fminf(v[nt][r], 65504.0f);
+        if constexpr (sizeof(T) == 4 || X3) {          // f32 / split-f16 parity modes: libm erff; 16-bit modes: the polynomial form below
+          v[nt][0] = gelu_erf(v[nt][0]); v[nt][1] = gelu_erf(v[nt][1]); v[nt][2] = gelu_erf(v[nt][2]); v[nt][3] = gelu_erf(v[nt][3]);
         }
       }
       if constexpr (EPI == OVG_EPI_RES) v[nt] = ex[cs][nt] + gam[nt] * v[nt];
       if constexpr (EPI == OVG_EPI_RES && INJECT) v[nt] += on[cs] * inj[cs][nt];
       if constexpr (EPI == OVG_EPI_PATCH) v[nt] += ex[cs][nt];
     }
-    if constexpr (EPI == OVG_EPI_GELU && !XP && !X3 && sizeof(T) == 2) {
+    if constexpr (EPI == OVG_EPI_GELU && !X3 && sizeof(T) == 2) {
       gelu_poly16(v);
       if constexpr (std::is_same<T, f16_t>::value) {
+        // f16 range guard: the hidden activation is the one 16-bit tensor fed by an unnormalised f32 sum (DINOv2-style
+        // massive activations reach 1e3..1e4 after fc1); saturate at the largest finite f16 instead of storing +inf
+        // (inf * 0-weight = NaN in fc2). GELU is bounded below by -0.17, so only the upper side needs it.
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -463,19 +444,19 @@ OVG_DEV void linear_epilogue_staged(const ovg_linear_params& p, const f32x4 (&ac
   }
 }
 
-template <typename T, int EPI, bool OUT_F32, int MT, int XP = 0, bool X3 = false>
-OVG_DEV void linear_epilogue(const ovg_linear_params& p, const f32x4 (&acc)[4][MT], const int m_w0, const int n_w0, const int row_lim = -1) {
+template <typename T, int EPI, bool OUT_F32, int MT, bool X3 = false>
+OVG_DEV void linear_epilogue(const ovg_linear_params& p, const f32x4 (&acc)[4][MT], const int m_w0, const int n_w0) {
   if constexpr (EPI == OVG_EPI_RES) {
-    if (p.inject != nullptr) { linear_epilogue_impl<T, EPI, OUT_F32, MT, true, XP, X3>(p, acc, m_w0, n_w0, row_lim); return; }
+    if (p.inject != nullptr) { linear_epilogue_impl<T, EPI, OUT_F32, MT, true, X3>(p, acc, m_w0, n_w0); return; }
   }
-  linear_epilogue_impl<T, EPI, OUT_F32, MT, false, XP, X3>(p, acc, m_w0, n_w0, row_lim);
+  linear_epilogue_impl<T, EPI, OUT_F32, MT, false, X3>(p, acc, m_w0, n_w0);
 }
 
-// Which epilogue a wave of a 16-bit kernel takes (wave-uniform): the staged one unless the caller pinned the r02 register form (XP), the output
+// Which epilogue a wave of a 16-bit kernel takes (wave-uniform): the staged one unless the output
 // cannot take 16-byte stores, or -- residual form -- one of the wave's rows is a camera-injection row (m % inj_period == 0: 1 row in 1374).
-template <typename T, int EPI, bool OUT_F32, int MT, int XP, bool X3 = false>
+template <typename T, int EPI, bool OUT_F32, int MT, bool X3 = false>
 OVG_DEV void linear_epilogue_auto(const ovg_linear_params& p, const f32x4 (&acc)[4][MT], const int m_w0, const int n_w0, unsigned char* img) {
-  if constexpr (!XP && sizeof(T) == 2) {
+  if constexpr (sizeof(T) == 2) {
     if constexpr ((EPI == OVG_EPI_STORE || EPI == OVG_EPI_GELU) && !OUT_F32 && !X3) {   // split-f16 outputs (two planes) keep the register form
       if (((p.ldy * (int64_t)sizeof(T)) & 15) == 0) { linear_epilogue_staged<T, EPI, MT>(p, acc, m_w0, n_w0, img); return; }
     }
@@ -488,11 +469,11 @@ OVG_DEV void linear_epilogue_auto(const ovg_linear_params& p, const f32x4 (&acc)
       if (!inj_here) { linear_epilogue_staged<T, EPI, MT>(p, acc, m_w0, n_w0, img); return; }
     }
   }
-  linear_epilogue<T, EPI, OUT_F32, MT, XP, X3>(p, acc, m_w0, n_w0);
+  linear_epilogue<T, EPI, OUT_F32, MT, X3>(p, acc, m_w0, n_w0);
 }
 
 
-template <typename T, int EPI, bool OUT_F32, int XP = 0, bool X3 = false>
+template <typename T, int EPI, bool OUT_F32, bool X3 = false>
 __global__ __launch_bounds__(256, 2) void linear_kernel(ovg_linear_params p, int ntiles_n) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 128 * 128];
   const int M = (int)p.M, N = (int)p.N, K = (int)p.K;
@@ -507,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void linear_kernel(ovg_linear_params p, int
   tl_mark(2);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // gemm_mainloop ends behind a __syncthreads: both stage buffers (32 KB) are idle, wave w owns 8 KB of them
-  linear_epilogue_auto<T, EPI, OUT_F32, 4, XP, X3>(p, acc, m0 + (wave & 1) * 64, n0 + (wave >> 1) * 64, lds + wave * 8192);
+  linear_epilogue_auto<T, EPI, OUT_F32, 4, X3>(p, acc, m0 + (wave & 1) * 64, n0 + (wave >> 1) * 64, lds + wave * 8192);
   tl_mark(3);
 }
 
@@ -668,9 +649,9 @@ OVG_DEV void qk_epilogue(const ovg_qkv_params& p, f32x4 (&acc)[4][MT], const int
 // four consecutive tokens of one feature per register group = ONE 8-byte store into V^T [B*H, 64, nk_pad] (the first
 // version held 4 features of one token and issued 16 two-byte stores per row block, each block fenced by a vmcnt(0)).
 template <typename T, int MT, bool X3 = false>
-OVG_DEV void v_epilogue(const ovg_qkv_params& p, const f32x4 (&acc)[4][MT], const int m_w0, const int ncol0_, const int row_lim = -1) {
+OVG_DEV void v_epilogue(const ovg_qkv_params& p, const f32x4 (&acc)[4][MT], const int m_w0, const int ncol0_) {
   const int ncol0 = __builtin_amdgcn_readfirstlane(ncol0_);
-  const int M = row_lim >= 0 ? row_lim : (int)p.M, seq = (int)p.seq;
+  const int M = (int)p.M, seq = (int)p.seq;
   const int lane = threadIdx.x & 63, g = lane >> 4, lr = lane & 15;
   const int h = (ncol0 % OVG_C) / OVG_D;
   const FastDiv div_seq(seq);
@@ -780,9 +761,9 @@ __global__ __launch_bounds__(256, 3) void qkv_kernel(ovg_qkv_params p, int nt_be
     gemm_mainloop<T, false, X3>(static_cast<const T*>(p.x), p.ldx, static_cast<const T*>(p.w), (int64_t)K, M, N, K, m0, n0, lds, acc,
                                 static_cast<const T*>(p.x_lo), static_cast<const T*>(p.w_lo));
     // behind the main loop's last __syncthreads the two stage buffers are idle: wave w stages its head rows through 8 KB of them
-    // (the OVG_TILE_R02_EPILOGUE flag keeps the r02 per-lane 8-byte stores: A/B; the split-f16 mode writes two planes from registers)
+    // (16-bit modes; the split-f16 mode writes two planes from registers)
     tl_mark(2);
-    unsigned char* img = (sizeof(T) == 2 && !X3 && !(p.tile & OVG_TILE_R02_EPILOGUE)) ? lds + __builtin_amdgcn_readfirstlane(wave) * 8192 : nullptr;
+    unsigned char* img = (sizeof(T) == 2 && !X3) ? lds + __builtin_amdgcn_readfirstlane(wave) * 8192 : nullptr;
     qk_epilogue<T, 4, X3>(p, acc, m0 + (wave & 1) * 64, n0 + (wave >> 1) * 64, p.rope_cos, p.rope_sin, img);
   }
   tl_mark(3);
@@ -791,7 +772,7 @@ __global__ __launch_bounds__(256, 3) void qkv_kernel(ovg_qkv_params p, int nt_be
 #include "ovg_gemm256.h"
 
 // 256 x 256 variants (16-bit modes): same epilogues on acc[4][8]
-template <typename T, int EPI, bool OUT_F32, int XP = 0, bool X3 = false>
+template <typename T, int EPI, bool OUT_F32, bool X3 = false>
 __global__ __launch_bounds__(512) void linear256_kernel(ovg_linear_params p, int ntiles_n) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds256[];
   const int M = (int)p.M, N = (int)p.N, K = (int)p.K;
@@ -806,7 +787,7 @@ __global__ __launch_bounds__(512) void linear256_kernel(ovg_linear_params p, int
   tl_mark(2);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // the ring is idle: mainloop() returns behind its last barrier, every DMA waited for; wave w owns 16 KB of it
-  linear_epilogue_auto<T, EPI, OUT_F32, 8, XP, X3>(p, acc, m0 + (wave >> 2) * 128, n0 + (wave & 3) * 64, lds256 + wave * 16384);
+  linear_epilogue_auto<T, EPI, OUT_F32, 8, X3>(p, acc, m0 + (wave >> 2) * 128, n0 + (wave & 3) * 64, lds256 + wave * 16384);
   tl_mark(3);
 }
 
@@ -832,8 +813,11 @@ __global__ __launch_bounds__(512) void qkv256_kernel(ovg_qkv_params p, int nt_be
     stage_rope_table(p, lds256 + g256::LDS_BYTES, 8);      // older than every stage DMA: retired by the loop's first counted wait, visible after its barriers
     g256::mainloop<T, false, X3>(static_cast<const T*>(p.x), p.ldx, static_cast<const T*>(p.w), (int64_t)K, M, N, K, m0, n0, lds256, acc,
                                   static_cast<const T*>(p.x_lo), static_cast<const T*>(p.w_lo));
-    // the OVG_TILE_R02_EPILOGUE flag keeps the r02 per-lane 8-byte stores (A/B); otherwise whole head rows through the idle ring
-    unsigned char* img = (X3 || (p.tile & OVG_TILE_R02_EPILOGUE)) ? nullptr : lds256 + __builtin_amdgcn_readfirstlane(wave) * 16384;
+    // whole head rows through the idle ring (the split-f16 mode writes two planes from registers)
+    // scheduling fence where the staged and the register epilogue used to part: without it hipcc interleaves the main loop's last
+    // k-stage with the epilogue set-up differently from the schedule every measurement of this kernel was taken with
+    if constexpr (!X3) __builtin_amdgcn_sched_barrier(0);
+    unsigned char* img = X3 ? nullptr : lds256 + __builtin_amdgcn_readfirstlane(wave) * 16384;
     tl_mark(2);
     qk_epilogue<T, 8, X3>(p, acc, m0 + (wave >> 2) * 128, n0 + (wave & 3) * 64, rope_tab, rope_tab + 128 * 16, img);
   }
@@ -863,71 +847,32 @@ constexpr int TILE_GROUP = 8, TILE_GROUP256 = 4;
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <typename T, int XP>
-int launch_linear128_xp(const ovg_linear_params& p, hipStream_t st) {
-  const int mt = (int)((p.M + BM - 1) / BM), nt = (int)(p.N / BN);
-  const dim3 grid(mt * nt), block(256);
-  const int ntg = nt | (TILE_GROUP << 16);
-  switch (p.epilogue) {
-    case OVG_EPI_STORE:
-      if (p.out_f32) OVG_LAUNCH((linear_kernel<T, OVG_EPI_STORE, true, XP>), grid, block, 0, st, p, ntg);
-      else OVG_LAUNCH((linear_kernel<T, OVG_EPI_STORE, false, XP>), grid, block, 0, st, p, ntg);
-      break;
-    case OVG_EPI_GELU:
-      OVG_LAUNCH((linear_kernel<T, OVG_EPI_GELU, false, XP>), grid, block, 0, st, p, ntg);
-      break;
-    case OVG_EPI_RES:
-      OVG_LAUNCH((linear_kernel<T, OVG_EPI_RES, true, XP>), grid, block, 0, st, p, ntg);
-      break;
-    case OVG_EPI_PATCH:
-      OVG_LAUNCH((linear_kernel<T, OVG_EPI_PATCH, true, XP>), grid, block, 0, st, p, ntg);
-      break;
-    default: return OVG_E_ARG;
-  }
-  OVG_CHECK_LAUNCH();
-  return OVG_OK;
-}
-template <typename T>
-int launch_linear128(const ovg_linear_params& p, hipStream_t st) {
+// One linear launch: the 256 x 256 kernel (16-bit modes, `big`) or the 128 x 128 one
+template <typename T, int EPI, bool OUT_F32, bool X3>
+int launch_linear_one(const ovg_linear_params& p, hipStream_t st, bool big) {
   if constexpr (sizeof(T) == 2) {
-#ifdef OVG_AB_VARIANTS
-    if (p.tile & OVG_TILE_R02_EPILOGUE) return launch_linear128_xp<T, 1>(p, st);      // A/B flag: the r02 epilogue forms
-#else
-    if (p.tile & OVG_TILE_R02_EPILOGUE) return OVG_E_UNSUPPORTED;                      // A/B history: only in -DOVG_AB_VARIANTS builds
-#endif
-  }
-  return launch_linear128_xp<T, 0>(p, st);
-}
-template <typename T, int EPI, bool OUT_F32, int XP = 0>
-int launch_linear256_one(const ovg_linear_params& p, hipStream_t st) {
-  const int ok = allow_big_lds(linear256_kernel<T, EPI, OUT_F32, XP>);
-  if (ok != OVG_OK) return ok;
-  const int mt = (int)((p.M + g256::BM2 - 1) / g256::BM2), nt = (int)(p.N / g256::BN2);
-  const int ntg = nt | (TILE_GROUP256 << 16);
-  OVG_LAUNCH((linear256_kernel<T, EPI, OUT_F32, XP>), dim3(mt * nt), dim3(512), g256::LDS_BYTES, st, p, ntg);
-  OVG_CHECK_LAUNCH();
-  return OVG_OK;
-}
-template <typename T>
-int launch_linear256(const ovg_linear_params& p, hipStream_t st, bool xp) {
-#ifdef OVG_AB_VARIANTS
-  if (xp) {                                          // A/B flag: the r02 epilogue forms
-    switch (p.epilogue) {
-      case OVG_EPI_STORE: return p.out_f32 ? launch_linear256_one<T, OVG_EPI_STORE, true>(p, st) : launch_linear256_one<T, OVG_EPI_STORE, false, 1>(p, st);
-      case OVG_EPI_GELU: return launch_linear256_one<T, OVG_EPI_GELU, false, 1>(p, st);
-      case OVG_EPI_RES: return launch_linear256_one<T, OVG_EPI_RES, true, 1>(p, st);
-      case OVG_EPI_PATCH: return launch_linear256_one<T, OVG_EPI_PATCH, true>(p, st);
-      default: return OVG_E_ARG;
+    if (big) {
+      const int ok = allow_big_lds(linear256_kernel<T, EPI, OUT_F32, X3>);
+      if (ok != OVG_OK) return ok;
+      const int mt = (int)((p.M + g256::BM2 - 1) / g256::BM2), nt = (int)(p.N / g256::BN2);
+      OVG_LAUNCH((linear256_kernel<T, EPI, OUT_F32, X3>), dim3(mt * nt), dim3(512), g256::LDS_BYTES, st, p, nt | (TILE_GROUP256 << 16));
+      OVG_CHECK_LAUNCH();
+      return OVG_OK;
     }
   }
-#else
-  if (xp) return OVG_E_UNSUPPORTED;                  // A/B history: only in -DOVG_AB_VARIANTS builds
-#endif
+  const int mt = (int)((p.M + BM - 1) / BM), nt = (int)(p.N / BN);
+  OVG_LAUNCH((linear_kernel<T, EPI, OUT_F32, X3>), dim3(mt * nt), dim3(256), 0, st, p, nt | (TILE_GROUP << 16));
+  OVG_CHECK_LAUNCH();
+  return OVG_OK;
+}
+// (epilogue, out_f32) -> kernel instantiation; GELU writes the compute type, RES / PATCH always f32
+template <typename T, bool X3>
+int dispatch_linear(const ovg_linear_params& p, hipStream_t st, bool big) {
   switch (p.epilogue) {
-    case OVG_EPI_STORE: return p.out_f32 ? launch_linear256_one<T, OVG_EPI_STORE, true>(p, st) : launch_linear256_one<T, OVG_EPI_STORE, false>(p, st);
-    case OVG_EPI_GELU: return launch_linear256_one<T, OVG_EPI_GELU, false>(p, st);
-    case OVG_EPI_RES: return launch_linear256_one<T, OVG_EPI_RES, true>(p, st);
-    case OVG_EPI_PATCH: return launch_linear256_one<T, OVG_EPI_PATCH, true>(p, st);
+    case OVG_EPI_STORE: return p.out_f32 ? launch_linear_one<T, OVG_EPI_STORE, true, X3>(p, st, big) : launch_linear_one<T, OVG_EPI_STORE, false, X3>(p, st, big);
+    case OVG_EPI_GELU: return launch_linear_one<T, OVG_EPI_GELU, false, X3>(p, st, big);
+    case OVG_EPI_RES: return launch_linear_one<T, OVG_EPI_RES, true, X3>(p, st, big);
+    case OVG_EPI_PATCH: return launch_linear_one<T, OVG_EPI_PATCH, true, X3>(p, st, big);
     default: return OVG_E_ARG;
   }
 }
@@ -952,9 +897,6 @@ int launch_linear256(const ovg_linear_params& p, hipStream_t st, bool xp) {
 //       rounds) -1.5 %, so not beyond one round;
 //   proj (residual epilogue, K = 1024) only where the 128 x 128 launch would spill into such a second round (tiles128 > 3 x CUs).
 // kind: 0 = other, 1 = fc1 (GELU), 2 = fc2 (RES, K >= 2048), 3 = proj (RES, K < 2048)
-#ifndef OVG_PROJ_256_ONE_ROUND
-#define OVG_PROJ_256_ONE_ROUND 1
-#endif
 int gemm_device_cus() {
   static const int n = [] {
     int dev = 0, v = 0;
@@ -963,8 +905,7 @@ int gemm_device_cus() {
   }();
   return n;
 }
-int choose_256(int tile_arg, bool sixteen_bit, int64_t M, int64_t N, int64_t K, bool light_epilogue_or_long_k, int kind = 0) {
-  const int tile = tile_arg & ~OVG_TILE_R02_EPILOGUE;      // the A/B flag does not take part in the tile choice
+int choose_256(int tile, bool sixteen_bit, int64_t M, int64_t N, int64_t K, bool light_epilogue_or_long_k, int kind = 0) {
   const bool legal = sixteen_bit && N % g256::BN2 == 0 && K % 64 == 0;
   if (tile == OVG_TILE_128) return 0;
   if (tile == OVG_TILE_256) return legal ? 1 : -1;
@@ -974,7 +915,7 @@ int choose_256(int tile_arg, bool sixteen_bit, int64_t M, int64_t N, int64_t K, 
   const int64_t cus = gemm_device_cus();
   const int64_t t256 = ((M + 255) / 256) * (N / 256), t128 = ((M + 127) / 128) * (N / 128);
   if (kind == 2 && M >= 8000 && t256 <= cus) return 1;
-  if (OVG_PROJ_256_ONE_ROUND && kind == 3 && t256 <= cus && t128 > 3 * cus) return 1;
+  if (kind == 3 && t256 <= cus && t128 > 3 * cus) return 1;
   return 0;
 }
 
@@ -983,38 +924,35 @@ int launch_linear(const ovg_linear_params& p, hipStream_t st) {
   const int big = choose_256(p.tile, sizeof(T) == 2, p.M, p.N, p.K, p.epilogue != OVG_EPI_RES || p.K >= 2048,
                              p.epilogue == OVG_EPI_GELU ? 1 : (p.epilogue == OVG_EPI_RES ? (p.K >= 2048 ? 2 : 3) : 0));
   if (big < 0) return OVG_E_ARG;
-  if constexpr (sizeof(T) == 2) {
-    if (big) return launch_linear256<T>(p, st, (p.tile & OVG_TILE_R02_EPILOGUE) != 0);
-  }
-  return launch_linear128<T>(p, st);
+  return dispatch_linear<T, false>(p, st, big != 0);
 }
 
 // split-f16 mode (OVG_F16X2): the same kernels with X3 = true on f16 planes; 256 x 256 tiles from M >= 20 000 rows on (three times the
 // main loop per epilogue: the ping-pong loop's advantage grows), register-form epilogues for the two-plane 16-bit outputs
-template <int EPI, bool OUT_F32>
-int launch_linear_x3_one(const ovg_linear_params& p, hipStream_t st, bool big) {
-  if (big) {
-    const int ok = allow_big_lds(linear256_kernel<f16_t, EPI, OUT_F32, 0, true>);
-    if (ok != OVG_OK) return ok;
-    const int mt = (int)((p.M + g256::BM2 - 1) / g256::BM2), nt = (int)(p.N / g256::BN2);
-    OVG_LAUNCH((linear256_kernel<f16_t, EPI, OUT_F32, 0, true>), dim3(mt * nt), dim3(512), g256::LDS_BYTES, st, p, nt | (TILE_GROUP256 << 16));
-  } else {
-    const int mt = (int)((p.M + BM - 1) / BM), nt = (int)(p.N / BN);
-    OVG_LAUNCH((linear_kernel<f16_t, EPI, OUT_F32, 0, true>), dim3(mt * nt), dim3(256), 0, st, p, nt | (TILE_GROUP << 16));
+int launch_linear_x3(const ovg_linear_params& p, hipStream_t st) {
+  const int big = choose_256(p.tile, true, p.M, p.N, p.K, true);
+  if (big < 0) return OVG_E_ARG;
+  return dispatch_linear<f16_t, true>(p, st, big != 0);
+}
+
+// One QKV launch over the n tiles [nt_begin, nt_begin + nt_count) (in units of the chosen tile width)
+template <typename T, bool X3>
+int launch_qkv(const ovg_qkv_params& p, hipStream_t st, bool big, int nt_begin, int nt_count) {
+  if constexpr (sizeof(T) == 2) {
+    if (big) {
+      constexpr int lds_bytes = g256::LDS_BYTES + ROPE_LDS_BYTES;
+      const int ok = allow_big_lds(qkv256_kernel<T, X3>, lds_bytes);
+      if (ok != OVG_OK) return ok;
+      const dim3 grid((unsigned)(((p.M + g256::BM2 - 1) / g256::BM2) * nt_count));
+      OVG_LAUNCH((qkv256_kernel<T, X3>), grid, dim3(512), lds_bytes, st, p, nt_begin, nt_count | (TILE_GROUP256 << 16));
+      OVG_CHECK_LAUNCH();
+      return OVG_OK;
+    }
   }
+  const dim3 grid((unsigned)(((p.M + BM - 1) / BM) * nt_count));
+  OVG_LAUNCH((qkv_kernel<T, X3>), grid, dim3(256), 0, st, p, nt_begin, nt_count | (TILE_GROUP << 16));
   OVG_CHECK_LAUNCH();
   return OVG_OK;
-}
-int launch_linear_x3(const ovg_linear_params& p, hipStream_t st) {
-  int big = choose_256(p.tile, true, p.M, p.N, p.K, true);
-  if (big < 0) return OVG_E_ARG;
-  switch (p.epilogue) {
-    case OVG_EPI_STORE: return p.out_f32 ? launch_linear_x3_one<OVG_EPI_STORE, true>(p, st, big) : launch_linear_x3_one<OVG_EPI_STORE, false>(p, st, big);
-    case OVG_EPI_GELU: return launch_linear_x3_one<OVG_EPI_GELU, false>(p, st, big);
-    case OVG_EPI_RES: return launch_linear_x3_one<OVG_EPI_RES, true>(p, st, big);
-    case OVG_EPI_PATCH: return launch_linear_x3_one<OVG_EPI_PATCH, true>(p, st, big);
-    default: return OVG_E_ARG;
-  }
 }
 
 #ifdef OVG_GEMM_TIMELINE
@@ -1046,6 +984,7 @@ extern "C" int ovg_linear(const ovg_linear_params* p, void* stream) {
     const int64_t osz = p->out_f32 ? 4 : esz;
     if ((p->ldy * osz) % (4 * osz)) return OVG_E_ARG;
   }
+  if (p->tile & OVG_TILE_R02_EPILOGUE) return OVG_E_UNSUPPORTED;   // retired A/B selectors (OVG_TILE_128X / OVG_TILE_256X)
   hipStream_t st = static_cast<hipStream_t>(stream);
   switch (p->dtype) {
     case OVG_BF16: return launch_linear<bf16_t>(*p, st);
@@ -1080,42 +1019,18 @@ extern "C" int ovg_qkv(const ovg_qkv_params* p, void* stream) {
     if (p->max_pos > 128 || !aligned16(p->rope_cos) || !aligned16(p->rope_sin)) return OVG_E_ARG;   // the table is staged in 16 KB of LDS
   }
   if (p->part < 0 || p->part > 2) return OVG_E_ARG;
+  if (p->tile & OVG_TILE_R02_EPILOGUE) return OVG_E_UNSUPPORTED;   // retired A/B selectors (OVG_TILE_128X / OVG_TILE_256X)
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int big = choose_256(p->tile, p->dtype != OVG_F32, p->M, (p->part == 0 ? 3 : (p->part == 1 ? 2 : 1)) * OVG_C, OVG_C, true);
   if (big < 0) return OVG_E_ARG;
-  if (big) {
-    const int q_t = OVG_C / g256::BN2, all_t = 3 * OVG_C / g256::BN2;
-    const int ntb = p->part == 1 ? q_t : 0;
-    const int ntc = p->part == 0 ? all_t : (p->part == 1 ? all_t - q_t : q_t);
-    const dim3 grid2((unsigned)(((p->M + g256::BM2 - 1) / g256::BM2) * ntc));
-    const int ntg2 = ntc | (TILE_GROUP256 << 16);
-    if (p->dtype == OVG_BF16) {
-      const int ok = allow_big_lds(qkv256_kernel<bf16_t>, g256::LDS_BYTES + ROPE_LDS_BYTES);
-      if (ok != OVG_OK) return ok;
-      OVG_LAUNCH((qkv256_kernel<bf16_t>), grid2, dim3(512), g256::LDS_BYTES + ROPE_LDS_BYTES, st, *p, ntb, ntg2);
-    } else if (p->dtype == OVG_F16X2) {
-      const int ok = allow_big_lds(qkv256_kernel<f16_t, true>, g256::LDS_BYTES + ROPE_LDS_BYTES);
-      if (ok != OVG_OK) return ok;
-      OVG_LAUNCH((qkv256_kernel<f16_t, true>), grid2, dim3(512), g256::LDS_BYTES + ROPE_LDS_BYTES, st, *p, ntb, ntg2);
-    } else {
-      const int ok = allow_big_lds(qkv256_kernel<f16_t>, g256::LDS_BYTES + ROPE_LDS_BYTES);
-      if (ok != OVG_OK) return ok;
-      OVG_LAUNCH((qkv256_kernel<f16_t>), grid2, dim3(512), g256::LDS_BYTES + ROPE_LDS_BYTES, st, *p, ntb, ntg2);
-    }
-    OVG_CHECK_LAUNCH();
-    return OVG_OK;
-  }
-  const int q_tiles = OVG_C / BN, all_tiles = 3 * OVG_C / BN;
+  // part 0: all of q | k | v; 1: k | v; 2: q -- as a range of n tiles of the chosen width
+  const int q_tiles = OVG_C / (big ? g256::BN2 : BN), all_tiles = 3 * q_tiles;
   const int nt_begin = p->part == 1 ? q_tiles : 0;
   const int nt_count = p->part == 0 ? all_tiles : (p->part == 1 ? all_tiles - q_tiles : q_tiles);
-  const dim3 grid((unsigned)(((p->M + BM - 1) / BM) * nt_count)), block(256);
-  const int ntg = nt_count | (TILE_GROUP << 16);
   switch (p->dtype) {
-    case OVG_BF16: OVG_LAUNCH((qkv_kernel<bf16_t>), grid, block, 0, st, *p, nt_begin, ntg); break;
-    case OVG_F16: OVG_LAUNCH((qkv_kernel<f16_t>), grid, block, 0, st, *p, nt_begin, ntg); break;
-    case OVG_F16X2: OVG_LAUNCH((qkv_kernel<f16_t, true>), grid, block, 0, st, *p, nt_begin, ntg); break;
-    default: OVG_LAUNCH((qkv_kernel<float>), grid, block, 0, st, *p, nt_begin, ntg); break;
+    case OVG_BF16: return launch_qkv<bf16_t, false>(*p, st, big != 0, nt_begin, nt_count);
+    case OVG_F16: return launch_qkv<f16_t, false>(*p, st, big != 0, nt_begin, nt_count);
+    case OVG_F16X2: return launch_qkv<f16_t, true>(*p, st, big != 0, nt_begin, nt_count);
+    default: return launch_qkv<float, false>(*p, st, false, nt_begin, nt_count);
   }
-  OVG_CHECK_LAUNCH();
-  return OVG_OK;
 }

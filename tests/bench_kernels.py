@@ -146,7 +146,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["attn", "gemm", "all"])
     ap.add_argument("--views", type=int, nargs="+", default=[8, 16])
-    ap.add_argument("--variants", type=int, nargs="+", default=[1, 0, 50], help="see dispatch16 in ovg_attn.hip (history variants need a -DOVG_AB_VARIANTS build)")
+    ap.add_argument("--variants", type=int, nargs="+", default=[1, 0, 50], help="see dispatch16 in ovg_attn.hip (the retired history variants answer UNSUPPORTED)")
     ap.add_argument("--modes", nargs="+", default=["global", "frame"])
     ap.add_argument("--kv-splits", type=int, nargs="+", default=[1], help="attn: split-KV factors to compare (1 = off, 0 = library plan, 2..8 forced)")
     ap.add_argument("--rounds", type=int, default=5)

@@ -212,8 +212,8 @@ def attn_reference(q, k, v):
     return torch.softmax(s, dim=-1) @ v
 
 
-# the kernels of the product library (the A/B history -- variants 2, 6, 8, 18, 19, 21, 25, 31-33, 51, 56, 58, 59 -- is compiled only with
-# -DOVG_AB_VARIANTS and answers OVG_E_UNSUPPORTED here): default plan, baseline, LDS-DMA staged speculative 256-row / lazy 256-row / forced
+# the kernels of the library (the A/B history -- variants 2, 6, 8, 18, 19, 21, 25, 31-33, 51, 56, 58, 59 -- left the tree and answers
+# OVG_E_UNSUPPORTED): default plan, baseline, LDS-DMA staged speculative 256-row / lazy 256-row / forced
 # fallback / speculative + lazy 128-row / speculative 512-row with a barrier every 2 tiles, and the plan's A/B knobs (71-73: tail splits)
 ATTN16_VARIANTS = (0, 1, 50, 52, 53, 54, 55, 57)
 

@@ -74,9 +74,9 @@ def test_gemm256_kernels_every_epilogue_ragged_m():
 
 
 def test_history_variants_are_not_in_the_product_library():
-    """Round-4 review, hygiene: the A/B history (r02 epilogue forms, attention variants of rounds 1-3) is compiled only into
-    tools/probes/build_alt.py builds (-DOVG_AB_VARIANTS); the product library refuses them by name. The round-5 lab GEMM selectors
-    (4 = persistent 256 x 256, 10 = DMA-in-M) left the ABI in round 6: they are plain argument errors now."""
+    """Round-4 review, hygiene: the A/B history (r02 epilogue forms, attention variants of rounds 1-4) is not in the library, which refuses
+    its selectors by name -- from ovg_linear and ovg_qkv, ovg_flash_attn and ovg_attn_plan alike, and without launching anything. The
+    round-5 lab GEMM selectors (4 = persistent 256 x 256, 10 = DMA-in-M) left the ABI in round 6: they are plain argument errors."""
     import torch
     from omnivggt_official_amd import ops
     x = torch.zeros(512, 1024, device="cuda", dtype=torch.bfloat16)
@@ -87,10 +87,29 @@ def test_history_variants_are_not_in_the_product_library():
     for tile in (4, 10, 42):
         with pytest.raises(L.OvgError, match="ARG"):
             ops.linear(x, w, None, torch.bfloat16, tile=tile)
-    q, k, vt = ops.alloc_qkv(16, 256, 256, torch.bfloat16, "cuda")
-    for variant in (6, 21, 33, 51, 59):
+    # ovg_qkv: M = 512 rows as two sequences of 256; a refused call writes nothing
+    wqkv = torch.zeros(3 * 1024, 1024, device="cuda", dtype=torch.bfloat16)
+    bqkv = torch.zeros(3 * 1024, device="cuda", dtype=torch.float32)
+    q, k, vt = ops.alloc_qkv(32, 256, 256, torch.bfloat16, "cuda")
+    for t in (q, k, vt):
+        t.fill_(-7.0)
+    for tile in (L.TILE_128X, L.TILE_256X):
         with pytest.raises(L.OvgError, match="UNSUPPORTED"):
-            ops.flash_attn(q, [(k, vt, 256)], 256, torch.bfloat16, variant=variant)
+            ops.qkv(x, wqkv, bqkv, 256, torch.bfloat16, q, k, vt, tile=tile)
+    for tile in (4, 10, 42):
+        with pytest.raises(L.OvgError, match="ARG"):
+            ops.qkv(x, wqkv, bqkv, 256, torch.bfloat16, q, k, vt, tile=tile)
+    torch.cuda.synchronize()
+    for t in (q, k, vt):
+        assert bool((t == -7.0).all())
+    retired = (2, 6, 8, 18, 19, 21, 25, 31, 32, 33, 51, 56, 58, 59)
+    for dt in (torch.bfloat16, torch.float16):
+        q, k, vt = ops.alloc_qkv(16, 256, 256, dt, "cuda")
+        for variant in retired:
+            with pytest.raises(L.OvgError, match="UNSUPPORTED"):
+                ops.flash_attn(q, [(k, vt, 256)], 256, dt, variant=variant)
+            with pytest.raises(L.OvgError, match="UNSUPPORTED"):
+                ops.attn_plan(16, 256, [256], dt, variant=variant)
 
 
 def test_global_attention_at_bench_key_counts():

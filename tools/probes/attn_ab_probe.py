@@ -1,7 +1,7 @@
 """In-process A/B of attention launches across library builds (the product + tools/probes/_build/*): interleaved timing on the same
 tensors, bit comparison against the product, and the speculative-softmax fallback counter of every launch.
 
-    python tools/probes/attn_ab_probe.py [--shapes s8 s16 rank8] [--rounds 4] [--names pipe1 pipe0]"""
+    python tools/probes/attn_ab_probe.py [--shapes s8 s16 rank8] [--rounds 4] [--names pipe0]"""
 import argparse
 import ctypes as C
 import os

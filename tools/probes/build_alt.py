@@ -2,7 +2,7 @@
 tools/probes/_build/<name>/libomnivggt_hip.so (git-ignored; travels to the GPU box with the snapshot).
 
     python tools/probes/build_alt.py name=-DFLAG=VALUE[,-DFLAG2=...] ...
-    e.g. python tools/probes/build_alt.py pipe1=-DOVG_ATTN_PIPE_LOOP=1 pipe0=-DOVG_ATTN_PIPE_LOOP=0
+    e.g. python tools/probes/build_alt.py pipe0=-DOVG_ATTN_PIPE_LOOP=0 tl=-DOVG_GEMM_TIMELINE
 
 Only ovg_attn.hip is recompiled per variant when every flag names an OVG_ATTN_* macro (the other objects are shared)."""
 import os
