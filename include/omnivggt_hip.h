@@ -60,7 +60,8 @@ extern "C" {
  *       so the number stays; a binding looks the two symbols up by name and reports a library that predates them
  *     + point-cloud rendering (ovg_render_points, ovg_render_workspace_bytes): added the same way, looked up by name
  *     + multi-view depth consistency (ovg_multiview_consistency, ovg_consistency_workspace_bytes): added the same way
- *     + nearest-neighbour search between point clouds (ovg_nearest_neighbours, ovg_nn_workspace_bytes): added the same way */
+ *     + nearest-neighbour search between point clouds (ovg_nearest_neighbours, ovg_nn_workspace_bytes): added the same way
+ *     + farthest-point sampling of point clouds (ovg_farthest_point_sample, ovg_fps_workspace_bytes): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -707,6 +708,56 @@ typedef struct {
 } ovg_nn_params;
 int64_t ovg_nn_workspace_bytes(int64_t nq, int64_t nr);
 int ovg_nearest_neighbours(const ovg_nn_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Farthest-point sampling of point clouds (added under ABI 13): npoint well-spread points of each of `batch` clouds, chosen one
+ * after the other, each the point farthest from everything chosen so far. The rule is exact (tests/fps_twin.py restates it in numpy
+ * float32 bit for bit) and reproduces the deterministic path of the reference's farthest_point_sample index for index.
+ *   points [batch][n][3] f32, contiguous; valid [batch][n] u8 is optional (NULL: all valid).
+ *   usable: as in ovg_nearest_neighbours -- all three coordinates finite and the valid byte (if given) non-zero.
+ *   state: mind[j] = float32(1e10) for every j (the reference's initial value, kept on purpose: a squared distance never counts
+ *   for more than 1e10, and points that far from every sample tie and are taken in index order).
+ *   step i = 0 .. npoint - 1 has a centre c:
+ *     step 0: c = first;  step 1 with OVG_FPS_INCLUDE_LAST: c = n - 1 (both FORCED: taken whether usable or not);
+ *     otherwise c = the usable j that maximises bits(mind[j]), the LOWEST j on ties; c = -1 when no point is usable.
+ *   outputs of the step: index[i] = c; sqdist[i] = mind[c] as it stood BEFORE this step's update (1e10 for the first sample and
+ *   for a forced centre that is unusable, whose mind never changes), +inf when c = -1. From the first non-forced sample on, sqdist
+ *   never increases: it is the squared coverage radius of the samples before it.
+ *   update: if c >= 0 and point c is usable, then for every usable j: dx = p[j].x - p[c].x, dy, dz likewise,
+ *   d = (dx dx + dy dy) + dz dz, every operation rounded to f32 on its own (no fused multiply-add; an overflow to +inf is fine),
+ *   mind[j] = d if d < mind[j]. A forced centre that is unusable is written to index as is and updates nothing.
+ *   distance [batch][n] f32 (optional, may be NULL): mind after the last step, +inf for unusable points. For usable points it equals
+ *   min(1e10, the sqdist ovg_nearest_neighbours reports against the usable sampled points) byte for byte.
+ *   When fewer distinct usable points than npoint exist the rule repeats the lowest-index usable point (all mind are 0 by then).
+ * Two forms, identical bytes:
+ *   OVG_FPS_PATH_ONE_WORKGROUP (n <= OVG_FPS_SMALL_MAX): one workgroup per cloud runs all npoint steps in one launch, coordinates
+ *   and mind in registers, the cloud staged once in LDS so that the next centre is an LDS broadcast read; per step a per-thread
+ *   best, a wave reduction of the packed key and one LDS round across the waves. ws is not used.
+ *   OVG_FPS_PATH_PER_STEP (any n): one launch per sample over a grid of (ceil(n / OVG_FPS_TILE), batch); mind lives in ws; every
+ *   workgroup reads the centre the previous launch chose from that step's key slot, updates its slice and merges
+ *   key = (bits(mind) << 32) | (0xFFFFFFFF - j) with a 64-bit unsigned atomic max into the next step's slot (0 = none: a real key
+ *   has a non-zero low word since j < 2^31). Stream order between the launches is the only synchronisation between workgroups:
+ *   no workgroup ever waits for another. npoint + 1 launches, + 1 for distance.
+ *   OVG_FPS_PATH_AUTO: one workgroup when n <= OVG_FPS_SMALL_MAX, else per step.
+ *   ws: >= ovg_fps_workspace_bytes(batch, n, npoint) bytes, 16-byte aligned, whatever the path: per cloud the npoint + 1 u64 key slots,
+ *   then the n f32 mind, 4 n + 8 (npoint + 1) bytes rounded up to 16. The query returns -1 unless 1 <= batch <= 65535,
+ *   1 <= n < 2^31 and 1 <= npoint < 2^31. index [batch][npoint] int32, sqdist [batch][npoint] f32. Nothing is allocated or read back.
+ *   OVG_E_ARG: NULL params / points / ws / index / sqdist, a bad batch / n / npoint, first outside [0, n), unknown flags, an unknown
+ *   path, OVG_FPS_PATH_ONE_WORKGROUP with n > OVG_FPS_SMALL_MAX, a pointer that is not 4-byte aligned, a misaligned or undersized
+ *   workspace.
+ * ------------------------------------------------------------------ */
+enum { OVG_FPS_SMALL_MAX = 8192, OVG_FPS_TILE = 1024 };
+enum { OVG_FPS_INCLUDE_LAST = 1 };
+enum { OVG_FPS_PATH_AUTO = 0, OVG_FPS_PATH_ONE_WORKGROUP = 1, OVG_FPS_PATH_PER_STEP = 2 };
+typedef struct {
+  const float* points; const uint8_t* valid;
+  int64_t batch; int64_t n; int64_t npoint; int64_t first;
+  int32_t flags; int32_t path;
+  void* ws; int64_t ws_bytes;
+  int32_t* index; float* sqdist; float* distance;
+} ovg_fps_params;
+int64_t ovg_fps_workspace_bytes(int64_t batch, int64_t n, int64_t npoint);
+int ovg_farthest_point_sample(const ovg_fps_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

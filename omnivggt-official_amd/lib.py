@@ -235,6 +235,16 @@ class NnParams(C.Structure):
                 ("flags", i32), ("splits", i32), ("ws", vp), ("ws_bytes", i64), ("index", vp), ("sqdist", vp)]
 
 
+FPS_SMALL_MAX, FPS_TILE = 8192, 1024                         # largest cloud of the one-workgroup form, points per workgroup of the per-step form
+FPS_INCLUDE_LAST = 1
+FPS_PATH_AUTO, FPS_PATH_ONE_WORKGROUP, FPS_PATH_PER_STEP = 0, 1, 2
+
+
+class FpsParams(C.Structure):
+    _fields_ = [("points", vp), ("valid", vp), ("batch", i64), ("n", i64), ("npoint", i64), ("first", i64), ("flags", i32), ("path", i32),
+                ("ws", vp), ("ws_bytes", i64), ("index", vp), ("sqdist", vp), ("distance", vp)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -308,6 +318,8 @@ SYMBOLS = {
     "ovg_consistency_workspace_bytes": (i64, [i32, i32, i32]),
     "ovg_nearest_neighbours": (i32, [C.POINTER(NnParams), vp]),
     "ovg_nn_workspace_bytes": (i64, [i64, i64]),
+    "ovg_farthest_point_sample": (i32, [C.POINTER(FpsParams), vp]),
+    "ovg_fps_workspace_bytes": (i64, [i64, i64, i64]),
 }
 
 

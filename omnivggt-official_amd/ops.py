@@ -771,3 +771,51 @@ def nearest_neighbours(query, reference, query_valid=None, reference_valid=None,
     p.ws, p.ws_bytes, p.index, p.sqdist = L.ptr(ws), nbytes(ws), L.ptr(index), L.ptr(sqdist)
     L.call("ovg_nearest_neighbours", p, _stream())
     return index, sqdist
+
+
+def fps_workspace_bytes(batch, n, npoint):
+    for v in (batch, n, npoint):
+        if not -(1 << 63) <= int(v) < (1 << 63):
+            raise L.OvgError("ovg_fps_workspace_bytes: unsupported (batch=%d, n=%d, npoint=%d)" % (batch, n, npoint))
+    b = L.load().ovg_fps_workspace_bytes(int(batch), int(n), int(npoint))
+    if b < 0:
+        raise L.OvgError("ovg_fps_workspace_bytes: unsupported (batch=%d, n=%d, npoint=%d)" % (batch, n, npoint))
+    return int(b)
+
+
+def farthest_point_sample(points, npoint, valid=None, first=0, include_last=False, path=0, ws=None, index=None, sqdist=None, distance=None):
+    """ovg_farthest_point_sample on contiguous device tensors: points f32 [B, N, 3], valid u8 [B, N] or None. -> (index int32
+    [B, npoint], sqdist f32 [B, npoint], distance): sample i of a cloud is the usable point farthest from samples 0 .. i - 1 (lowest index
+    on ties; sample 0 is `first`, sample 1 is N - 1 with include_last), sqdist its squared distance to them (1e10 for the first), -1 /
+    +inf where a cloud has no usable point. path: L.FPS_PATH_AUTO lets the library choose, L.FPS_PATH_ONE_WORKGROUP / L.FPS_PATH_PER_STEP
+    force a form; all give the same bytes. ws: an optional uint8 device tensor of at least fps_workspace_bytes(B, N, npoint) bytes;
+    index / sqdist: optional outputs to write into; distance: None, or True to allocate, or an f32 [B, N] tensor to fill with every
+    point's squared distance to the nearest sample (returned as the third value, else None). Nothing is read back."""
+    _chk_dev(points, valid, ws, index, sqdist, None if isinstance(distance, bool) else distance)
+    if points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 3 or points.shape[2] != 3:
+        raise L.OvgError("farthest_point_sample: points must be a contiguous f32 tensor [B, N, 3]")
+    B, N, npoint = int(points.shape[0]), int(points.shape[1]), int(npoint)
+    if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or tuple(valid.shape) != (B, N)):
+        raise L.OvgError("farthest_point_sample: valid must be a contiguous u8 tensor [%d, %d]" % (B, N))
+    need = fps_workspace_bytes(B, N, npoint)
+    if ws is None or nbytes(ws) < need:
+        ws = torch.empty(need, device=points.device, dtype=torch.uint8)
+    if index is None:
+        index = torch.empty(B, npoint, device=points.device, dtype=torch.int32)
+    if sqdist is None:
+        sqdist = torch.empty(B, npoint, device=points.device, dtype=torch.float32)
+    if index.dtype != torch.int32 or sqdist.dtype != torch.float32 or index.numel() != B * npoint or sqdist.numel() != B * npoint or \
+            not (index.is_contiguous() and sqdist.is_contiguous()):
+        raise L.OvgError("farthest_point_sample: index / sqdist must be contiguous int32 / f32 tensors [%d, %d]" % (B, npoint))
+    if distance is True:
+        distance = torch.empty(B, N, device=points.device, dtype=torch.float32)
+    elif distance is False:
+        distance = None
+    if distance is not None and (distance.dtype != torch.float32 or distance.numel() != B * N or not distance.is_contiguous()):
+        raise L.OvgError("farthest_point_sample: distance must be a contiguous f32 tensor [%d, %d]" % (B, N))
+    p = L.FpsParams()
+    p.points, p.valid, p.batch, p.n, p.npoint, p.first = L.ptr(points), L.ptr(valid), B, N, npoint, int(first)
+    p.flags, p.path = L.FPS_INCLUDE_LAST if include_last else 0, int(path)
+    p.ws, p.ws_bytes, p.index, p.sqdist, p.distance = L.ptr(ws), nbytes(ws), L.ptr(index), L.ptr(sqdist), L.ptr(distance)
+    L.call("ovg_farthest_point_sample", p, _stream())
+    return index, sqdist, distance

@@ -521,6 +521,84 @@ def cloud_distance(pred, gt, threshold=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# Farthest-point sampling: a fixed number of well-spread points (ovg_farthest_point_sample)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class FPSResult:
+    """Result of farthest_point_sample: index int32 (the sampled points in selection order, -1 where a cloud has no usable point),
+    sqdist float32 (each sample's squared distance to the samples before it, 1e10 for the first, +inf with index -1) and distance
+    (float32, every point's squared distance to its nearest sample, +inf for unusable points; None unless asked for)."""
+    __slots__ = ("index", "sqdist", "distance")
+
+    def __init__(self, index, sqdist, distance=None):
+        self.index, self.sqdist, self.distance = index, sqdist, distance
+
+
+def farthest_point_sample(xyz, npoint, valid=None, include_ends=False, first=0, return_distance=False):
+    """npoint well-spread points of every cloud, chosen on the device one after the other (ovg_farthest_point_sample): sample 0 is point
+    `first`, every further sample is the point farthest from all samples so far. The deterministic path of the reference's
+    farthest_point_sample (omnivggt/utils/po_utils/misc.py, a Python loop of torch launches), index for index: the rule is exact
+    (tests/fps_twin.py restates it in numpy float32): d = (dx dx + dy dy) + dz dz in float32 without fused multiply-adds, every point
+    keeps the smallest d to a sample, starting from the reference's 1e10 (distances saturate there: points farther than 1e5 from every
+    sample tie), the largest wins and ties go to the LOWEST index, so two calls, and both forms of the kernel, give identical bytes.
+    include_ends: sample 1 is the last point (the reference's option; needs N >= 2). A point is usable when its coordinates are
+    finite and its valid entry (if given) is non-zero: unusable points are never chosen (only forced: `first`, or the last point
+    with include_ends, are reported as they are and change nothing). With fewer distinct usable points than npoint the lowest-index
+    usable point repeats, as in the reference.
+
+    xyz: float32 device tensor (N, 3) or (B, N, 3), or a PointCloud (its points); valid: optional bool / uint8 tensor (N,) / (B, N).
+    -> FPSResult(index, sqdist, distance) shaped (npoint,) or (B, npoint) (distance: (N,) or (B, N) with return_distance, else None).
+    index is int32 like NNResult's (the reference returns int64); sqdist from the first free sample on never increases: it is the
+    squared coverage radius of the samples before it. npoint > N raises ValueError (the reference turns random there), so does
+    include_ends with N < 2; N == 0 or npoint == 0 give empty results. No device -> host synchronisation. CPU tensors raise OvgError
+    (there is no CPU fallback); bad shapes or dtypes raise ValueError."""
+    x = xyz.points if isinstance(xyz, PointCloud) else xyz
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or x.shape[-1] != 3 or x.dtype != torch.float32:
+        raise ValueError("xyz must be a float32 tensor (N, 3) or (B, N, 3) or a PointCloud")
+    lead, N = tuple(x.shape[:-2]), int(x.shape[-2])
+    if isinstance(npoint, bool) or not isinstance(npoint, int) or npoint < 0:
+        raise ValueError("npoint must be a non-negative integer, got %r" % (npoint,))
+    if isinstance(first, bool) or not isinstance(first, int):
+        raise ValueError("first must be an integer, got %r" % (first,))
+    if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != lead + (N,) or valid.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError("valid must be a bool / uint8 tensor shaped %r" % (lead + (N,),))
+    if npoint > N:
+        raise ValueError("farthest_point_sample: npoint %d exceeds the %d points of a cloud" % (npoint, N))
+    if include_ends and N < 2:
+        raise ValueError("farthest_point_sample: include_ends needs at least two points")
+    if N >= 1 << 31:
+        raise ValueError("a cloud holds %d points: the sampler takes fewer than 2^31" % N)
+    if N and not 0 <= first < N:
+        raise ValueError("farthest_point_sample: first %d is outside [0, %d)" % (first, N))
+    if not all(t is None or t.is_cuda for t in (x, valid)):
+        raise ops.L.OvgError("farthest_point_sample needs HIP device tensors: there is no CPU fallback")
+    B = 1 if not lead else lead[0]
+    if N == 0 or npoint == 0 or B == 0:
+        dist = torch.full(lead + (N,), float("inf"), device=x.device, dtype=torch.float32) if return_distance else None
+        return FPSResult(torch.empty(lead + (npoint,), device=x.device, dtype=torch.int32),
+                         torch.empty(lead + (npoint,), device=x.device, dtype=torch.float32), dist)
+    v = None if valid is None else (valid.to(torch.uint8) if valid.dtype == torch.bool else valid).reshape(B, N).contiguous()
+    idx, sq, dist = ops.farthest_point_sample(x.reshape(B, N, 3).contiguous(), npoint, v, first=first, include_last=bool(include_ends),
+                                              distance=bool(return_distance))
+    return FPSResult(idx.reshape(lead + (npoint,)), sq.reshape(lead + (npoint,)), None if dist is None else dist.reshape(lead + (N,)))
+
+
+def farthest_point_downsample(cloud, n, first=0):
+    """The n farthest-point samples of a PointCloud (farthest_point_sample from point `first`) as a PointCloud, in selection order:
+    a preview or evaluation subset of exactly n well-spread points, where voxel_downsample gives one point per cell. points, colors and
+    conf are gathered, `indices` are the input cloud's at the samples when it has them (so they still name pixels of the prediction
+    maps) and the positions in the input cloud otherwise; transform, extrinsic, conf_threshold and scene_scale are passed through
+    unchanged. write_ply, write_glb and render_point_cloud accept the result as they are. Samples of -1 (a cloud without a usable
+    point) are dropped; counting them is the one device -> host synchronisation. n above the cloud's size raises ValueError."""
+    M = len(cloud)
+    res = farthest_point_sample(cloud.points.reshape(M, 3), n, first=first)
+    idx = res.index[res.index >= 0].long()                                  # the one synchronisation
+    return PointCloud(cloud.points.reshape(M, 3)[idx], None if cloud.colors is None else cloud.colors.reshape(M, 3)[idx],
+                      cloud.conf_threshold, cloud.scene_scale, cloud.transform, cloud.extrinsic,
+                      idx if cloud.indices is None else cloud.indices[idx], None if cloud.conf is None else cloud.conf[idx])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # Voxel-grid decimation and the PLY / GLB writers
 # ---------------------------------------------------------------------------------------------------------------------------------
 
