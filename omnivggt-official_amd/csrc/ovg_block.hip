@@ -7,15 +7,25 @@
 
 namespace {
 
-int check_block(const ovg_block_params* p) {
+// with_extra: the entry runs the attention step, so extra[0 .. nseg_extra) must be filled in (the prologue runs before the caller has them)
+int check_block(const ovg_block_params* p, bool with_extra) {
   if (!p || !p->x_in || !p->x_out || !p->ws_xn || !p->ws_q || !p->ws_k || !p->ws_vt || !p->ws_attn || !p->ws_hid) return OVG_E_ARG;
   if (p->M <= 0 || p->seq <= 0 || p->M % p->seq || p->BH != (p->M / p->seq) * OVG_H) return OVG_E_ARG;
+  // what ovg_block_workspace_bytes refuses, refused here: the inner entries check the same, but ovg_qkv only after LN1 has been launched
+  if (p->nq_pad < p->seq || p->nk_pad < p->seq || p->nk_pad % OVG_KV_TILE) return OVG_E_ARG;
+  if (p->dtype != OVG_BF16 && p->dtype != OVG_F16 && p->dtype != OVG_F32 && p->dtype != OVG_F16X2) return OVG_E_DTYPE;
   if (p->nseg_extra < 0 || p->nseg_extra >= OVG_MAX_SEG) return OVG_E_ARG;
   if (p->local_seg_index < 0 || p->local_seg_index > p->nseg_extra) return OVG_E_ARG;
   if (p->dtype == OVG_F16X2) {      // split-f16: every 16-bit tensor has its lo plane
     if (!p->ws_xn_lo || !p->ws_q_lo || !p->ws_k_lo || !p->ws_vt_lo || !p->ws_attn_lo || !p->ws_hid_lo) return OVG_E_ARG;
     if (!p->w.qkv_w_lo || !p->w.proj_w_lo || !p->w.fc1_w_lo || !p->w.fc2_w_lo) return OVG_E_ARG;
   }
+  if (with_extra && !p->skip_attention)      // ovg_flash_attn's segment checks, before the launches that precede it in ovg_block_forward
+    for (int i = 0; i < p->nseg_extra; ++i) {
+      const ovg_kv_segment& s = p->extra[i];
+      if (!s.k || !s.vt || s.nk <= 0 || s.nk_pad < s.nk || s.nk_pad % OVG_KV_TILE) return OVG_E_ARG;
+      if (p->dtype == OVG_F16X2 && (!s.k_lo || !s.vt_lo)) return OVG_E_ARG;
+    }
   return OVG_OK;
 }
 
@@ -118,15 +128,15 @@ extern "C" int ovg_block_workspace_bytes(const ovg_block_params* p, ovg_block_wo
 }
 
 extern "C" int ovg_block_attn_prologue(const ovg_block_params* p, void* stream) {
-  int rc = check_block(p);
+  int rc = check_block(p, false);
   return rc ? rc : run_prologue(p, stream, p->qkv_part);
 }
 extern "C" int ovg_block_attn_epilogue(const ovg_block_params* p, void* stream) {
-  int rc = check_block(p);
+  int rc = check_block(p, true);
   return rc ? rc : run_epilogue(p, stream);
 }
 extern "C" int ovg_block_forward(const ovg_block_params* p, void* stream) {
-  int rc = check_block(p);
+  int rc = check_block(p, true);
   if (rc) return rc;
   rc = run_prologue(p, stream, 0);
   return rc ? rc : run_epilogue(p, stream);

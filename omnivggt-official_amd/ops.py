@@ -265,15 +265,31 @@ def pack_weights(src, dtype, k_pad=None, out=None):
     return out
 
 
-def block_workspace_bytes(M, seq, dtype):
-    """dict of scratch bytes an ovg_block_forward call with these shapes needs (host-only query)."""
+def block_workspace_bytes(M, seq, dtype, nq_pad=None, nk_pad=None, BH=None):
+    """dict of scratch bytes an ovg_block_forward call with these shapes needs (host-only query; split-f16 mode: of ONE plane of
+    each tensor). nq_pad / nk_pad: rows of the q / k buffers (default: seq padded to 64); BH: default (M // seq) * 16."""
     p = L.BlockParams()
-    p.M, p.seq, p.BH = M, seq, (M // seq) * H
-    p.nq_pad = p.nk_pad = pad_to(seq, KV_TILE)
-    p.dtype = L.dtype_code(dtype)
+    p.M, p.seq, p.BH = M, seq, ((M // seq) * H if BH is None else BH)
+    p.nq_pad = pad_to(seq, KV_TILE) if nq_pad is None else nq_pad
+    p.nk_pad = pad_to(seq, KV_TILE) if nk_pad is None else nk_pad
+    p.dtype = dtype if isinstance(dtype, int) else L.dtype_code(dtype)
     ws = L.BlockWorkspace()
     L.check(L.load().ovg_block_workspace_bytes(L.C.byref(p), L.C.byref(ws)), "ovg_block_workspace_bytes")
     return {f: getattr(ws, f) for f, _ in L.BlockWorkspace._fields_}
+
+
+def block_extra_segments(p, segments, local_seg_index=0):
+    """Fill the remote K / V^T segments of an L.BlockParams: segments = list of (k [BH,nk_pad,64], vt [BH,64,nk_pad], nk) as flash_attn
+    takes them (HiLo pairs in the split-f16 mode); the block's own keys become segment `local_seg_index` of the 1 + len(segments)
+    the attention step runs over, the others keep their order. More than OVG_MAX_SEG - 1 segments cannot be stored: the count is
+    passed on as it is and the entry refuses it."""
+    for i, (k, vt, nk) in enumerate(segments[:L.OVG_MAX_SEG]):
+        (k, k_lo), (vt, vt_lo) = hi_lo(k), hi_lo(vt)
+        _chk_dev(k, vt)
+        p.extra[i].k, p.extra[i].vt, p.extra[i].nk, p.extra[i].nk_pad = L.ptr(k), L.ptr(vt), nk, k.shape[1]
+        p.extra[i].k_lo, p.extra[i].vt_lo = L.ptr(k_lo), L.ptr(vt_lo)
+    p.nseg_extra, p.local_seg_index = len(segments), local_seg_index
+    return p
 
 
 def heads_to_tokens(x, n, dtype, out=None):

@@ -900,8 +900,10 @@ def test_camera_head_every_row_block_edge_guarded():
         for S in (1, 2, 15, 16, 17, 63, 64, 65):
             toks = torch.randn(S, 2048, generator=g) * 1.3
             slot = Slot.get((4 * S, 9), torch.float32, None, tag="cam")
-            ops.camera_head(_strided_input(toks, True), W, dt, out=slot.view.view(4, S, 9))
-            _sync_check(slot.check)
+            # the workspace: exactly the queried byte count, inside a guard band of its own
+            wsb = Slot.get((1, ops.camera_head_workspace_bytes(S, dt)), torch.uint8, None, spare_rows=0, tag="camws")
+            ops.camera_head(_strided_input(toks, True), W, dt, ws=wsb.view.view(-1), out=slot.view.view(4, S, 9))
+            _sync_check(slot.check, wsb.check)
             with torch.no_grad():
                 twin = emul.camera_head(toks, Wc, dt)
             # global gate only: the reference is the rounding twin (float32, 16-bit activation buffers rounded where the kernel stores them)
