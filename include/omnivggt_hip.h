@@ -194,12 +194,32 @@ int ovg_qkv(const ovg_qkv_params*, void* stream);
 typedef struct { const void* k; const void* vt; int64_t nk; int64_t nk_pad;
                  const void* k_lo; const void* vt_lo;   /* OVG_F16X2: lo planes of k / vt (same shapes) */
 } ovg_kv_segment;
+/* ovg_attn_params.variant (the numbers are the ones of the A/B logs under profiles/). 0 is what the model runs; the others are for
+ * benchmarks, the A/B tools and the tests. */
+#define OVG_ATTN_AUTO 0               /* the launch plan chooses: bf16 -> speculative kernel, q tile (128 / 256 / 512 rows), split and tail by shape;
+                                       * f16 -> lazy-rescale kernel (256-row tiles from 4096 rows on, else 128); f32 / split-f16: one kernel each */
+#define OVG_ATTN_BASELINE 1           /* baseline kernel, every dtype (the f32 parity path, the in-process reference of the tests); never splits */
+#define OVG_ATTN_SPEC256 50           /* speculative-softmax kernel, 256-row q tiles (4 waves, 3-slot ring): the bf16 default for short launches */
+#define OVG_ATTN_LAZY256 52           /* lazy-rescale kernel, 256-row q tiles: the f16 default from 4096 rows on */
+#define OVG_ATTN_FORCED256 53         /* the 256-row speculative kernel with its fallback forced (tests) */
+#define OVG_ATTN_SPEC128 54           /* speculative kernel, 128-row q tiles: bf16 launches the smaller tile pads or quantises better */
+#define OVG_ATTN_LAZY128 55           /* lazy-rescale kernel, 128-row q tiles: the f16 default below 4096 rows */
+#define OVG_ATTN_SPEC512 57           /* speculative kernel, 512-row q tiles (8 waves, 5-slot ring): the bf16 default from 2.5 rounds of them on */
+/* plan knobs of the A/B tools and the tests: a kernel + one plan rule allowed outside the default plan */
+#define OVG_ATTN_PLAN_ROWTAIL512 71   /* SPEC512 with the rule of its 128-row tail */
+#define OVG_ATTN_PLAN_ROWTAIL256 72   /* SPEC256 with a 128-row tail from one full round on (the default wants exactly one) */
+#define OVG_ATTN_PLAN_KEYTAIL256 73   /* SPEC256 with a key-split tail whenever a last round is left; kv_splits s > 1 = exactly s key ranges */
+#define OVG_ATTN_PLAN_KEYTAIL512 74   /* SPEC512 with its key-split tail rule alone; kv_splits s > 1 = exactly s key ranges */
+#define OVG_ATTN_F32X_FAST_PV 92      /* OVG_F16X2 only (opt-in): the PV contraction without its P_lo x V_hi product (+16 %, up to 1.0e-4 on single rows) */
+/* Retired (the A/B history of rounds 1-4; OVG_E_UNSUPPORTED from ovg_flash_attn and ovg_attn_plan): 2, 6, 8, 18, 19, 21, 25, 31, 32, 33, 51, 56,
+ * 58, 59. Any other number is OVG_E_ARG from both. All of this for the 16-bit dtypes: OVG_F32 runs the baseline kernel and OVG_F16X2 its one
+ * kernel (92 aside) whatever the number. */
 typedef struct {
   const void* q; int64_t nq; int64_t nq_pad;
   ovg_kv_segment seg[OVG_MAX_SEG]; int nseg;
   void* out; int64_t ldo;
   int64_t BH; int dtype;
-  int variant;   /* 0 = default; >0 selects tuning variants */
+  int variant;   /* OVG_ATTN_* above; 0 = OVG_ATTN_AUTO */
   /* head-parallel (all-to-all) sharding, both 0 otherwise:
    *   kv_heads > 0: K / V^T segments hold kv_heads heads; batch entry bh reads head bh % kv_heads (the BH entries
    *                 are (source rank, head) pairs of queries that share this rank's heads);

@@ -107,15 +107,11 @@ class Workspace:
         self.device, self._split = device, {}
 
     def split_ws(self, variant=0, kv_splits=0, cus=0):
-        """(ws_part, ws_lse) for this shape's self-attention launch if ovg_attn_plan -- asked with the SAME variant and the same
-        forced / automatic split factor the launch will carry -- cuts it along the keys (launches that would leave CUs idle:
-        8-view global attention = 688 workgroups on 512 slots), else (None, None). The buffers' sizes travel with the pointers
-        (ovg_attn_params.ws_part_bytes / ws_lse_bytes), so a plan / launch mismatch is an error code, not an overrun."""
+        """(ws_part, ws_lse) for this shape's self-attention launch with these knobs if the launch plan cuts it along the keys (launches
+        that would leave CUs idle: 8-view global attention = 688 workgroups on 512 slots), else (None, None)."""
         key = (variant, kv_splits, cus)
         if key not in self._split:
-            plan = (ops.attn_plan(self.BH, self.seq, [self.seq], self.dtype, variant, kv_splits, nq_pad=self.q.shape[1], cus=cus)
-                    if (self.dtype in (torch.bfloat16, torch.float16) and kv_splits != 1) else {"splits": 1})
-            self._split[key] = ops.alloc_split_ws(plan, self.device)
+            self._split[key] = ops.attn_split_ws(self.BH, self.seq, [self.seq], self.dtype, ops.AttnKnobs(*key, None), self.q.shape[1], self.device)
         return self._split[key]
 
     def share_from(self, other):
@@ -182,15 +178,12 @@ class BlockRunner:
             hi, lo = ops.hi_lo(getattr(ws, name))
             setattr(p, "ws_" + name, L.ptr(hi))
             setattr(p, "ws_%s_lo" % name, L.ptr(lo))
-        p.attn_variant = int(getattr(self.knobs, "attn_variant", 0))
-        if L.is_split(self.dtype) and p.attn_variant == 0 and getattr(self.knobs, "f32x_fast_pv", False):
-            p.attn_variant = L.ATTN_F32X_FAST_PV                 # split-f16 mode without the P_lo x V_hi product of the PV contraction (opt-in)
+        knobs = ops.attn_knobs(self.knobs, self.dtype)
+        p.attn_variant, p.attn_kv_splits, p.attn_cus = knobs.variant, knobs.kv_splits, knobs.cus
+        p.attn_fallback_count = L.ptr(knobs.fallback_counter)
         p.gemm_tile = int(getattr(self.knobs, "gemm_tile", 0))
-        p.attn_kv_splits = int(getattr(self.knobs, "attn_kv_splits", 0))
-        p.attn_fallback_count = L.ptr(getattr(self.knobs, "fallback_counter", None))
-        p.attn_cus = int(getattr(self.knobs, "attn_cus", 0))
-        if p.attn_kv_splits != 1 and hasattr(ws, "split_ws"):
-            part, lse = ws.split_ws(p.attn_variant, p.attn_kv_splits, p.attn_cus)
+        if hasattr(ws, "split_ws"):
+            part, lse = ws.split_ws(knobs.variant, knobs.kv_splits, knobs.cus)
             p.ws_attn_part, p.ws_attn_lse = L.ptr(part), L.ptr(lse)
             p.ws_attn_part_bytes, p.ws_attn_lse_bytes = ops.nbytes(part), ops.nbytes(lse)
         return p

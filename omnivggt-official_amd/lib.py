@@ -16,7 +16,12 @@ OVG_MAX_SEG = 8
 KV_TILE = 64
 ABI_VERSION = 13
 TILE_AUTO, TILE_128, TILE_256 = 0, 1, 2
+# ovg_attn_params.variant (OVG_ATTN_* of include/omnivggt_hip.h): 0 = the launch plan chooses; the kernels by name; the plan knobs of the A/B tools
+ATTN_AUTO, ATTN_BASELINE = 0, 1
+ATTN_SPEC256, ATTN_LAZY256, ATTN_FORCED256, ATTN_SPEC128, ATTN_LAZY128, ATTN_SPEC512 = 50, 52, 53, 54, 55, 57
+ATTN_PLAN_ROWTAIL512, ATTN_PLAN_ROWTAIL256, ATTN_PLAN_KEYTAIL256, ATTN_PLAN_KEYTAIL512 = 71, 72, 73, 74
 ATTN_F32X_FAST_PV = 92                                         # ovg_attn_params.variant in the split-f16 mode (opt-in): PV without P_lo x V_hi, +16 % at 3e-5 .. 1e-4 instead of 1e-5 .. 5e-5
+ATTN_RETIRED = (2, 6, 8, 18, 19, 21, 25, 31, 32, 33, 51, 56, 58, 59)     # the A/B history of rounds 1-4: always OVG_E_UNSUPPORTED
 TILE_R02_EPILOGUE, TILE_128X, TILE_256X = 16, 17, 18      # retired selectors (r02 epilogue forms): always OVG_E_UNSUPPORTED
 
 ERRORS = {0: "OVG_OK", -1: "OVG_E_ARG", -2: "OVG_E_DTYPE", -3: "OVG_E_LAUNCH", -4: "OVG_E_UNSUPPORTED"}

@@ -3,6 +3,8 @@
 They only marshal device pointers, shapes and the current HIP stream into the parameter
 structs of include/omnivggt_hip.h; every byte of compute happens in libomnivggt_hip.so.
 """
+import collections
+
 import torch
 
 from . import lib as L
@@ -188,6 +190,30 @@ def alloc_split_ws(plan, device):
         return None, None
     return (torch.empty(plan["part_bytes"], device=device, dtype=torch.uint8),
             torch.empty(plan["lse_bytes"] // 4, device=device, dtype=torch.float32))
+
+
+AttnKnobs = collections.namedtuple("AttnKnobs", "variant kv_splits cus fallback_counter")
+
+
+def attn_knobs(owner, dtype, cus=None):
+    """The attention knobs of `owner` (the aggregator, or any object with some of .attn_variant / .f32x_fast_pv / .attn_kv_splits / .attn_cus /
+    .fallback_counter; None = library defaults), read at call time, as the launch will carry them. cus: the caller's own CU budget instead of
+    owner.attn_cus (the sharded run plans against what RCCL leaves)."""
+    variant = int(getattr(owner, "attn_variant", 0))
+    if L.is_split(dtype) and variant == L.ATTN_AUTO and getattr(owner, "f32x_fast_pv", False):
+        variant = L.ATTN_F32X_FAST_PV                 # split-f16 mode without the P_lo x V_hi product of the PV contraction (opt-in)
+    return AttnKnobs(variant, int(getattr(owner, "attn_kv_splits", 0)), int(getattr(owner, "attn_cus", 0) if cus is None else cus),
+                     getattr(owner, "fallback_counter", None))
+
+
+def attn_split_ws(BH, nq, nks, dtype, knobs, nq_pad, device, alloc=alloc_split_ws):
+    """(ws_part, ws_lse) for the attention launch of this shape under `knobs` (attn_knobs) if ovg_attn_plan -- asked with the SAME variant,
+    split factor and CU budget the launch will carry -- cuts it along the keys, else (None, None): only the 16-bit kernels split, and
+    kv_splits == 1 forbids it. The buffers' sizes travel with the pointers (ovg_attn_params.ws_part_bytes / ws_lse_bytes), so a plan / launch
+    mismatch is an error code, not an overrun. alloc(plan, device): where the buffers come from (tests: guarded ones). Callers cache."""
+    if dtype not in (torch.bfloat16, torch.float16) or knobs.kv_splits == 1:
+        return None, None
+    return alloc(attn_plan(BH, nq, nks, dtype, knobs.variant, knobs.kv_splits, nq_pad=nq_pad, cus=knobs.cus), device)
 
 
 def flash_attn(q, segments, nq, dtype, out=None, variant=0, kv_heads=0, head_major=False, lse=None, kv_splits=0, split_ws=None, fallback_count=None, cus=0):

@@ -195,21 +195,16 @@ class HipExecutor:
     def _attention(self, q, segs, n, out, lse=None, kv_heads=0, head_major=False):
         """One flash-attention launch, timed with a HIP event pair when bench.py asked for it."""
         nk = sum(s[2] for s in segs)
-        dt, variant = self.agg.compute_dtype, self.agg.attn_variant
-        if ops.L.is_split(dt) and variant == 0 and getattr(self.agg, "f32x_fast_pv", False):
-            variant = ops.L.ATTN_F32X_FAST_PV
-        splits = getattr(self.agg, "attn_kv_splits", 0)
-        cus = self.cus                                               # CUs left to the attention plans beside RCCL's channels (ViewSharding sets it)
-        split_ws = None
-        if splits != 1 and dt in (torch.bfloat16, torch.float16):     # per-rank launches are the ones that quantise badly (688 workgroups on 512 slots)
-            key = ("split", q.shape[0], n, q.shape[1], tuple(s[2] for s in segs), variant, splits, cus)
-            split_ws = self._cached(key, lambda: ops.alloc_split_ws(
-                ops.attn_plan(q.shape[0], n, [s[2] for s in segs], dt, variant, splits, nq_pad=q.shape[1], cus=cus), self.device))
+        dt = self.agg.compute_dtype
+        knobs = ops.attn_knobs(self.agg, dt, cus=self.cus)           # cus: CUs left to the attention plans beside RCCL's channels (ViewSharding sets it)
+        nks = tuple(s[2] for s in segs)                              # per-rank launches are the ones that quantise badly (688 workgroups on 512 slots)
+        split_ws = self._cached(("split", q.shape[0], n, q.shape[1], nks, dt) + knobs[:3],
+                                lambda: ops.attn_split_ws(q.shape[0], n, list(nks), dt, knobs, q.shape[1], self.device))
         ev = self.agg.next_attention_events(4.0 * q.shape[0] * n * nk * 64)
         if ev is not None:
             ev[0].record()
-        ops.flash_attn(q, segs, n, dt, out=out, variant=variant, kv_heads=kv_heads, head_major=head_major, lse=lse,
-                       kv_splits=splits, split_ws=split_ws, fallback_count=getattr(self.agg, "fallback_counter", None), cus=cus)
+        ops.flash_attn(q, segs, n, dt, out=out, variant=knobs.variant, kv_heads=kv_heads, head_major=head_major, lse=lse,
+                       kv_splits=knobs.kv_splits, split_ws=split_ws, fallback_count=knobs.fallback_counter, cus=knobs.cus)
         if ev is not None:
             ev[1].record()
         return out

@@ -149,18 +149,19 @@ class WS:
     def split_ws(self, variant=0, kv_splits=0, cus=0):
         key = (variant, kv_splits, cus, tuple(self.nks))
         if key not in self._split:
-            plan = (ops.attn_plan(self.BH, self.seq, self.nks, self.dtype, variant, kv_splits, nq_pad=self.npad, cus=cus)
-                    if (self.mode in ("bf16", "f16") and kv_splits != 1) else {"splits": 1})
-            if plan["splits"] > 1:
-                a, ca = kg.guarded((1, plan["part_bytes"]), torch.uint8, DEV)
-                b, cb = kg.guarded((1, plan["lse_bytes"] // 4), torch.float32, DEV)
-                self.checks += [ca, cb]
-                self._split[key] = (a.view(-1), b.view(-1))
-                print("split-KV %s BH=%d nq=%d keys=%s: plan runs %d splits in %d + %d bytes" % (
-                    self.mode, self.BH, self.seq, self.nks, plan["splits"], plan["part_bytes"], plan["lse_bytes"]), flush=True)
-            else:
-                self._split[key] = (None, None)
+            self._split[key] = ops.attn_split_ws(self.BH, self.seq, self.nks, self.dtype, ops.AttnKnobs(variant, kv_splits, cus, None), self.npad, DEV,
+                                                 alloc=self._guarded_split)
         return self._split[key]
+
+    def _guarded_split(self, plan, device):
+        if plan["splits"] <= 1:
+            return None, None
+        a, ca = kg.guarded((1, plan["part_bytes"]), torch.uint8, device)
+        b, cb = kg.guarded((1, plan["lse_bytes"] // 4), torch.float32, device)
+        self.checks += [ca, cb]
+        print("split-KV %s BH=%d nq=%d keys=%s: plan runs %d splits in %d + %d bytes" % (
+            self.mode, self.BH, self.seq, self.nks, plan["splits"], plan["part_bytes"], plan["lse_bytes"]), flush=True)
+        return a.view(-1), b.view(-1)
 
     def check(self, what):
         for i, c in enumerate(self.checks):
@@ -202,9 +203,8 @@ def _parts(mode, ws, x_in, x_out, tpv, gw, knobs, inject=None, per=0, segments=N
             tokens_per_view=tpv, grid_w=gw, tile=knobs.gemm_tile)
     segs = list(segments or [])
     segs.insert(local, (ws.k, ws.vt, seq))
-    ops.flash_attn(ws.q, segs, seq, dt, out=ws.attn, variant=knobs.attn_variant, kv_splits=knobs.attn_kv_splits,
-                   split_ws=ws.split_ws(knobs.attn_variant, knobs.attn_kv_splits, knobs.attn_cus) if knobs.attn_kv_splits != 1 else None,
-                   cus=knobs.attn_cus)
+    ak = ops.attn_knobs(knobs, dt)
+    ops.flash_attn(ws.q, segs, seq, dt, out=ws.attn, variant=ak.variant, kv_splits=ak.kv_splits, split_ws=ws.split_ws(ak.variant, ak.kv_splits, ak.cus), cus=ak.cus)
     x_mid = torch.empty(ws.M, 1024, device=DEV)
     ops.linear(ws.attn, t["attn.proj.weight"], t["attn.proj.bias"], dt, epilogue=L.EPI_RES, out=x_mid, res=x_in, gamma=t["ls1.gamma"],
                tile=knobs.gemm_tile)

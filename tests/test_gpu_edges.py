@@ -701,6 +701,69 @@ def test_split_kv_forced_on_short_queries_stays_inside_its_workspace(mode):
                                   extra=kg.attn_p_floor(vv, mode) + kg.f16_subnormal_floor(mode), quiet=True)
 
 
+# The three forms of a plan that writes partials, each at the smallest shape that reaches it (16 entries; confirmed with ops.attn_plan on the
+# CPU): a tail rule needs nq >= 4096 and 16 (256-row) / 32 (512-row) key tiles per range, so the chip is shrunk with `cus` and the tail forced
+# with the plan knobs (kv_splits = key ranges).  name: (nq, variant, kv_splits, cus, the plan)
+SPLIT_FORMS = {
+    # 6 key tiles in 3 ranges, partials for all 384 padded rows of every entry
+    "whole_launch": (321, L.ATTN_SPEC256, 3, 0,
+                     {"splits": 3, "q_tile": 256, "main_rows": 321, "tail_q_tile": 0, "part_bytes": 3 * 16 * 384 * 64 * 4, "lse_bytes": 3 * 16 * 384 * 4}),
+    # 272 units of 256 rows on 48 slots: 5 full rounds = 240 units = 3840 rows unsplit, the other 300 rows (padded to 512) in 2 key ranges
+    "key_tail_256": (4140, L.ATTN_PLAN_KEYTAIL256, 2, 24,
+                     {"splits": 2, "q_tile": 256, "main_rows": 3840, "tail_q_tile": 256, "part_bytes": 2 * 16 * 512 * 64 * 4, "lse_bytes": 2 * 16 * 512 * 4}),
+    # 160 units of 512 rows on 12 slots: 13 full rounds = 156 units -> 9 tiles = 4608 rows per entry unsplit, the other 88 rows (padded to 512) in 2 ranges
+    "key_tail_512": (4696, L.ATTN_PLAN_KEYTAIL512, 2, 12,
+                     {"splits": 2, "q_tile": 512, "main_rows": 4608, "tail_q_tile": 512, "part_bytes": 2 * 16 * 512 * 64 * 4, "lse_bytes": 2 * 16 * 512 * 4}),
+}
+
+
+@pytest.mark.parametrize("form", list(SPLIT_FORMS))
+@pytest.mark.parametrize("mode", ["bf16", "f16"])
+def test_split_workspace_of_every_plan_form_is_exactly_what_the_plan_reports(mode, form):
+    """One sizing function serves ovg_attn_plan's answer, ovg_flash_attn's refusal and the kernels' partial layout: a launch with workspaces of
+    exactly the reported byte counts stays inside them and equals the baseline kernel (output and log-sum-exp, gpu_selftest.TOL); four bytes
+    less of either buffer is OVG_E_ARG before anything is written."""
+    nq, variant, splits, cus, want = SPLIT_FORMS[form]
+    dt = MODES[mode]
+    qd, segs, _, _, _ = _attn_inputs(mode, 16, 16, nq, [nq], torch.Generator().manual_seed(400 + len(form)), True)
+    nq_pad = qd.shape[1]
+    plan = ops.attn_plan(16, nq, [nq], dt, variant, splits, nq_pad=nq_pad, cus=cus)
+    assert plan == want, (form, plan)
+
+    def run(variant, splits, ws, cus):
+        out, oc = _out_slot(mode, (nq, 1024), False, 1032, tag="attn_form")
+        ls = Slot.get((16, nq_pad), torch.float32, None, tag="lse_form")
+        out.fill_(-7.25)
+        ls.view.fill_(-7.25)
+        return out, ls, oc + [ls.check], lambda: ops.flash_attn(qd, segs, nq, dt, out=out, variant=variant, lse=ls.view, kv_splits=splits, split_ws=ws, cus=cus)
+
+    out, ls, checks, call = run(L.ATTN_BASELINE, 1, None, 0)
+    call()
+    _sync_check(*checks)
+    ref_o, ref_l = _val(out).clone(), ls.view[:, :nq].double().cpu()
+
+    a = Slot.get((1, plan["part_bytes"]), torch.uint8, None, spare_rows=0, tag="wsp")
+    b = Slot.get((1, plan["lse_bytes"] // 4), torch.float32, None, spare_rows=0, tag="wsl")
+    part, lse = a.view.view(-1), b.view.view(-1)
+    out, ls, checks, call = run(variant, splits, (part, lse), cus)
+    call()
+    _sync_check(a.check, b.check, *checks)
+    assert bool((ls.view[:, nq:] == -7.25).all()), "%s %s: the lse tail nq..nq_pad was written" % (form, mode)
+    _global("attn_form_%s_%s" % (form, mode), _val(out), ref_o, st.TOL[mode])
+    _global("attn_form_%s_%s.lse" % (form, mode), ls.view[:, :nq].double().cpu(), ref_l, st.TOL[mode])
+    _global_only(2)
+
+    for what, ws in (("part", (part[:-4], lse)), ("lse", (part, lse[:-1]))):        # 4 bytes short of either buffer
+        out, ls, checks, call = run(variant, splits, ws, cus)
+        with pytest.raises(L.OvgError, match="OVG_E_ARG"):
+            call()
+        kg.STATS["refusals"] += 1
+        print("[REFUSED] attn %s %s: %s workspace 4 bytes short" % (form, mode, what), flush=True)
+        _sync_check(a.check, b.check, *checks)
+        assert bool((_val(out) == -7.25).all()) and bool((ls.view == -7.25).all()), "%s %s: a refused launch wrote its output" % (form, mode)
+    Slot.cache.clear()
+
+
 @pytest.mark.parametrize("mode", ["bf16", "f16", "f32", "f32x"])
 def test_attn_merge_and_heads_to_tokens_short_rows_strided(mode):
     g = torch.Generator().manual_seed(115)
