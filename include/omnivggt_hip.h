@@ -61,7 +61,8 @@ extern "C" {
  *     + point-cloud rendering (ovg_render_points, ovg_render_workspace_bytes): added the same way, looked up by name
  *     + multi-view depth consistency (ovg_multiview_consistency, ovg_consistency_workspace_bytes): added the same way
  *     + nearest-neighbour search between point clouds (ovg_nearest_neighbours, ovg_nn_workspace_bytes): added the same way
- *     + farthest-point sampling of point clouds (ovg_farthest_point_sample, ovg_fps_workspace_bytes): added the same way */
+ *     + farthest-point sampling of point clouds (ovg_farthest_point_sample, ovg_fps_workspace_bytes): added the same way
+ *     + radius neighbour search on a hash grid (ovg_radius_search, ovg_radius_workspace_bytes): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -778,6 +779,67 @@ typedef struct {
 } ovg_fps_params;
 int64_t ovg_fps_workspace_bytes(int64_t batch, int64_t n, int64_t npoint);
 int ovg_farthest_point_sample(const ovg_fps_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Radius neighbour search through a uniform hash grid (added under ABI 13): for every query point how many reference points lie
+ * within a radius and which one is nearest, at a cost linear in the clouds for a sensible radius. The result is DEFINED without the
+ * grid, as the rule of ovg_nearest_neighbours restricted to d <= radius_sq; tests/radius_twin.py restates it by brute force in
+ * numpy float32 bit for bit.
+ *   query [nq][3] f32, reference [nr][3] f32; query_valid [nq] u8 and reference_valid [nr] u8 are optional (NULL: all valid).
+ *   1. USABLE and d = (dx dx + dy dy) + dz dz are those of ovg_nearest_neighbours: every operation rounded to f32 on its own;
+ *   2. a usable reference j is a CANDIDATE of a usable query i when bits(d) <= bits(radius_sq): inclusive, d == radius_sq counts;
+ *      with OVG_RS_EXCLUDE_SAME_INDEX (nq == nr: a search inside one cloud) j != i as well;
+ *   3. count[i] (int32) = the number of candidates;
+ *   4. index[i] = the j that minimises (bits(d), j) over the candidates (equal distances go to the LOWEST index), sqdist[i] = that d;
+ *   5. an unusable query, or one without a candidate: count 0, index -1, sqdist +inf;
+ *   6. radius_sq must be finite and >= 2^-100 (no step of the covering argument below meets a subnormal). A d that overflows to
+ *      +inf is never a candidate here (it is one in the unbounded search).
+ * The grid never changes a byte of this. With REACH = the f32 just above sqrt((double)radius_sq) (1 + 2^-20): d <= radius_sq gives
+ * fl(dx^2) <= radius_sq, so |q.x - r.x| < REACH in exact arithmetic and, r.x being a float and rounding monotone,
+ * fl(q.x - REACH) <= r.x <= fl(q.x + REACH); likewise y, z. The cell of a coordinate,
+ *   C(x) = clamp(floor(fl(fl(x - origin) / cell)), -2^20, 2^20 - 1)   (clamped as a float, then converted),
+ * is a chain of monotone maps, so every candidate of q lies in the box of cells [C(fl(q - REACH)), C(fl(q + REACH))] per axis, and
+ * scanning exactly that box with the rule above IS the exhaustive result: for every cell edge, every origin (origin: device f32[3],
+ * NULL = zeros; a non-finite component counts as 0 and raises OVG_RS_BAD_ORIGIN), far coordinates included (they share the clamped
+ * boundary cells). cell >= REACH is required only to keep the box to a few cells per axis. The origin is NOT taken from the cloud:
+ * one outlier at -9e20 would put everything else into one cell.
+ * Two stages (flags OR-ed in `stage`), like ovg_voxel_downsample:
+ *   OVG_RS_BUILD  clear the table of max(OVG_RS_MIN_SLOTS, 2 nr) slots; every usable reference claims its cell's slot (open
+ *     addressing, linear probing, a 64-bit compare-and-swap on the packed 63-bit cell key) and counts itself; an exclusive scan of
+ *     the slot counts; a scatter of 16-byte records {x, y, z, bits(j)} into cell order through a per-cell cursor (the order INSIDE a
+ *     cell is left open: count, minimum and integer sums do not depend on it); a cost pass in which every usable query sums the
+ *     counts of the cells of its box. out_stats int64[4] (device) = { flags (OVG_RS_BAD_ORIGIN), occupied cells, the most points
+ *     in one cell, candidate pairs = the cost pass's total: the number of distances SEARCH will evaluate }.
+ *   OVG_RS_SEARCH  reads what BUILD left in ws (same reference, radius_sq, cell, origin): one query per thread (workgroups of
+ *     OVG_RS_QUERY_BLOCK) walks its box, probes each cell and runs the rule over the cell's records; count / index / sqdist are
+ *     stored directly. Integer atomics only, no float atomics, no workgroup ever waits for another.
+ *     WORK GUARD: a radius too large for the cloud makes one thread's loop quadratic. SEARCH writes NOTHING to count / index / sqdist
+ *     when the candidate pairs BUILD counted exceed max_pairs (>= 0), or when ws holds no BUILD of this nr; out_stats (optional in
+ *     this stage) then reports OVG_RS_OVER_BUDGET / OVG_RS_NOT_BUILT in its flags. Callers read out_stats between the stages.
+ *   ws: >= ovg_radius_workspace_bytes(nq, nr) bytes, 16-byte aligned: 256 + 16 max(1024, 2 nr) + 16 nr + 4 ceil(slots / 4096),
+ *   each part rounded up to 256; the query returns -1 unless 1 <= nq, nr < 2^31. Nothing is allocated or read back.
+ *   OVG_E_ARG: NULL params / query / reference / ws (out_stats in BUILD; count / index / sqdist in SEARCH), bad nq / nr, radius_sq
+ *   not finite or < 2^-100, cell not finite or < REACH, unknown flags or stage, OVG_RS_EXCLUDE_SAME_INDEX with nq != nr,
+ *   max_pairs < 0 in SEARCH, a pointer that is not 4-byte (out_stats: 8-byte) aligned, a misaligned or undersized workspace.
+ * ------------------------------------------------------------------ */
+enum { OVG_RS_BUILD = 1, OVG_RS_SEARCH = 2 };
+enum { OVG_RS_EXCLUDE_SAME_INDEX = 1 };
+enum { OVG_RS_BAD_ORIGIN = 1, OVG_RS_OVER_BUDGET = 2, OVG_RS_NOT_BUILT = 4 };      /* out_stats[0] */
+enum { OVG_RS_MIN_SLOTS = 1024, OVG_RS_QUERY_BLOCK = 256 };
+typedef struct {
+  const float* query; const float* reference;
+  const uint8_t* query_valid; const uint8_t* reference_valid;
+  const float* origin;
+  int64_t nq; int64_t nr;
+  float radius_sq; float cell;
+  int32_t flags; int32_t stage;
+  int64_t max_pairs;
+  void* ws; int64_t ws_bytes;
+  int64_t* out_stats;
+  int32_t* count; int32_t* index; float* sqdist;
+} ovg_radius_params;
+int64_t ovg_radius_workspace_bytes(int64_t nq, int64_t nr);
+int ovg_radius_search(const ovg_radius_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

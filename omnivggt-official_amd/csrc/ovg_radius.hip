@@ -1,0 +1,381 @@
+// Radius neighbour search through a uniform hash grid (ovg_radius_search): for every query the number of reference points within
+// radius_sq and the nearest of them, by the rule of ovg_nearest_neighbours restricted to d <= radius_sq (include/omnivggt_hip.h).
+// BUILD bins the usable references: an open-addressing table of 16-byte slots {cell key, count, cursor} (the claim is ovg_pointcloud.hip's
+// 64-bit compare-and-swap on the packed cell key), an exclusive scan of the counts, a scatter of 16-byte records {x, y, z, bits(j)}
+// into cell order, and a cost pass that sums the cell counts of every query's box. SEARCH: one query per thread walks its box of
+// cells and runs the exact rule over each cell's records. The box covers every candidate for any cell edge and origin (header), so
+// the grid changes the cost and never a byte. The table is bound by random 64-bit atomics, the search by its gather of records.
+#include <math.h>
+#include "ovg_common.h"
+
+// tests/radius_twin.py restates the rule and the cell function in numpy float32, one rounding per operation: no fused multiply-adds
+// in this unit (build.py compiles it with -ffp-contract=off as well)
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kThreads = OVG_RS_QUERY_BLOCK;
+constexpr int kScanPer = 16;                           // slots per thread of the scan passes
+constexpr int kScanTile = kThreads * kScanPer;         // slots per workgroup of the scan passes
+constexpr uint64_t kEmpty = ~0ull;                     // no cell key has bit 63
+constexpr uint32_t kInfBits = 0x7F800000u;
+constexpr uint64_t kNoneKey = ~0ull;                   // above every (bits(d) << 32) | j of a candidate: bits(d) <= bits(radius_sq) < bits(+inf)
+constexpr float kCellLo = -1048576.0f, kCellHi = 1048575.0f;   // -2^20, 2^20 - 1
+constexpr float kMinRadiusSq = 0x1p-100f;
+
+struct RsHead { uint32_t flags, max_cell; uint64_t occupied, pairs; int64_t nr; };   // nr: 0 after the clear, the cloud's once BUILD is through
+struct RsSlot { uint64_t key; uint32_t count, end; };  // end: the cell's first record after the scan, one past its last after the scatter
+struct RsWs { RsHead* head; RsSlot* table; int64_t nslots; u32x4* rec; uint32_t* tile; int64_t ntiles; };
+
+static_assert(sizeof(RsSlot) == 16 && sizeof(RsHead) <= 256, "workspace layout");
+
+bool rs_shape_ok(int64_t nq, int64_t nr) { return nq > 0 && nr > 0 && nq < (1ll << 31) && nr < (1ll << 31); }
+int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
+int64_t rs_slots(int64_t nr) { return 2 * nr < OVG_RS_MIN_SLOTS ? OVG_RS_MIN_SLOTS : 2 * nr; }   // load factor <= 1/2
+int64_t rs_tiles(int64_t nr) { return (rs_slots(nr) + kScanTile - 1) / kScanTile; }
+int64_t rs_ws_bytes(int64_t nr) { return 256 + round256(rs_slots(nr) * 16) + round256(nr * 16) + round256(rs_tiles(nr) * 4); }
+RsWs rs_ws(const ovg_radius_params* p) {
+  uint8_t* b = static_cast<uint8_t*>(p->ws);
+  const int64_t ns = rs_slots(p->nr);
+  uint8_t* rec = b + 256 + round256(ns * 16);
+  return {reinterpret_cast<RsHead*>(b), reinterpret_cast<RsSlot*>(b + 256), ns, reinterpret_cast<u32x4*>(rec),
+          reinterpret_cast<uint32_t*>(rec + round256(p->nr * 16)), rs_tiles(p->nr)};
+}
+
+// the f32 just above sqrt((double)radius_sq) (1 + 2^-20): the header fixes this formula, tests/radius_twin.py restates it
+float rs_reach(float radius_sq) {
+  const double v = sqrt((double)radius_sq) * (1.0 + 0x1p-20);
+  const float r = (float)v;
+  return (double)r > v ? r : nextafterf(r, INFINITY);
+}
+
+OVG_DEV bool finite1(float f) { return (__float_as_uint(f) & kInfBits) != kInfBits; }
+OVG_DEV bool finite3(float x, float y, float z) { return finite1(x) && finite1(y) && finite1(z); }
+
+OVG_DEV float rs_origin(const float* origin, int k) {
+  const float o = origin ? origin[k] : 0.0f;
+  return finite1(o) ? o : 0.0f;
+}
+
+// C(x) of the header, shifted to [0, 2^21): monotone in x. With a finite origin and cell no NaN arises (x is finite or +-inf)
+OVG_DEV uint32_t rs_cell(float x, float o, float cell) {
+  const float c = floorf(__fdiv_rn(__fsub_rn(x, o), cell));
+  const float k = c >= kCellLo ? (c <= kCellHi ? c : kCellHi) : kCellLo;
+  return (uint32_t)((int32_t)k + (1 << 20));
+}
+
+OVG_DEV uint64_t rs_key(uint32_t cx, uint32_t cy, uint32_t cz) { return ((uint64_t)cx << 42) | ((uint64_t)cy << 21) | (uint64_t)cz; }
+
+OVG_DEV uint64_t rs_mix(uint64_t h) {                  // murmur3's 64-bit finaliser
+  h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
+  return h;
+}
+
+OVG_DEV int64_t rs_home(const RsWs& ws, uint64_t key) { return (int64_t)__umul64hi(rs_mix(key), (uint64_t)ws.nslots); }
+
+// the slot of a cell in a table that no launch is writing keys to: -1 when the cell holds no reference
+OVG_DEV int64_t rs_find(const RsWs& ws, uint64_t key, uint32_t& count, uint32_t& end) {
+  int64_t s = rs_home(ws, key);
+  for (int64_t t = 0; t < ws.nslots; ++t) {            // at most nr of the >= 2 nr slots are claimed: the walk ends at a free one
+    const u32x4 e = reinterpret_cast<const u32x4*>(ws.table)[s];
+    const uint64_t k = ((uint64_t)e[1] << 32) | e[0];
+    if (k == key) { count = e[2]; end = e[3]; return s; }
+    if (k == kEmpty) return -1;
+    s = s + 1 == ws.nslots ? 0 : s + 1;
+  }
+  return -1;
+}
+
+struct RsBox { uint32_t lo[3], hi[3]; };
+
+// the cells [C(fl(q - reach)), C(fl(q + reach))] per axis: every candidate of q lies in one of them (header)
+OVG_DEV RsBox rs_box(const float (&q)[3], const float* origin, float cell, float reach) {
+  RsBox b;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float o = rs_origin(origin, k);
+    b.lo[k] = rs_cell(__fsub_rn(q[k], reach), o, cell);
+    b.hi[k] = rs_cell(__fadd_rn(q[k], reach), o, cell);
+  }
+  return b;
+}
+
+// point i of a cloud; false when it is unusable
+OVG_DEV bool rs_point(const float* pts, const uint8_t* valid, uint32_t i, float (&v)[3]) {
+  const float* p = pts + 3 * (int64_t)i;
+  v[0] = p[0], v[1] = p[1], v[2] = p[2];
+  return finite3(v[0], v[1], v[2]) && (!valid || valid[i] != 0);
+}
+
+OVG_DEV uint32_t wave_incl_scan_u32(uint32_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t o = __shfl_up(v, d, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(kThreads) void rs_clear(RsWs ws) {
+  const int64_t t0 = (int64_t)blockIdx.x * kThreads + threadIdx.x, step = (int64_t)gridDim.x * kThreads;
+  u32x4* tab = reinterpret_cast<u32x4*>(ws.table);
+  const u32x4 empty = {0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u};
+  for (int64_t i = t0; i < ws.nslots; i += step) tab[i] = empty;
+  if (t0 == 0) *ws.head = {0u, 0u, 0ull, 0ull, 0ll};
+}
+
+// every usable reference claims the slot of its cell and counts itself
+__global__ __launch_bounds__(kThreads) void rs_count(ovg_radius_params p, RsWs ws) {
+  const uint32_t j = blockIdx.x * kThreads + threadIdx.x;                  // nr < 2^31: no wrap in unsigned arithmetic
+  float r[3];
+  if (j >= (uint32_t)p.nr || !rs_point(p.reference, p.reference_valid, j, r)) return;
+  const uint64_t key = rs_key(rs_cell(r[0], rs_origin(p.origin, 0), p.cell), rs_cell(r[1], rs_origin(p.origin, 1), p.cell),
+                              rs_cell(r[2], rs_origin(p.origin, 2), p.cell));
+  int64_t s = rs_home(ws, key);
+  for (int64_t t = 0; t < ws.nslots; ++t) {
+    RsSlot* slot = ws.table + s;
+    uint64_t k = __hip_atomic_load(&slot->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == kEmpty) {
+      uint64_t expect = kEmpty;
+      k = __hip_atomic_compare_exchange_strong(&slot->key, &expect, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? key : expect;
+    }
+    if (k == key) {
+      __hip_atomic_fetch_add(&slot->count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+    s = s + 1 == ws.nslots ? 0 : s + 1;
+  }
+}
+
+// the exclusive scan of the slot counts in three launches: sums per tile of kScanTile slots (and the table's statistics), one
+// workgroup over the tile sums, the slots of every tile. Inside a tile the order is (thread, k) with slot = base + k * kThreads +
+// thread: any fixed order serves, the cells only have to tile [0, usable references) without gaps
+__global__ __launch_bounds__(kThreads) void rs_tile_sums(RsWs ws) {
+  __shared__ uint32_t red[3][kThreads / 64];
+  const int64_t base = (int64_t)blockIdx.x * kScanTile;
+  uint32_t sum = 0, occ = 0, mx = 0;
+#pragma unroll 4
+  for (int k = 0; k < kScanPer; ++k) {
+    const int64_t s = base + (int64_t)k * kThreads + threadIdx.x;
+    const uint32_t c = s < ws.nslots ? ws.table[s].count : 0u;
+    sum += c, occ += c != 0, mx = max(mx, c);
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    sum += __shfl_down(sum, d, 64), occ += __shfl_down(occ, d, 64);
+    mx = max(mx, (uint32_t)__shfl_down(mx, d, 64));
+  }
+  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = sum, red[1][threadIdx.x >> 6] = occ, red[2][threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kThreads / 64; ++w) sum += red[0][w], occ += red[1][w], mx = max(mx, red[2][w]);
+    ws.tile[blockIdx.x] = sum;
+    if (occ) {                                         // integer sums and maxima: the same whatever the arrival order
+      __hip_atomic_fetch_add(&ws.head->occupied, (uint64_t)occ, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_max(&ws.head->max_cell, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// exclusive scan of the tile sums in place, one workgroup of 1024 threads (the total is below 2^31)
+__global__ __launch_bounds__(1024) void rs_scan_tiles(RsWs ws) {
+  __shared__ uint32_t wsum[16];
+  __shared__ uint32_t carry;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int64_t b0 = 0; b0 < ws.ntiles; b0 += 1024) {
+    const int64_t b = b0 + threadIdx.x;
+    const uint32_t v = b < ws.ntiles ? ws.tile[b] : 0u;
+    const uint32_t incl = wave_incl_scan_u32(v);
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t excl = carry + incl - v;
+    for (int w = 0; w < wave; ++w) excl += wsum[w];
+    if (b < ws.ntiles) ws.tile[b] = excl;
+    __syncthreads();
+    if (threadIdx.x == 1023) carry = excl + v;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void rs_starts(RsWs ws) {
+  __shared__ uint32_t wsum[kThreads / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * kScanTile;
+  uint32_t c[kScanPer], sum = 0;
+#pragma unroll
+  for (int k = 0; k < kScanPer; ++k) {
+    const int64_t s = base + (int64_t)k * kThreads + threadIdx.x;
+    c[k] = s < ws.nslots ? ws.table[s].count : 0u;
+    sum += c[k];
+  }
+  const uint32_t incl = wave_incl_scan_u32(sum);
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  uint32_t run = ws.tile[blockIdx.x] + incl - sum;
+  for (int w = 0; w < wave; ++w) run += wsum[w];
+#pragma unroll
+  for (int k = 0; k < kScanPer; ++k) {
+    const int64_t s = base + (int64_t)k * kThreads + threadIdx.x;
+    if (s < ws.nslots) ws.table[s].end = run;
+    run += c[k];
+  }
+}
+
+// every usable reference takes the next record of its cell (rs_count claimed the slot in an earlier launch: plain reads find it)
+__global__ __launch_bounds__(kThreads) void rs_scatter(ovg_radius_params p, RsWs ws) {
+  const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
+  float r[3];
+  if (j >= (uint32_t)p.nr || !rs_point(p.reference, p.reference_valid, j, r)) return;
+  const uint64_t key = rs_key(rs_cell(r[0], rs_origin(p.origin, 0), p.cell), rs_cell(r[1], rs_origin(p.origin, 1), p.cell),
+                              rs_cell(r[2], rs_origin(p.origin, 2), p.cell));
+  uint32_t count, end;
+  const int64_t s = rs_find(ws, key, count, end);
+  if (s < 0) return;
+  const uint32_t pos = __hip_atomic_fetch_add(&ws.table[s].end, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (pos >= (uint32_t)p.nr) return;                   // the counts sum to the usable references: never taken after a matching rs_count
+  const u32x4 e = {__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), j};
+  ws.rec[pos] = e;
+}
+
+// the cost of the search: for every usable query the references in the cells of its box (hash probes only)
+__global__ __launch_bounds__(kThreads) void rs_cost(ovg_radius_params p, RsWs ws, float reach) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  float q[3];
+  uint64_t sum = 0;
+  if (i < (uint32_t)p.nq && rs_point(p.query, p.query_valid, i, q)) {
+    const RsBox b = rs_box(q, p.origin, p.cell, reach);
+    for (uint32_t cx = b.lo[0]; cx <= b.hi[0]; ++cx)
+      for (uint32_t cy = b.lo[1]; cy <= b.hi[1]; ++cy)
+        for (uint32_t cz = b.lo[2]; cz <= b.hi[2]; ++cz) {
+          uint32_t count, end;
+          if (rs_find(ws, rs_key(cx, cy, cz), count, end) >= 0) sum += count;
+        }
+  }
+  for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+  if ((threadIdx.x & 63) == 0 && sum) __hip_atomic_fetch_add(&ws.head->pairs, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+OVG_DEV uint32_t rs_origin_flag(const float* origin) {
+  return origin && !finite3(origin[0], origin[1], origin[2]) ? (uint32_t)OVG_RS_BAD_ORIGIN : 0u;
+}
+
+// after BUILD: the table now describes this cloud; its statistics leave for the host
+__global__ void rs_built(ovg_radius_params p, RsWs ws) {
+  RsHead& h = *ws.head;
+  h.flags = rs_origin_flag(p.origin);
+  h.nr = p.nr;
+  p.out_stats[0] = (int64_t)h.flags, p.out_stats[1] = (int64_t)h.occupied, p.out_stats[2] = (int64_t)h.max_cell, p.out_stats[3] = (int64_t)h.pairs;
+}
+
+OVG_DEV uint32_t rs_refusal(const ovg_radius_params& p, const RsHead& h) {
+  if (h.nr != p.nr) return OVG_RS_NOT_BUILT;
+  return h.pairs > (uint64_t)p.max_pairs ? (uint32_t)OVG_RS_OVER_BUDGET : 0u;
+}
+
+__global__ void rs_searched(ovg_radius_params p, RsWs ws) {
+  const RsHead& h = *ws.head;
+  const uint32_t no = rs_refusal(p, h);
+  p.out_stats[0] = (int64_t)(no == OVG_RS_NOT_BUILT ? no : (h.flags | no));
+  p.out_stats[1] = no == OVG_RS_NOT_BUILT ? 0 : (int64_t)h.occupied;
+  p.out_stats[2] = no == OVG_RS_NOT_BUILT ? 0 : (int64_t)h.max_cell;
+  p.out_stats[3] = no == OVG_RS_NOT_BUILT ? 0 : (int64_t)h.pairs;
+}
+
+// one query per thread: the box of cells, a probe per cell, the rule over the cell's records. The trip counts depend on the data
+// (cells per box, records per cell): lanes of a wave idle while the longest of them runs; queries arrive in pixel order, so
+// neighbouring lanes mostly share their cells
+__global__ __launch_bounds__(kThreads) void rs_search(ovg_radius_params p, RsWs ws, float reach) {
+  if (rs_refusal(p, *ws.head)) return;                 // the work guard, the same in every thread: nothing is written
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= (uint32_t)p.nq) return;
+  float q[3];
+  int32_t cnt = 0;
+  uint64_t best = kNoneKey;
+  if (rs_point(p.query, p.query_valid, i, q)) {
+    const uint32_t rbits = __float_as_uint(p.radius_sq), nr = (uint32_t)p.nr;
+    const bool exclude = (p.flags & OVG_RS_EXCLUDE_SAME_INDEX) != 0;
+    const RsBox b = rs_box(q, p.origin, p.cell, reach);
+    for (uint32_t cx = b.lo[0]; cx <= b.hi[0]; ++cx)
+      for (uint32_t cy = b.lo[1]; cy <= b.hi[1]; ++cy)
+        for (uint32_t cz = b.lo[2]; cz <= b.hi[2]; ++cz) {
+          uint32_t count, end;
+          if (rs_find(ws, rs_key(cx, cy, cz), count, end) < 0) continue;
+          end = min(end, nr);                          // a workspace another call has scribbled over still cannot send a read outside rec
+          const uint32_t first = end - min(count, end);
+#pragma unroll 4
+          for (uint32_t r = first; r < end; ++r) {
+            const u32x4 e = ws.rec[r];
+            const float dx = q[0] - __uint_as_float(e[0]), dy = q[1] - __uint_as_float(e[1]), dz = q[2] - __uint_as_float(e[2]);
+            const float d = (dx * dx + dy * dy) + dz * dz;                 // +0, positive or +inf: the bits order like the value
+            const uint32_t bits = __float_as_uint(d);
+            const bool ok = bits <= rbits && !(exclude && e[3] == i);
+            const uint64_t key = ((uint64_t)bits << 32) | e[3];            // (bits(d), j): the order inside a cell does not matter
+            cnt += ok;
+            best = ok && key < best ? key : best;
+          }
+        }
+  }
+  const bool found = best != kNoneKey;
+  p.count[i] = cnt;
+  p.index[i] = found ? (int32_t)(uint32_t)best : -1;
+  p.sqdist[i] = __uint_as_float(found ? (uint32_t)(best >> 32) : kInfBits);
+}
+
+bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
+
+unsigned grid_for(int64_t work, int64_t per_block, int64_t cap) {
+  const int64_t b = (work + per_block - 1) / per_block;
+  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+}  // namespace
+
+extern "C" int64_t ovg_radius_workspace_bytes(int64_t nq, int64_t nr) { return rs_shape_ok(nq, nr) ? rs_ws_bytes(nr) : -1; }
+
+extern "C" int ovg_radius_search(const ovg_radius_params* p, void* stream) {
+  if (!p || !p->query || !p->reference || !p->ws) return OVG_E_ARG;
+  if (!rs_shape_ok(p->nq, p->nr) || (p->flags & ~OVG_RS_EXCLUDE_SAME_INDEX)) return OVG_E_ARG;
+  if (p->stage < 1 || p->stage > (OVG_RS_BUILD | OVG_RS_SEARCH)) return OVG_E_ARG;
+  if ((p->flags & OVG_RS_EXCLUDE_SAME_INDEX) && p->nq != p->nr) return OVG_E_ARG;
+  if (!(p->radius_sq >= kMinRadiusSq) || !isfinite(p->radius_sq)) return OVG_E_ARG;
+  const float reach = rs_reach(p->radius_sq);
+  if (!(p->cell >= reach) || !isfinite(p->cell)) return OVG_E_ARG;
+  if ((p->stage & OVG_RS_BUILD) && !p->out_stats) return OVG_E_ARG;
+  if ((p->stage & OVG_RS_SEARCH) && (!p->count || !p->index || !p->sqdist || p->max_pairs < 0)) return OVG_E_ARG;
+  if (!al(p->query, 4) || !al(p->reference, 4) || !al(p->origin, 4) || !al(p->count, 4) || !al(p->index, 4) || !al(p->sqdist, 4) ||
+      !al(p->out_stats, 8))
+    return OVG_E_ARG;
+  if (!al(p->ws, 16) || p->ws_bytes < rs_ws_bytes(p->nr)) return OVG_E_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const RsWs ws = rs_ws(p);
+  const dim3 block(kThreads), per_ref((unsigned)((p->nr + kThreads - 1) / kThreads)), per_query((unsigned)((p->nq + kThreads - 1) / kThreads));
+  if (p->stage & OVG_RS_BUILD) {
+    OVG_LAUNCH(rs_clear, dim3(grid_for(ws.nslots, kThreads * 4, 4096)), block, 0, st, ws);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(rs_count, per_ref, block, 0, st, *p, ws);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(rs_tile_sums, dim3((unsigned)ws.ntiles), block, 0, st, ws);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(rs_scan_tiles, dim3(1), dim3(1024), 0, st, ws);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(rs_starts, dim3((unsigned)ws.ntiles), block, 0, st, ws);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(rs_scatter, per_ref, block, 0, st, *p, ws);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(rs_cost, per_query, block, 0, st, *p, ws, reach);
+    OVG_CHECK_LAUNCH();
+    OVG_LAUNCH(rs_built, dim3(1), dim3(1), 0, st, *p, ws);
+    OVG_CHECK_LAUNCH();
+  }
+  if (p->stage & OVG_RS_SEARCH) {
+    OVG_LAUNCH(rs_search, per_query, block, 0, st, *p, ws, reach);
+    OVG_CHECK_LAUNCH();
+    if (p->out_stats) {
+      OVG_LAUNCH(rs_searched, dim3(1), dim3(1), 0, st, *p, ws);
+      OVG_CHECK_LAUNCH();
+    }
+  }
+  return OVG_OK;
+}

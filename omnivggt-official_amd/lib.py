@@ -250,6 +250,18 @@ class FpsParams(C.Structure):
                 ("ws", vp), ("ws_bytes", i64), ("index", vp), ("sqdist", vp), ("distance", vp)]
 
 
+RS_BUILD, RS_SEARCH = 1, 2                                   # ovg_radius_params.stage
+RS_EXCLUDE_SAME_INDEX = 1
+RS_BAD_ORIGIN, RS_OVER_BUDGET, RS_NOT_BUILT = 1, 2, 4        # out_stats[0]
+RS_MIN_SLOTS, RS_QUERY_BLOCK = 1024, 256                     # smallest hash table, queries per workgroup (tests place shapes around them)
+
+
+class RadiusParams(C.Structure):
+    _fields_ = [("query", vp), ("reference", vp), ("query_valid", vp), ("reference_valid", vp), ("origin", vp), ("nq", i64), ("nr", i64),
+                ("radius_sq", f32), ("cell", f32), ("flags", i32), ("stage", i32), ("max_pairs", i64), ("ws", vp), ("ws_bytes", i64),
+                ("out_stats", vp), ("count", vp), ("index", vp), ("sqdist", vp)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -325,6 +337,8 @@ SYMBOLS = {
     "ovg_nn_workspace_bytes": (i64, [i64, i64]),
     "ovg_farthest_point_sample": (i32, [C.POINTER(FpsParams), vp]),
     "ovg_fps_workspace_bytes": (i64, [i64, i64, i64]),
+    "ovg_radius_search": (i32, [C.POINTER(RadiusParams), vp]),
+    "ovg_radius_workspace_bytes": (i64, [i64, i64]),
 }
 
 

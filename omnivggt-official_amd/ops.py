@@ -861,3 +861,71 @@ def farthest_point_sample(points, npoint, valid=None, first=0, include_last=Fals
     p.ws, p.ws_bytes, p.index, p.sqdist, p.distance = L.ptr(ws), nbytes(ws), L.ptr(index), L.ptr(sqdist), L.ptr(distance)
     L.call("ovg_farthest_point_sample", p, _stream())
     return index, sqdist, distance
+
+
+def radius_reach(radius_sq):
+    """REACH of include/omnivggt_hip.h for a float32 radius_sq: the float32 just above sqrt((double)radius_sq) (1 + 2^-20). The box of
+    cells a query scans spans +-REACH per axis, and REACH is the smallest cell edge ovg_radius_search accepts."""
+    import math
+    import struct
+    r2 = struct.unpack("f", struct.pack("f", float(radius_sq)))[0]
+    v = math.sqrt(r2) * (1.0 + 2.0 ** -20)
+    bits = struct.unpack("I", struct.pack("f", v))[0]                        # rounded to nearest
+    if struct.unpack("f", struct.pack("I", bits))[0] <= v:
+        bits += 1                                                            # positive and finite: the next float up
+    return struct.unpack("f", struct.pack("I", bits))[0]
+
+
+def radius_workspace_bytes(nq, nr):
+    for v in (nq, nr):
+        if not -(1 << 63) <= int(v) < (1 << 63):
+            raise L.OvgError("ovg_radius_workspace_bytes: unsupported (nq=%d, nr=%d)" % (nq, nr))
+    b = L.load().ovg_radius_workspace_bytes(int(nq), int(nr))
+    if b < 0:
+        raise L.OvgError("ovg_radius_workspace_bytes: unsupported (nq=%d, nr=%d)" % (nq, nr))
+    return int(b)
+
+
+def radius_search(stage, query, reference, radius_sq, cell, ws, query_valid=None, reference_valid=None, origin=None, exclude_self=False,
+                  max_pairs=0, out_stats=None, count=None, index=None, sqdist=None):
+    """ovg_radius_search on contiguous device tensors: query f32 [nq, 3], reference f32 [nr, 3], query_valid / reference_valid u8 [nq] /
+    [nr] or None, origin f32 [3] or None (zeros); radius_sq and cell are host floats (taken as float32; cell >= radius_reach(radius_sq)),
+    ws a uint8 device tensor of at least radius_workspace_bytes(nq, nr) bytes that carries the grid from one stage to the next.
+    stage L.RS_BUILD bins the references and writes (flags, occupied cells, largest cell, candidate pairs) to out_stats (int64 [4],
+    allocated when None); L.RS_SEARCH writes count int32 [nq], index int32 [nq] and sqdist f32 [nq] (allocated when None) -- or nothing
+    at all when the candidate pairs exceed max_pairs, which out_stats (if given) then reports as L.RS_OVER_BUDGET.
+    -> (out_stats, count, index, sqdist), None for what the stage does not write. Nothing is read back."""
+    _chk_dev(query, reference, ws, query_valid, reference_valid, origin, out_stats, count, index, sqdist)
+    for t, name in ((query, "query"), (reference, "reference")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
+            raise L.OvgError("radius_search: %s must be a contiguous f32 tensor [n, 3]" % name)
+    nq, nr = int(query.shape[0]), int(reference.shape[0])
+    for v, n, name in ((query_valid, nq, "query_valid"), (reference_valid, nr, "reference_valid")):
+        if v is not None and (v.dtype != torch.uint8 or not v.is_contiguous() or tuple(v.shape) != (n,)):
+            raise L.OvgError("radius_search: %s must be a contiguous u8 tensor [%d]" % (name, n))
+    if origin is not None and (origin.dtype != torch.float32 or not origin.is_contiguous() or origin.numel() != 3):
+        raise L.OvgError("radius_search: origin must be a contiguous f32 tensor of three elements")
+    if exclude_self and nq != nr:
+        raise L.OvgError("radius_search: exclude_self needs nq == nr (got %d, %d)" % (nq, nr))
+    stage = int(stage)
+    if stage & L.RS_BUILD and out_stats is None:
+        out_stats = torch.empty(4, device=query.device, dtype=torch.int64)
+    if out_stats is not None and (out_stats.dtype != torch.int64 or out_stats.numel() != 4 or not out_stats.is_contiguous()):
+        raise L.OvgError("radius_search: out_stats must be a contiguous int64 tensor of four elements")
+    if stage & L.RS_SEARCH:
+        count = torch.empty(nq, device=query.device, dtype=torch.int32) if count is None else count
+        index = torch.empty(nq, device=query.device, dtype=torch.int32) if index is None else index
+        sqdist = torch.empty(nq, device=query.device, dtype=torch.float32) if sqdist is None else sqdist
+        for t, dt in ((count, torch.int32), (index, torch.int32), (sqdist, torch.float32)):
+            if t.dtype != dt or t.numel() != nq or not t.is_contiguous():
+                raise L.OvgError("radius_search: count / index / sqdist must be contiguous int32 / int32 / f32 tensors [%d]" % nq)
+    else:
+        count = index = sqdist = None
+    p = L.RadiusParams()
+    p.query, p.reference, p.query_valid, p.reference_valid = L.ptr(query), L.ptr(reference), L.ptr(query_valid), L.ptr(reference_valid)
+    p.origin, p.nq, p.nr, p.radius_sq, p.cell = L.ptr(origin), nq, nr, float(radius_sq), float(cell)
+    p.flags, p.stage, p.max_pairs = L.RS_EXCLUDE_SAME_INDEX if exclude_self else 0, stage, int(max_pairs)
+    p.ws, p.ws_bytes, p.out_stats = L.ptr(ws), nbytes(ws), L.ptr(out_stats)
+    p.count, p.index, p.sqdist = L.ptr(count), L.ptr(index), L.ptr(sqdist)
+    L.call("ovg_radius_search", p, _stream())
+    return out_stats, count, index, sqdist

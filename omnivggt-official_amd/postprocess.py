@@ -521,6 +521,203 @@ def cloud_distance(pred, gt, threshold=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# Radius neighbour search on a hash grid: floater removal and F-score of full clouds (ovg_radius_search)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+# The default work budget of a radius search, in candidate pairs (distances the search evaluates). MEASURED on an MI355X
+# (profiles/radius_probe.txt, tools/probes/radius_probe.py): the grid loop evaluates 4.7e10 .. 4.1e11 pairs/s (lowest at 8 neighbours
+# per query, where hash probes and short divergent loops dominate). 2^37 = 1.4e11 pairs is the largest power of two that stays under
+# 5 s at the LOWEST measured rate (2.9 s); 2^40, the size of the 1 M x 1 M exhaustive search, would be 23 s there. The 64-neighbour
+# search inside the full 64-view cloud (17.2 M points) needs 5.2e9.
+RADIUS_MAX_PAIRS = 1 << 37
+
+
+class RadiusResult:
+    """Result of radius_neighbours: count int32 (reference points within the radius), index int32 (the nearest of them, -1 where there
+    is none) and sqdist float32 (the squared distance to it, +inf where there is none), device tensors shaped like the query without
+    its last dimension."""
+    __slots__ = ("count", "index", "sqdist")
+
+    def __init__(self, count, index, sqdist):
+        self.count, self.index, self.sqdist = count, index, sqdist
+
+
+def _f32(x):
+    import struct
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def _radius_sq(radius, what="radius"):
+    """f32(f32(radius)^2), checked: the squared radius exactly as the kernel compares with it."""
+    import math
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not (radius > 0 and math.isfinite(radius)):
+        raise ValueError("%s must be a positive finite number, got %r" % (what, radius))
+    try:
+        r = _f32(float(radius))
+        r2 = _f32(r * r)                                                     # the product of two float32 is exact in float64: one rounding
+    except OverflowError:
+        r2 = float("inf")
+    if not (math.isfinite(r2) and r2 >= 2.0 ** -100):
+        raise ValueError("%s %r squares to %r in float32: outside [2^-100, float32 max]" % (what, radius, r2))
+    return r2
+
+
+def radius_neighbours(query, reference, radius, query_valid=None, reference_valid=None, exclude_self=False, cell_size=None, origin=None,
+                      max_pairs=None):
+    """For every query point the number of reference points within `radius` and the nearest of them, searched through a uniform hash grid
+    on the device (ovg_radius_search), so that the cost is linear in the clouds for a sensible radius where nearest_neighbours is
+    quadratic. The result is defined WITHOUT the grid, as nearest_neighbours' rule restricted to d <= radius_sq (tests/radius_twin.py
+    restates it by brute force): d = (dx dx + dy dy) + dz dz in float32 without fused multiply-adds, radius_sq = f32(f32(radius)^2),
+    a usable reference is within the radius when d <= radius_sq (inclusive), the nearest is the smallest d, equal distances go to the
+    LOWEST reference index. The grid never changes a byte, nor does cell_size or origin; two calls give identical
+    bytes. An unusable query (non-finite coordinates or a zero valid entry), or one with nothing within the radius, gets count 0,
+    index -1, sqdist +inf; a distance that overflows float32 is never within a radius.
+
+    query, reference: float32 device tensors (..., 3), or PointClouds; query_valid / reference_valid: optional bool / uint8 tensors
+    shaped like the points without the last dimension. exclude_self=True searches inside one cloud (equal sizes): point i does not count
+    for itself. cell_size: the grid's cell edge, at least (and by default) the radius plus a rounding margin (ops.radius_reach);
+    origin: three finite floats or a float32 device tensor [3] the grid is anchored at (default zeros) -- both move work, not results.
+    max_pairs: the work budget (default RADIUS_MAX_PAIRS). A radius too large for the cloud would make single threads walk most of it;
+    the grid is built first, the number of candidate pairs (distances the search would evaluate) is read back -- the one device -> host
+    synchronisation -- and a count above the budget raises ValueError before the search is launched.
+
+    -> RadiusResult(count int32, index int32, sqdist float32) shaped like the query's leading dimensions. An empty side returns
+    zeros / -1 / +inf without a launch. CPU tensors raise OvgError (there is no CPU fallback); a bad radius, cell or shape raises
+    ValueError."""
+    import math
+    L = ops.L
+    q, r = _nn_points(query, "query"), _nn_points(reference, "reference")
+    lead = tuple(q.shape[:-1])
+    qv, rv = _nn_valid(query_valid, lead, "query_valid"), _nn_valid(reference_valid, tuple(r.shape[:-1]), "reference_valid")
+    nq, nr = q.numel() // 3, r.numel() // 3
+    if exclude_self and nq != nr:
+        raise ValueError("exclude_self searches inside one cloud: query and reference must hold the same number of points (%d, %d)" % (nq, nr))
+    radius_sq = _radius_sq(radius)
+    reach = ops.radius_reach(radius_sq)
+    if cell_size is None:
+        cell = reach
+    else:
+        if isinstance(cell_size, bool) or not isinstance(cell_size, (int, float)) or not math.isfinite(cell_size):
+            raise ValueError("cell_size must be a finite number, got %r" % (cell_size,))
+        cell = _f32(float(cell_size))
+        if not (cell >= reach and math.isfinite(cell)):
+            raise ValueError("cell_size %r is below the reach %r of radius %r (the radius plus its rounding margin)" % (cell_size, reach, radius))
+    if max_pairs is None:
+        max_pairs = RADIUS_MAX_PAIRS
+    if isinstance(max_pairs, bool) or not isinstance(max_pairs, int) or not 0 <= max_pairs < 1 << 63:
+        raise ValueError("max_pairs must be a non-negative integer, got %r" % (max_pairs,))
+    org = None
+    if isinstance(origin, torch.Tensor):
+        if origin.dtype != torch.float32 or origin.numel() != 3:
+            raise ValueError("origin must hold three float32 values")
+        org = origin
+    elif origin is not None:
+        try:
+            vals = [float(v) for v in origin]
+        except (TypeError, ValueError):
+            raise ValueError("origin must be three finite numbers or a float32 tensor [3], got %r" % (origin,)) from None
+        if len(vals) != 3 or not all(math.isfinite(v) and abs(v) <= 3.4028234663852886e38 for v in vals):
+            raise ValueError("origin must be three finite float32 numbers, got %r" % (origin,))
+    if not all(t is None or t.is_cuda for t in (q, r, qv, rv, org)):
+        raise L.OvgError("radius_neighbours needs HIP device tensors: there is no CPU fallback")
+    dev = q.device
+    if nq == 0 or nr == 0:
+        return RadiusResult(torch.zeros(lead, device=dev, dtype=torch.int32), torch.full(lead, -1, device=dev, dtype=torch.int32),
+                            torch.full(lead, float("inf"), device=dev, dtype=torch.float32))
+    if origin is not None and org is None:
+        org = torch.tensor(vals, device=dev, dtype=torch.float32)
+    elif org is not None:
+        org = org.reshape(3).contiguous()
+    u8 = lambda v: None if v is None else (v.to(torch.uint8) if v.dtype == torch.bool else v).reshape(-1).contiguous()
+    args = dict(query=q.reshape(nq, 3).contiguous(), reference=r.reshape(nr, 3).contiguous(), radius_sq=radius_sq, cell=cell,
+                ws=torch.empty(ops.radius_workspace_bytes(nq, nr), device=dev, dtype=torch.uint8), query_valid=u8(qv),
+                reference_valid=u8(rv), origin=org, exclude_self=bool(exclude_self))
+    stats = ops.radius_search(L.RS_BUILD, **args)[0]
+    flags, cells, largest, pairs = (int(v) for v in stats.cpu().tolist())   # the one synchronisation
+    if flags & L.RS_BAD_ORIGIN:
+        raise ValueError("radius_neighbours: the origin on the device is not finite")
+    if pairs > max_pairs:
+        raise ValueError("radius_neighbours: radius %r makes the search evaluate %d candidate pairs, above the budget of %d (max_pairs); "
+                         "the largest of the %d occupied cells holds %d of the %d reference points -- lower the radius, or raise max_pairs "
+                         "knowingly" % (radius, pairs, max_pairs, cells, largest, nr))
+    _, cnt, idx, sq = ops.radius_search(L.RS_SEARCH, max_pairs=max_pairs, **args)
+    return RadiusResult(cnt.reshape(lead), idx.reshape(lead), sq.reshape(lead))
+
+
+def radius_outlier_mask(cloud_or_points, radius=None, rel_radius=None, min_neighbours=2, valid=None):
+    """Radius outlier test of a cloud on the device: True where a point has at least min_neighbours OTHER points within `radius`
+    (radius_neighbours inside the cloud with exclude_self; Open3D's remove_radius_outlier counts the point itself, so its nb_points is
+    min_neighbours + 1). It judges what multiview_consistency cannot: floaters that a single view sees. Exactly one of radius (in the
+    cloud's units) and rel_radius (a PointCloud only: f32(rel_radius) * scene_scale, multiplied on the host) must be given. valid:
+    optional bool / uint8 tensor; a point that is not valid or not finite is no neighbour of anything and is itself False.
+    -> bool device tensor shaped like the points without the last dimension. Synchronises as radius_neighbours does; errors as there."""
+    import math
+    if (radius is None) == (rel_radius is None):
+        raise ValueError("radius_outlier_mask: give exactly one of radius and rel_radius")
+    if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, int) or min_neighbours < 1:
+        raise ValueError("min_neighbours must be a positive integer, got %r" % (min_neighbours,))
+    pts = _nn_points(cloud_or_points, "cloud_or_points")
+    _nn_valid(valid, tuple(pts.shape[:-1]), "valid")
+    if rel_radius is not None:
+        if isinstance(rel_radius, bool) or not isinstance(rel_radius, (int, float)) or not (rel_radius > 0 and math.isfinite(rel_radius)):
+            raise ValueError("rel_radius must be a positive finite number, got %r" % (rel_radius,))
+        if not isinstance(cloud_or_points, PointCloud) or cloud_or_points.scene_scale is None:
+            raise ValueError("rel_radius needs a PointCloud with its scene_scale")
+        _radius_sq(rel_radius, "rel_radius")
+        if not pts.is_cuda:
+            raise ops.L.OvgError("radius_outlier_mask needs HIP device tensors: there is no CPU fallback")
+        radius = _f32(_f32(float(rel_radius)) * float(cloud_or_points.scene_scale.to(torch.float32)))   # one float32 multiply
+    res = radius_neighbours(pts, pts, radius, valid, valid, exclude_self=True)
+    return res.count >= min_neighbours
+
+
+def remove_radius_outliers(cloud, radius=None, rel_radius=None, min_neighbours=2):
+    """A PointCloud without its radius outliers (radius_outlier_mask), in input order: points, colors and conf are gathered, `indices`
+    are the input cloud's at the kept points when it has them (so they still name pixels of the prediction maps) and the positions in the
+    input cloud otherwise; transform, extrinsic, conf_threshold and scene_scale are passed through unchanged, as
+    farthest_point_downsample does. write_ply, write_glb and render_point_cloud accept the result as they are."""
+    if not isinstance(cloud, PointCloud):
+        raise ValueError("remove_radius_outliers takes a PointCloud")
+    M = len(cloud)
+    keep = radius_outlier_mask(cloud, radius=radius, rel_radius=rel_radius, min_neighbours=min_neighbours)
+    idx = torch.nonzero(keep.reshape(-1)).reshape(-1)
+    return PointCloud(cloud.points.reshape(M, 3)[idx], None if cloud.colors is None else cloud.colors.reshape(M, 3)[idx],
+                      cloud.conf_threshold, cloud.scene_scale, cloud.transform, cloud.extrinsic,
+                      idx if cloud.indices is None else cloud.indices[idx], None if cloud.conf is None else cloud.conf[idx])
+
+
+def cloud_fscore(pred, gt, threshold, max_pairs=None):
+    """Precision, recall and F-score of a predicted cloud against a ground-truth cloud at a distance threshold, with the truncated
+    accuracy / completeness / chamfer, from two radius searches on the device (radius_neighbours at radius = threshold): linear in the
+    clouds, where cloud_distance's two unbounded exhaustive searches stop at about a million points.
+    n_pred / n_gt: the usable points (finite coordinates) of each side. precision: the share of the usable predicted points with a
+    ground-truth point within the threshold; recall: the same from the ground truth; fscore = 2 P R / (P + R), 0 when both are 0.
+    accuracy / completeness: the float64 mean of min(sqrt(sqdist), threshold) over the usable points of the side (a point with nothing
+    within the threshold counts as the threshold: the truncated distance); chamfer their mean. Medians are None; a side without usable
+    points reports nan.
+    "Within" here is d_f32 <= f32(f32(threshold)^2) on the float32 squared distance, inclusive, where cloud_distance tests
+    sqrt(d) < threshold in float64: two functions, two rules, and a point exactly at the threshold may count here and not there.
+    pred, gt: float32 (..., 3) device tensors or PointClouds. -> CloudDistance. max_pairs: the budget of each search, as in
+    radius_neighbours (ValueError when exceeded)."""
+    _radius_sq(threshold, "threshold")
+    a, b = _nn_points(pred, "pred"), _nn_points(gt, "gt")
+    if not (a.is_cuda and b.is_cuda):
+        raise ops.L.OvgError("cloud_fscore needs HIP device tensors: there is no CPU fallback")
+    sides = []
+    for x, y in ((a, b), (b, a)):
+        res = radius_neighbours(x, y, threshold, max_pairs=max_pairs)
+        ok = torch.isfinite(x).all(dim=-1).reshape(-1)
+        d = res.sqdist.reshape(-1).double().sqrt().clamp_max(float(threshold))
+        hits = (res.count.reshape(-1) >= 1) & ok
+        n, k, total = torch.stack([ok.sum().double(), hits.sum().double(), torch.where(ok, d, d.new_zeros(())).sum()]).tolist()
+        n, k = int(n), int(k)
+        sides.append((total / n if n else float("nan"), n, k / n if n else float("nan")))
+    (acc, n_pred, prec), (comp, n_gt, rec) = sides
+    return CloudDistance(accuracy=acc, completeness=comp, chamfer=(acc + comp) / 2, n_pred=n_pred, n_gt=n_gt, threshold=float(threshold),
+                         precision=prec, recall=rec, fscore=2 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # Farthest-point sampling: a fixed number of well-spread points (ovg_farthest_point_sample)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
