@@ -62,7 +62,9 @@ extern "C" {
  *     + multi-view depth consistency (ovg_multiview_consistency, ovg_consistency_workspace_bytes): added the same way
  *     + nearest-neighbour search between point clouds (ovg_nearest_neighbours, ovg_nn_workspace_bytes): added the same way
  *     + farthest-point sampling of point clouds (ovg_farthest_point_sample, ovg_fps_workspace_bytes): added the same way
- *     + radius neighbour search on a hash grid (ovg_radius_search, ovg_radius_workspace_bytes): added the same way */
+ *     + radius neighbour search on a hash grid (ovg_radius_search, ovg_radius_workspace_bytes): added the same way
+ *     + k nearest neighbours within a radius on that grid, and PCA normals from the table (ovg_knn_search, ovg_knn_normals): added
+ *       the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -840,6 +842,76 @@ typedef struct {
 } ovg_radius_params;
 int64_t ovg_radius_workspace_bytes(int64_t nq, int64_t nr);
 int ovg_radius_search(const ovg_radius_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * The k nearest neighbours within a radius (added under ABI 13), on the grid ovg_radius_search builds: the neighbourhood itself where
+ * ovg_radius_search returns its size and its nearest point (the hybrid search: k nearest, but only those within the radius).
+ * Defined WITHOUT the grid by rules 1, 2, 3 and 6 of ovg_radius_search; tests/knn_twin.py restates it by brute force:
+ *   d = (dx dx + dy dy) + dz dz in f32, one rounding per operation; a CANDIDATE of a usable query i is a usable reference j with
+ *   bits(d) <= bits(radius_sq) (inclusive), and j != i with OVG_RS_EXCLUDE_SAME_INDEX;
+ *   count[i] = the number of candidates: the value ovg_radius_search writes;
+ *   index[i][t], sqdist[i][t], t < k: the candidates in ascending order of (bits(d), j) -- nearest first, equal distances in
+ *   ascending reference index; ranks t >= min(k, count[i]) hold index -1 and sqdist +inf; an unusable query has count 0 and every
+ *   rank -1 / +inf. Rank 0 is ovg_radius_search's index / sqdist. 1 <= k <= OVG_KNN_MAX_K.
+ * A search only: it reads the grid ovg_radius_search(stage = OVG_RS_BUILD) left in ws for the same reference, radius_sq, cell and
+ * origin (ws_bytes >= ovg_radius_workspace_bytes(nq, nr)), with the same walk over the same box, so the grid never changes a byte
+ * of this either. One query per thread in workgroups of OVG_RS_QUERY_BLOCK; the running selection is a sorted list of K packed keys
+ * (bits(d) << 32) | j in registers, K the smallest of 4, 8, 16, 32 that is >= k (the result does not depend on K): a candidate is
+ * compared with the worst key first, and only an accepted one runs the K compare-and-swaps of the insertion.
+ * WORK GUARD and OVG_RS_NOT_BUILT as in OVG_RS_SEARCH: nothing is written to count / index / sqdist when the candidate pairs BUILD
+ * counted exceed max_pairs or ws holds no BUILD of this nr; out_stats int64[4] (optional) reports as it does there.
+ *   count [nq] int32, index [nq][k] int32, sqdist [nq][k] f32. Nothing is allocated or read back.
+ *   OVG_E_ARG: as OVG_RS_SEARCH (NULL params / query / reference / ws / count / index / sqdist, bad nq / nr, radius_sq, cell, flags,
+ *   OVG_RS_EXCLUDE_SAME_INDEX with nq != nr, max_pairs < 0, alignment, a misaligned or undersized workspace), and k outside
+ *   [1, OVG_KNN_MAX_K].
+ * ------------------------------------------------------------------ */
+enum { OVG_KNN_MAX_K = 32 };
+typedef struct {
+  const float* query; const float* reference;
+  const uint8_t* query_valid; const uint8_t* reference_valid;
+  const float* origin;
+  int64_t nq; int64_t nr;
+  float radius_sq; float cell;
+  int32_t flags; int32_t k;
+  int64_t max_pairs;
+  void* ws; int64_t ws_bytes;
+  int64_t* out_stats;
+  int32_t* count; int32_t* index; float* sqdist;
+} ovg_knn_params;
+int ovg_knn_search(const ovg_knn_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * PCA normals from a neighbour table (added under ABI 13): for every query the normal of the plane through the reference points
+ * that its row of `index` names (as ovg_knn_search writes it: any k >= 1).
+ *   query [nq][3] f32, reference [nr][3] f32, index [nq][k] int32; viewpoint f32: NULL, [3] shared by all queries
+ *   (viewpoint_stride 0) or [nq][3] (viewpoint_stride 3).
+ *   Everything in float64, every operation rounded on its own (no fused multiply-add), over the ranks t in ascending order:
+ *   1. the NEIGHBOURS are the entries with 0 <= index < nr, any other entry is skipped; m = their number;
+ *   2. mean = (the sum of the neighbours, from +0) / m per coordinate;
+ *   3. covariance entry ab = (the sum of (p - mean)_a (p - mean)_b, from +0) / m, for xx xy xz yy yz zz (m = 0: all zero);
+ *   4. m < 3 or a non-finite covariance entry: normal (0, 0, 0), curvature 0;
+ *   5. else OVG_KNN_NORMALS_SWEEPS sweeps of cyclic Jacobi rotations (0,1), (0,2), (1,2) (a zero off-diagonal entry is skipped;
+ *      theta = (aqq - app) / (2 apq), t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c); the normal is
+ *      the column of the accumulated rotations under the SMALLEST diagonal entry lambda0 (the lowest column on ties), divided by its
+ *      length;
+ *   6. curvature = lambda0 / ((xx + yy) + zz) of step 3 (the surface variation; 0 when the trace or lambda0 is not positive);
+ *   7. orientation: with a viewpoint v the normal is negated when (n.x (v - q).x + n.y (v - q).y) + n.z (v - q).z < 0; without, when
+ *      its component of largest magnitude (the lowest axis on ties) is negative; then it is rounded to f32.
+ *   normal [nq][3] f32; optional (NULL: not written) curvature [nq] f32, covariance [nq][6] f64 (step 3, written for every query),
+ *   used [nq] int32 (m). One query per thread; nothing is allocated or read back.
+ *   OVG_E_ARG: NULL params / query / reference / index / normal, nq or nr outside [1, 2^31), k < 1, viewpoint_stride not 0 or 3
+ *   (not 0 without a viewpoint), a pointer that is not 4-byte (covariance: 8-byte) aligned.
+ * ------------------------------------------------------------------ */
+enum { OVG_KNN_NORMALS_SWEEPS = 8 };
+typedef struct {
+  const float* query; const float* reference;
+  const int32_t* index; const float* viewpoint;
+  int64_t nq; int64_t nr;
+  int32_t k; int32_t viewpoint_stride;
+  float* normal; float* curvature;
+  double* covariance; int32_t* used;
+} ovg_knn_normals_params;
+int ovg_knn_normals(const ovg_knn_normals_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

@@ -323,6 +323,65 @@ __global__ __launch_bounds__(kThreads) void rs_search(ovg_radius_params p, RsWs 
   p.sqdist[i] = __uint_as_float(found ? (uint32_t)(best >> 32) : kInfBits);
 }
 
+// ovg_knn_search: rs_search's walk, keeping the K smallest keys instead of the smallest. The selection is a sorted list of K keys in
+// registers (key[0] the nearest). A candidate first meets the worst key: one 64-bit compare, and most candidates end there once the
+// list is full of near points. An accepted one runs a chain of K compare-and-swaps from the front, which carries the larger key of
+// every pair on and drops the last: every index is a compile-time constant after unrolling, so the list never goes to scratch (a
+// runtime-indexed per-thread array would). Keys of different references differ in their low word, so no compare ever ties. The K
+// smallest keys hold the k <= K smallest: the result does not depend on the instance that ran.
+template <int K>
+__global__ __launch_bounds__(kThreads) void knn_search(ovg_radius_params p, RsWs ws, float reach, int32_t k, int32_t* index, float* sqdist) {
+  if (rs_refusal(p, *ws.head)) return;                 // the work guard, the same in every thread: nothing is written
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= (uint32_t)p.nq) return;
+  float q[3];
+  int32_t cnt = 0;
+  uint64_t key[K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) key[t] = kNoneKey;
+  if (rs_point(p.query, p.query_valid, i, q)) {
+    const uint32_t rbits = __float_as_uint(p.radius_sq), nr = (uint32_t)p.nr;
+    const bool exclude = (p.flags & OVG_RS_EXCLUDE_SAME_INDEX) != 0;
+    const RsBox b = rs_box(q, p.origin, p.cell, reach);
+    for (uint32_t cx = b.lo[0]; cx <= b.hi[0]; ++cx)
+      for (uint32_t cy = b.lo[1]; cy <= b.hi[1]; ++cy)
+        for (uint32_t cz = b.lo[2]; cz <= b.hi[2]; ++cz) {
+          uint32_t count, end;
+          if (rs_find(ws, rs_key(cx, cy, cz), count, end) < 0) continue;
+          end = min(end, nr);
+          const uint32_t first = end - min(count, end);
+          for (uint32_t r = first; r < end; ++r) {
+            const u32x4 e = ws.rec[r];
+            const float dx = q[0] - __uint_as_float(e[0]), dy = q[1] - __uint_as_float(e[1]), dz = q[2] - __uint_as_float(e[2]);
+            const float d = (dx * dx + dy * dy) + dz * dz;
+            const uint32_t bits = __float_as_uint(d);
+            const bool ok = bits <= rbits && !(exclude && e[3] == i);
+            uint64_t c = ((uint64_t)bits << 32) | e[3];
+            cnt += ok;
+            if (ok && c < key[K - 1]) {
+#pragma unroll
+              for (int t = 0; t < K; ++t) {
+                const bool below = c < key[t];
+                const uint64_t lo = below ? c : key[t], hi = below ? key[t] : c;
+                key[t] = lo, c = hi;
+              }
+            }
+          }
+        }
+  }
+  p.count[i] = cnt;
+  int32_t* oi = index + (int64_t)i * k;
+  float* od = sqdist + (int64_t)i * k;
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    if (t < k) {
+      const bool found = key[t] != kNoneKey;
+      oi[t] = found ? (int32_t)(uint32_t)key[t] : -1;
+      od[t] = __uint_as_float(found ? (uint32_t)(key[t] >> 32) : kInfBits);
+    }
+  }
+}
+
 bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 unsigned grid_for(int64_t work, int64_t per_block, int64_t cap) {
@@ -376,6 +435,42 @@ extern "C" int ovg_radius_search(const ovg_radius_params* p, void* stream) {
       OVG_LAUNCH(rs_searched, dim3(1), dim3(1), 0, st, *p, ws);
       OVG_CHECK_LAUNCH();
     }
+  }
+  return OVG_OK;
+}
+
+extern "C" int ovg_knn_search(const ovg_knn_params* p, void* stream) {
+  if (!p || !p->query || !p->reference || !p->ws) return OVG_E_ARG;
+  if (!rs_shape_ok(p->nq, p->nr) || (p->flags & ~OVG_RS_EXCLUDE_SAME_INDEX)) return OVG_E_ARG;
+  if (p->k < 1 || p->k > OVG_KNN_MAX_K) return OVG_E_ARG;
+  if ((p->flags & OVG_RS_EXCLUDE_SAME_INDEX) && p->nq != p->nr) return OVG_E_ARG;
+  if (!(p->radius_sq >= kMinRadiusSq) || !isfinite(p->radius_sq)) return OVG_E_ARG;
+  const float reach = rs_reach(p->radius_sq);
+  if (!(p->cell >= reach) || !isfinite(p->cell)) return OVG_E_ARG;
+  if (!p->count || !p->index || !p->sqdist || p->max_pairs < 0) return OVG_E_ARG;
+  if (!al(p->query, 4) || !al(p->reference, 4) || !al(p->origin, 4) || !al(p->count, 4) || !al(p->index, 4) || !al(p->sqdist, 4) ||
+      !al(p->out_stats, 8))
+    return OVG_E_ARG;
+  if (!al(p->ws, 16) || p->ws_bytes < rs_ws_bytes(p->nr)) return OVG_E_ARG;
+  // the search stage of ovg_radius_search over the same workspace: its params carry the grid's description, the guard and count
+  const ovg_radius_params rp = {p->query, p->reference, p->query_valid, p->reference_valid, p->origin, p->nq, p->nr, p->radius_sq, p->cell,
+                                p->flags, OVG_RS_SEARCH, p->max_pairs, p->ws, p->ws_bytes, p->out_stats, p->count, nullptr, nullptr};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const RsWs ws = rs_ws(&rp);
+  const dim3 block(kThreads), per_query((unsigned)((p->nq + kThreads - 1) / kThreads));
+  if (p->k <= 4) {
+    OVG_LAUNCH(knn_search<4>, per_query, block, 0, st, rp, ws, reach, p->k, p->index, p->sqdist);
+  } else if (p->k <= 8) {
+    OVG_LAUNCH(knn_search<8>, per_query, block, 0, st, rp, ws, reach, p->k, p->index, p->sqdist);
+  } else if (p->k <= 16) {
+    OVG_LAUNCH(knn_search<16>, per_query, block, 0, st, rp, ws, reach, p->k, p->index, p->sqdist);
+  } else {
+    OVG_LAUNCH(knn_search<32>, per_query, block, 0, st, rp, ws, reach, p->k, p->index, p->sqdist);
+  }
+  OVG_CHECK_LAUNCH();
+  if (p->out_stats) {
+    OVG_LAUNCH(rs_searched, dim3(1), dim3(1), 0, st, rp, ws);
+    OVG_CHECK_LAUNCH();
   }
   return OVG_OK;
 }

@@ -262,6 +262,21 @@ class RadiusParams(C.Structure):
                 ("out_stats", vp), ("count", vp), ("index", vp), ("sqdist", vp)]
 
 
+KNN_MAX_K = 32                                               # ovg_knn_params.k
+KNN_NORMALS_SWEEPS = 8                                       # Jacobi sweeps of ovg_knn_normals
+
+
+class KnnParams(C.Structure):
+    _fields_ = [("query", vp), ("reference", vp), ("query_valid", vp), ("reference_valid", vp), ("origin", vp), ("nq", i64), ("nr", i64),
+                ("radius_sq", f32), ("cell", f32), ("flags", i32), ("k", i32), ("max_pairs", i64), ("ws", vp), ("ws_bytes", i64),
+                ("out_stats", vp), ("count", vp), ("index", vp), ("sqdist", vp)]
+
+
+class KnnNormalsParams(C.Structure):
+    _fields_ = [("query", vp), ("reference", vp), ("index", vp), ("viewpoint", vp), ("nq", i64), ("nr", i64), ("k", i32),
+                ("viewpoint_stride", i32), ("normal", vp), ("curvature", vp), ("covariance", vp), ("used", vp)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -339,6 +354,8 @@ SYMBOLS = {
     "ovg_fps_workspace_bytes": (i64, [i64, i64, i64]),
     "ovg_radius_search": (i32, [C.POINTER(RadiusParams), vp]),
     "ovg_radius_workspace_bytes": (i64, [i64, i64]),
+    "ovg_knn_search": (i32, [C.POINTER(KnnParams), vp]),
+    "ovg_knn_normals": (i32, [C.POINTER(KnnNormalsParams), vp]),
 }
 
 

@@ -929,3 +929,82 @@ def radius_search(stage, query, reference, radius_sq, cell, ws, query_valid=None
     p.count, p.index, p.sqdist = L.ptr(count), L.ptr(index), L.ptr(sqdist)
     L.call("ovg_radius_search", p, _stream())
     return out_stats, count, index, sqdist
+
+
+def knn_search(query, reference, radius_sq, cell, ws, k, query_valid=None, reference_valid=None, origin=None, exclude_self=False,
+               max_pairs=0, out_stats=None, count=None, index=None, sqdist=None):
+    """ovg_knn_search on contiguous device tensors, with the arguments of radius_search's L.RS_SEARCH stage and 1 <= k <= L.KNN_MAX_K:
+    ws must hold what radius_search(L.RS_BUILD, ...) left there for the same reference, radius_sq, cell and origin. Writes count int32
+    [nq], index int32 [nq, k] and sqdist f32 [nq, k] (allocated when None): the k nearest references within the radius, nearest
+    first, equal distances in ascending index, -1 / +inf from rank min(k, count) on -- or nothing at all when the candidate pairs
+    exceed max_pairs or ws holds no grid, which out_stats (int64 [4], if given) then reports as L.RS_OVER_BUDGET / L.RS_NOT_BUILT.
+    -> (out_stats, count, index, sqdist). Nothing is read back."""
+    _chk_dev(query, reference, ws, query_valid, reference_valid, origin, out_stats, count, index, sqdist)
+    for t, name in ((query, "query"), (reference, "reference")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
+            raise L.OvgError("knn_search: %s must be a contiguous f32 tensor [n, 3]" % name)
+    nq, nr, k = int(query.shape[0]), int(reference.shape[0]), int(k)
+    if not 1 <= k <= L.KNN_MAX_K:
+        raise L.OvgError("knn_search: k must be in [1, %d], got %d" % (L.KNN_MAX_K, k))
+    for v, n, name in ((query_valid, nq, "query_valid"), (reference_valid, nr, "reference_valid")):
+        if v is not None and (v.dtype != torch.uint8 or not v.is_contiguous() or tuple(v.shape) != (n,)):
+            raise L.OvgError("knn_search: %s must be a contiguous u8 tensor [%d]" % (name, n))
+    if origin is not None and (origin.dtype != torch.float32 or not origin.is_contiguous() or origin.numel() != 3):
+        raise L.OvgError("knn_search: origin must be a contiguous f32 tensor of three elements")
+    if exclude_self and nq != nr:
+        raise L.OvgError("knn_search: exclude_self needs nq == nr (got %d, %d)" % (nq, nr))
+    if out_stats is not None and (out_stats.dtype != torch.int64 or out_stats.numel() != 4 or not out_stats.is_contiguous()):
+        raise L.OvgError("knn_search: out_stats must be a contiguous int64 tensor of four elements")
+    count = torch.empty(nq, device=query.device, dtype=torch.int32) if count is None else count
+    index = torch.empty(nq, k, device=query.device, dtype=torch.int32) if index is None else index
+    sqdist = torch.empty(nq, k, device=query.device, dtype=torch.float32) if sqdist is None else sqdist
+    for t, dt, n in ((count, torch.int32, nq), (index, torch.int32, nq * k), (sqdist, torch.float32, nq * k)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise L.OvgError("knn_search: count / index / sqdist must be contiguous int32 [%d] / int32 [%d, %d] / f32 [%d, %d] tensors"
+                             % (nq, nq, k, nq, k))
+    p = L.KnnParams()
+    p.query, p.reference, p.query_valid, p.reference_valid = L.ptr(query), L.ptr(reference), L.ptr(query_valid), L.ptr(reference_valid)
+    p.origin, p.nq, p.nr, p.radius_sq, p.cell = L.ptr(origin), nq, nr, float(radius_sq), float(cell)
+    p.flags, p.k, p.max_pairs = L.RS_EXCLUDE_SAME_INDEX if exclude_self else 0, k, int(max_pairs)
+    p.ws, p.ws_bytes, p.out_stats = L.ptr(ws), nbytes(ws), L.ptr(out_stats)
+    p.count, p.index, p.sqdist = L.ptr(count), L.ptr(index), L.ptr(sqdist)
+    L.call("ovg_knn_search", p, _stream())
+    return out_stats, count, index, sqdist
+
+
+def knn_normals(query, reference, index, viewpoint=None, normal=None, curvature=None, covariance=None, used=None):
+    """ovg_knn_normals on contiguous device tensors: query f32 [nq, 3], reference f32 [nr, 3], index int32 [nq, k] (a neighbour table
+    as knn_search writes it), viewpoint None, f32 [3] (shared) or f32 [nq, 3] (one per query). -> (normal f32 [nq, 3], curvature,
+    covariance, used): the unit normal of the plane through every row's neighbours (zeros where fewer than three), towards the
+    viewpoint. curvature (f32 [nq]), covariance (f64 [nq, 6]: xx xy xz yy yz zz) and used (int32 [nq]: neighbours per row) are
+    written when given as tensors or True (allocated), else returned as None. Nothing is read back."""
+    opt = lambda t: None if isinstance(t, bool) else t
+    _chk_dev(query, reference, index, viewpoint, normal, opt(curvature), opt(covariance), opt(used))
+    for t, name in ((query, "query"), (reference, "reference")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
+            raise L.OvgError("knn_normals: %s must be a contiguous f32 tensor [n, 3]" % name)
+    nq, nr = int(query.shape[0]), int(reference.shape[0])
+    if index.dtype != torch.int32 or not index.is_contiguous() or index.dim() != 2 or index.shape[0] != nq or index.shape[1] < 1:
+        raise L.OvgError("knn_normals: index must be a contiguous int32 tensor [%d, k]" % nq)
+    k = int(index.shape[1])
+    stride = 0
+    if viewpoint is not None:
+        if viewpoint.dtype != torch.float32 or not viewpoint.is_contiguous() or tuple(viewpoint.shape) not in ((3,), (nq, 3)):
+            raise L.OvgError("knn_normals: viewpoint must be a contiguous f32 tensor [3] or [%d, 3]" % nq)
+        stride = 3 if viewpoint.dim() == 2 else 0
+    outs = []
+    for t, shape, dt, name in ((normal, (nq, 3), torch.float32, "normal"), (curvature, (nq,), torch.float32, "curvature"),
+                               (covariance, (nq, 6), torch.float64, "covariance"), (used, (nq,), torch.int32, "used")):
+        if t is True or (t is None and name == "normal"):
+            t = torch.empty(shape, device=query.device, dtype=dt)
+        elif t is False:
+            t = None
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise L.OvgError("knn_normals: %s must be a contiguous %s tensor %r" % (name, dt, shape))
+        outs.append(t)
+    p = L.KnnNormalsParams()
+    p.query, p.reference, p.index, p.viewpoint = L.ptr(query), L.ptr(reference), L.ptr(index), L.ptr(viewpoint)
+    p.nq, p.nr, p.k, p.viewpoint_stride = nq, nr, k, stride
+    p.normal, p.curvature, p.covariance, p.used = (L.ptr(t) for t in outs)
+    L.call("ovg_knn_normals", p, _stream())
+    return tuple(outs)

@@ -562,28 +562,11 @@ def _radius_sq(radius, what="radius"):
     return r2
 
 
-def radius_neighbours(query, reference, radius, query_valid=None, reference_valid=None, exclude_self=False, cell_size=None, origin=None,
-                      max_pairs=None):
-    """For every query point the number of reference points within `radius` and the nearest of them, searched through a uniform hash grid
-    on the device (ovg_radius_search), so that the cost is linear in the clouds for a sensible radius where nearest_neighbours is
-    quadratic. The result is defined WITHOUT the grid, as nearest_neighbours' rule restricted to d <= radius_sq (tests/radius_twin.py
-    restates it by brute force): d = (dx dx + dy dy) + dz dz in float32 without fused multiply-adds, radius_sq = f32(f32(radius)^2),
-    a usable reference is within the radius when d <= radius_sq (inclusive), the nearest is the smallest d, equal distances go to the
-    LOWEST reference index. The grid never changes a byte (DESIGN.md 12f), nor does cell_size or origin; two calls give identical
-    bytes. An unusable query (non-finite coordinates or a zero valid entry), or one with nothing within the radius, gets count 0,
-    index -1, sqdist +inf; a distance that overflows float32 is never within a radius.
-
-    query, reference: float32 device tensors (..., 3), or PointClouds; query_valid / reference_valid: optional bool / uint8 tensors
-    shaped like the points without the last dimension. exclude_self=True searches inside one cloud (equal sizes): point i does not count
-    for itself. cell_size: the grid's cell edge, at least (and by default) the radius plus a rounding margin (ops.radius_reach);
-    origin: three finite floats or a float32 device tensor [3] the grid is anchored at (default zeros) -- both move work, not results.
-    max_pairs: the work budget (default RADIUS_MAX_PAIRS). A radius too large for the cloud would make single threads walk most of it;
-    the grid is built first, the number of candidate pairs (distances the search would evaluate) is read back -- the one device -> host
-    synchronisation -- and a count above the budget raises ValueError before the search is launched.
-
-    -> RadiusResult(count int32, index int32, sqdist float32) shaped like the query's leading dimensions. An empty side returns
-    zeros / -1 / +inf without a launch. CPU tensors raise OvgError (there is no CPU fallback); a bad radius, cell or shape raises
-    ValueError."""
+def _radius_grid(what, query, reference, radius, query_valid, reference_valid, exclude_self, cell_size, origin, max_pairs):
+    """The front half radius_neighbours and knn_neighbours share: the argument checks, the grid of the reference cloud (ops.radius_search,
+    L.RS_BUILD), the one device -> host read of its statistics and the budget's ValueError.
+    -> (lead, device, args, max_pairs): lead the query's leading shape; args the keyword arguments of the search stage over the built
+    grid, or None when a side is empty (nothing was launched)."""
     import math
     L = ops.L
     q, r = _nn_points(query, "query"), _nn_points(reference, "reference")
@@ -619,11 +602,10 @@ def radius_neighbours(query, reference, radius, query_valid=None, reference_vali
         if len(vals) != 3 or not all(math.isfinite(v) and abs(v) <= 3.4028234663852886e38 for v in vals):
             raise ValueError("origin must be three finite float32 numbers, got %r" % (origin,))
     if not all(t is None or t.is_cuda for t in (q, r, qv, rv, org)):
-        raise L.OvgError("radius_neighbours needs HIP device tensors: there is no CPU fallback")
+        raise L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
     dev = q.device
     if nq == 0 or nr == 0:
-        return RadiusResult(torch.zeros(lead, device=dev, dtype=torch.int32), torch.full(lead, -1, device=dev, dtype=torch.int32),
-                            torch.full(lead, float("inf"), device=dev, dtype=torch.float32))
+        return lead, dev, None, max_pairs
     if origin is not None and org is None:
         org = torch.tensor(vals, device=dev, dtype=torch.float32)
     elif org is not None:
@@ -635,13 +617,59 @@ def radius_neighbours(query, reference, radius, query_valid=None, reference_vali
     stats = ops.radius_search(L.RS_BUILD, **args)[0]
     flags, cells, largest, pairs = (int(v) for v in stats.cpu().tolist())   # the one synchronisation
     if flags & L.RS_BAD_ORIGIN:
-        raise ValueError("radius_neighbours: the origin on the device is not finite")
+        raise ValueError("%s: the origin on the device is not finite" % what)
     if pairs > max_pairs:
-        raise ValueError("radius_neighbours: radius %r makes the search evaluate %d candidate pairs, above the budget of %d (max_pairs); "
+        raise ValueError("%s: radius %r makes the search evaluate %d candidate pairs, above the budget of %d (max_pairs); "
                          "the largest of the %d occupied cells holds %d of the %d reference points -- lower the radius, or raise max_pairs "
-                         "knowingly" % (radius, pairs, max_pairs, cells, largest, nr))
-    _, cnt, idx, sq = ops.radius_search(L.RS_SEARCH, max_pairs=max_pairs, **args)
+                         "knowingly" % (what, radius, pairs, max_pairs, cells, largest, nr))
+    return lead, dev, args, max_pairs
+
+
+def radius_neighbours(query, reference, radius, query_valid=None, reference_valid=None, exclude_self=False, cell_size=None, origin=None,
+                      max_pairs=None):
+    """For every query point the number of reference points within `radius` and the nearest of them, searched through a uniform hash grid
+    on the device (ovg_radius_search), so that the cost is linear in the clouds for a sensible radius where nearest_neighbours is
+    quadratic. The result is defined WITHOUT the grid, as nearest_neighbours' rule restricted to d <= radius_sq (tests/radius_twin.py
+    restates it by brute force): d = (dx dx + dy dy) + dz dz in float32 without fused multiply-adds, radius_sq = f32(f32(radius)^2),
+    a usable reference is within the radius when d <= radius_sq (inclusive), the nearest is the smallest d, equal distances go to the
+    LOWEST reference index. The grid never changes a byte (DESIGN.md 12f), nor does cell_size or origin; two calls give identical
+    bytes. An unusable query (non-finite coordinates or a zero valid entry), or one with nothing within the radius, gets count 0,
+    index -1, sqdist +inf; a distance that overflows float32 is never within a radius.
+
+    query, reference: float32 device tensors (..., 3), or PointClouds; query_valid / reference_valid: optional bool / uint8 tensors
+    shaped like the points without the last dimension. exclude_self=True searches inside one cloud (equal sizes): point i does not count
+    for itself. cell_size: the grid's cell edge, at least (and by default) the radius plus a rounding margin (ops.radius_reach);
+    origin: three finite floats or a float32 device tensor [3] the grid is anchored at (default zeros) -- both move work, not results.
+    max_pairs: the work budget (default RADIUS_MAX_PAIRS). A radius too large for the cloud would make single threads walk most of it;
+    the grid is built first, the number of candidate pairs (distances the search would evaluate) is read back -- the one device -> host
+    synchronisation -- and a count above the budget raises ValueError before the search is launched.
+
+    -> RadiusResult(count int32, index int32, sqdist float32) shaped like the query's leading dimensions. An empty side returns
+    zeros / -1 / +inf without a launch. CPU tensors raise OvgError (there is no CPU fallback); a bad radius, cell or shape raises
+    ValueError."""
+    lead, dev, args, max_pairs = _radius_grid("radius_neighbours", query, reference, radius, query_valid, reference_valid, exclude_self,
+                                              cell_size, origin, max_pairs)
+    if args is None:
+        return RadiusResult(torch.zeros(lead, device=dev, dtype=torch.int32), torch.full(lead, -1, device=dev, dtype=torch.int32),
+                            torch.full(lead, float("inf"), device=dev, dtype=torch.float32))
+    _, cnt, idx, sq = ops.radius_search(ops.L.RS_SEARCH, max_pairs=max_pairs, **args)
     return RadiusResult(cnt.reshape(lead), idx.reshape(lead), sq.reshape(lead))
+
+
+def _cloud_radius(what, cloud_or_points, pts, radius, rel_radius):
+    """The radius of a search inside a cloud: `radius` as given, or f32(rel_radius) * scene_scale of a PointCloud in one float32
+    multiply on the host (which reads scene_scale back)."""
+    import math
+    if rel_radius is None:
+        return radius
+    if isinstance(rel_radius, bool) or not isinstance(rel_radius, (int, float)) or not (rel_radius > 0 and math.isfinite(rel_radius)):
+        raise ValueError("rel_radius must be a positive finite number, got %r" % (rel_radius,))
+    if not isinstance(cloud_or_points, PointCloud) or cloud_or_points.scene_scale is None:
+        raise ValueError("rel_radius needs a PointCloud with its scene_scale")
+    _radius_sq(rel_radius, "rel_radius")
+    if not pts.is_cuda:
+        raise ops.L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
+    return _f32(_f32(float(rel_radius)) * float(cloud_or_points.scene_scale.to(torch.float32)))
 
 
 def radius_outlier_mask(cloud_or_points, radius=None, rel_radius=None, min_neighbours=2, valid=None):
@@ -651,22 +679,13 @@ def radius_outlier_mask(cloud_or_points, radius=None, rel_radius=None, min_neigh
     cloud's units) and rel_radius (a PointCloud only: f32(rel_radius) * scene_scale, multiplied on the host) must be given. valid:
     optional bool / uint8 tensor; a point that is not valid or not finite is no neighbour of anything and is itself False.
     -> bool device tensor shaped like the points without the last dimension. Synchronises as radius_neighbours does; errors as there."""
-    import math
     if (radius is None) == (rel_radius is None):
         raise ValueError("radius_outlier_mask: give exactly one of radius and rel_radius")
     if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, int) or min_neighbours < 1:
         raise ValueError("min_neighbours must be a positive integer, got %r" % (min_neighbours,))
     pts = _nn_points(cloud_or_points, "cloud_or_points")
     _nn_valid(valid, tuple(pts.shape[:-1]), "valid")
-    if rel_radius is not None:
-        if isinstance(rel_radius, bool) or not isinstance(rel_radius, (int, float)) or not (rel_radius > 0 and math.isfinite(rel_radius)):
-            raise ValueError("rel_radius must be a positive finite number, got %r" % (rel_radius,))
-        if not isinstance(cloud_or_points, PointCloud) or cloud_or_points.scene_scale is None:
-            raise ValueError("rel_radius needs a PointCloud with its scene_scale")
-        _radius_sq(rel_radius, "rel_radius")
-        if not pts.is_cuda:
-            raise ops.L.OvgError("radius_outlier_mask needs HIP device tensors: there is no CPU fallback")
-        radius = _f32(_f32(float(rel_radius)) * float(cloud_or_points.scene_scale.to(torch.float32)))   # one float32 multiply
+    radius = _cloud_radius("radius_outlier_mask", cloud_or_points, pts, radius, rel_radius)
     res = radius_neighbours(pts, pts, radius, valid, valid, exclude_self=True)
     return res.count >= min_neighbours
 
@@ -678,8 +697,12 @@ def remove_radius_outliers(cloud, radius=None, rel_radius=None, min_neighbours=2
     farthest_point_downsample does. write_ply, write_glb and render_point_cloud accept the result as they are."""
     if not isinstance(cloud, PointCloud):
         raise ValueError("remove_radius_outliers takes a PointCloud")
+    return _gather_cloud(cloud, radius_outlier_mask(cloud, radius=radius, rel_radius=rel_radius, min_neighbours=min_neighbours))
+
+
+def _gather_cloud(cloud, keep):
+    """The points of a PointCloud where the bool mask `keep` is True, in input order."""
     M = len(cloud)
-    keep = radius_outlier_mask(cloud, radius=radius, rel_radius=rel_radius, min_neighbours=min_neighbours)
     idx = torch.nonzero(keep.reshape(-1)).reshape(-1)
     return PointCloud(cloud.points.reshape(M, 3)[idx], None if cloud.colors is None else cloud.colors.reshape(M, 3)[idx],
                       cloud.conf_threshold, cloud.scene_scale, cloud.transform, cloud.extrinsic,
@@ -715,6 +738,169 @@ def cloud_fscore(pred, gt, threshold, max_pairs=None):
     (acc, n_pred, prec), (comp, n_gt, rec) = sides
     return CloudDistance(accuracy=acc, completeness=comp, chamfer=(acc + comp) / 2, n_pred=n_pred, n_gt=n_gt, threshold=float(threshold),
                          precision=prec, recall=rec, fscore=2 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The k nearest neighbours on the same grid: surface normals and the statistical outlier filter (ovg_knn_search, ovg_knn_normals)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+KNN_MAX_K = ops.L.KNN_MAX_K
+
+
+class KNNResult:
+    """Result of knn_neighbours: count int32 (reference points within the radius, shaped like the query without its last dimension:
+    fewer than k were found where count < k), index int32 and sqdist float32 shaped like that plus (k,): the nearest neighbours in
+    ascending distance, -1 / +inf from rank min(k, count) on. Device tensors."""
+    __slots__ = ("count", "index", "sqdist")
+
+    def __init__(self, count, index, sqdist):
+        self.count, self.index, self.sqdist = count, index, sqdist
+
+
+def _knn_k(k):
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError("k must be an integer in [1, %d], got %r" % (KNN_MAX_K, k))
+    return k
+
+
+def knn_neighbours(query, reference, k, radius, query_valid=None, reference_valid=None, exclude_self=False, cell_size=None, origin=None,
+                   max_pairs=None):
+    """For every query point its k nearest reference points among those within `radius` (the hybrid search: Open3D's
+    KDTreeSearchParamHybrid), through the hash grid of radius_neighbours on the device (ovg_knn_search). A radius is REQUIRED: it is
+    what bounds the cells a query visits, and an unbounded k-nearest search is out of scope; `count` tells whether fewer than k were
+    found. The result is defined WITHOUT the grid (tests/knn_twin.py restates it by brute force): with radius_neighbours' float32 d,
+    usable points and inclusive d <= radius_sq, the neighbours of a query are its candidates in ascending order of (d, reference
+    index) -- nearest first, equal distances in ascending index -- so rank 0 is radius_neighbours' index / sqdist, count is its
+    count, and the first k columns of a search with a larger k are the search with k. Two calls give identical bytes; cell_size and
+    origin move work, never a result.
+
+    Arguments, the work budget max_pairs with its one device -> host read and ValueError, and the errors are radius_neighbours';
+    k is an integer in [1, KNN_MAX_K].
+
+    -> KNNResult(count int32 lead, index int32 lead + (k,), sqdist float32 lead + (k,)), lead the query's leading dimensions. An
+    empty side returns zeros / -1 / +inf without a launch."""
+    k = _knn_k(k)
+    lead, dev, args, max_pairs = _radius_grid("knn_neighbours", query, reference, radius, query_valid, reference_valid, exclude_self,
+                                              cell_size, origin, max_pairs)
+    if args is None:
+        return KNNResult(torch.zeros(lead, device=dev, dtype=torch.int32), torch.full(lead + (k,), -1, device=dev, dtype=torch.int32),
+                         torch.full(lead + (k,), float("inf"), device=dev, dtype=torch.float32))
+    _, cnt, idx, sq = ops.knn_search(k=k, max_pairs=max_pairs, **args)
+    return KNNResult(cnt.reshape(lead), idx.reshape(lead + (k,)), sq.reshape(lead + (k,)))
+
+
+def estimate_normals(cloud_or_points, k=16, radius=None, rel_radius=None, viewpoint=None, valid=None, return_curvature=False, image_hw=None):
+    """Surface normals of a cloud on the device: for every point the plane through its k nearest neighbours within the radius
+    (knn_neighbours inside the cloud, the point being its own first neighbour as in Open3D's estimate_normals), by the float64
+    covariance of the neighbours and the eigenvector of its smallest eigenvalue (ovg_knn_normals, include/omnivggt_hip.h). A point
+    with fewer than three neighbours (itself included), and a point that is not valid or not finite, gets the normal (0, 0, 0).
+    Exactly one of radius (in the cloud's units) and rel_radius (a PointCloud only: f32(rel_radius) * scene_scale) must be given, as
+    in radius_outlier_mask; valid: optional bool / uint8 tensor, a point that is not valid is no neighbour of anything.
+    viewpoint: None -- the normal's component of largest magnitude is made positive (deterministic, not a surface orientation);
+    three numbers or a float32 tensor [3] -- every normal points to the half space of that point; a float32 tensor shaped like the
+    points -- one viewpoint per point; "cameras" (a PointCloud with `indices` and `extrinsic`, and image_hw=(H, W) of the prediction
+    maps) -- every point is oriented towards the centre -R^T t of the camera that saw it, view = indices // (H W) (clamped to the
+    cloud's cameras; a cloud of one selected frame uses its one camera), computed on the device.
+    -> float32 device tensor shaped like the points, unit normals; with return_curvature also the surface variation
+    lambda0 / (lambda0 + lambda1 + lambda2) as a float32 tensor without the last dimension (0 on a plane, at most 1/3).
+    Synchronises as radius_neighbours does; errors as there."""
+    import math
+    k = _knn_k(k)
+    if (radius is None) == (rel_radius is None):
+        raise ValueError("estimate_normals: give exactly one of radius and rel_radius")
+    pts = _nn_points(cloud_or_points, "cloud_or_points")
+    lead = tuple(pts.shape[:-1])
+    _nn_valid(valid, lead, "valid")
+    n = pts.numel() // 3
+    view, cams = None, None
+    if isinstance(viewpoint, str):
+        if viewpoint != "cameras":
+            raise ValueError("viewpoint %r: the only named viewpoint is \"cameras\"" % (viewpoint,))
+        c = cloud_or_points
+        if not isinstance(c, PointCloud) or c.indices is None or c.extrinsic is None:
+            raise ValueError("viewpoint=\"cameras\" needs a PointCloud with its indices and extrinsic")
+        if (not isinstance(image_hw, (tuple, list)) or len(image_hw) != 2
+                or not all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in image_hw)):
+            raise ValueError("viewpoint=\"cameras\" needs image_hw=(H, W), two positive integers, got %r" % (image_hw,))
+        if not isinstance(c.extrinsic, torch.Tensor) or c.extrinsic.dim() != 3 or tuple(c.extrinsic.shape[1:]) != (3, 4) or c.extrinsic.shape[0] < 1:
+            raise ValueError("viewpoint=\"cameras\": the cloud's extrinsic must be a tensor (S, 3, 4)")
+        if c.indices.numel() != n:
+            raise ValueError("viewpoint=\"cameras\": the cloud holds %d indices for %d points" % (c.indices.numel(), n))
+        view, cams = c.indices, c.extrinsic
+    elif isinstance(viewpoint, torch.Tensor):
+        if viewpoint.dtype != torch.float32 or (tuple(viewpoint.shape) != (3,) and tuple(viewpoint.shape) != tuple(pts.shape)):
+            raise ValueError("viewpoint must be a float32 tensor [3] or one shaped like the points %r" % (tuple(pts.shape),))
+    elif viewpoint is not None:
+        try:
+            vals = [float(v) for v in viewpoint]
+        except (TypeError, ValueError):
+            raise ValueError("viewpoint must be three finite numbers, a float32 tensor or \"cameras\", got %r" % (viewpoint,)) from None
+        if len(vals) != 3 or not all(math.isfinite(v) and abs(v) <= 3.4028234663852886e38 for v in vals):
+            raise ValueError("viewpoint must be three finite float32 numbers, got %r" % (viewpoint,))
+    radius = _cloud_radius("estimate_normals", cloud_or_points, pts, radius, rel_radius)
+    _radius_sq(radius)
+    if not all(t is None or t.is_cuda for t in (pts, valid, viewpoint if isinstance(viewpoint, torch.Tensor) else None, view, cams)):
+        raise ops.L.OvgError("estimate_normals needs HIP device tensors: there is no CPU fallback")
+    res = knn_neighbours(pts, pts, k, radius, valid, valid)
+    dev = pts.device
+    if n == 0:
+        normal = torch.zeros(lead + (3,), device=dev, dtype=torch.float32)
+        return (normal, torch.zeros(lead, device=dev, dtype=torch.float32)) if return_curvature else normal
+    if view is not None:
+        e = cams.to(torch.float64)
+        centres = (-(e[:, :, :3].transpose(1, 2) @ e[:, :, 3:4]).reshape(-1, 3)).to(torch.float32)      # -R^T t, rounded once
+        v = torch.div(view.reshape(-1), image_hw[0] * image_hw[1], rounding_mode="floor") if centres.shape[0] > 1 else torch.zeros_like(view.reshape(-1))
+        vp = centres[v.clamp(0, centres.shape[0] - 1)].contiguous()
+    elif isinstance(viewpoint, torch.Tensor):
+        vp = viewpoint.reshape(-1, 3).contiguous() if viewpoint.dim() > 1 else viewpoint.contiguous()
+    elif viewpoint is not None:
+        vp = torch.tensor(vals, device=dev, dtype=torch.float32)
+    else:
+        vp = None
+    flat = pts.reshape(n, 3).contiguous()
+    normal, curv, _, _ = ops.knn_normals(flat, flat, res.index.reshape(n, k), viewpoint=vp, curvature=bool(return_curvature))
+    normal = normal.reshape(lead + (3,))
+    return (normal, curv.reshape(lead)) if return_curvature else normal
+
+
+def statistical_outlier_mask(cloud_or_points, k=16, std_ratio=2.0, radius=None, rel_radius=None, valid=None):
+    """Statistical outlier test of a cloud on the device: True where a point's mean distance to its k nearest OTHER points is at most
+    the cloud's mean of that figure plus std_ratio standard deviations. knn_neighbours runs inside the cloud with exclude_self and a
+    radius (exactly one of radius and rel_radius, as in radius_outlier_mask: it bounds the search, choose it a few times the
+    expected spacing). A point with count < k -- fewer than k others within the radius, or not valid, or not finite -- is an outlier
+    and takes no part in the statistics. For the others a_i = the float64 mean of sqrt(float64(sqdist)) over the k ranks,
+    thr = mean(a) + std_ratio * std(a) with the population standard deviation in float64, and the mask is a_i <= thr.
+    Open3D's remove_statistical_outlier counts the point itself among its nb_neighbors (at distance 0), so its nb_neighbors is
+    k + 1 and its mean distance is ours times k / (k + 1); mean and deviation scale alike, so the kept set is the same for the
+    same std_ratio, but for the radius bound, which Open3D's unbounded search does not have.
+    -> bool device tensor shaped like the points without the last dimension. Synchronises as radius_neighbours does; errors as there."""
+    import math
+    k = _knn_k(k)
+    if isinstance(std_ratio, bool) or not isinstance(std_ratio, (int, float)) or not (std_ratio >= 0 and math.isfinite(std_ratio)):
+        raise ValueError("std_ratio must be a non-negative finite number, got %r" % (std_ratio,))
+    if (radius is None) == (rel_radius is None):
+        raise ValueError("statistical_outlier_mask: give exactly one of radius and rel_radius")
+    pts = _nn_points(cloud_or_points, "cloud_or_points")
+    _nn_valid(valid, tuple(pts.shape[:-1]), "valid")
+    radius = _cloud_radius("statistical_outlier_mask", cloud_or_points, pts, radius, rel_radius)
+    res = knn_neighbours(pts, pts, k, radius, valid, valid, exclude_self=True)
+    full = res.count >= k
+    a = res.sqdist.to(torch.float64).sqrt().sum(-1) / k                      # ranks in ascending order; +inf where a row is not full
+    sel = a[full]
+    if sel.numel() == 0:
+        return full
+    mean = sel.mean()
+    thr = mean + float(std_ratio) * ((sel - mean) ** 2).mean().sqrt()
+    return full & (a <= thr)
+
+
+def remove_statistical_outliers(cloud, k=16, std_ratio=2.0, radius=None, rel_radius=None):
+    """A PointCloud without its statistical outliers (statistical_outlier_mask), in input order, gathered as remove_radius_outliers
+    gathers: points, colors and conf at the kept points, `indices` the input cloud's there (or the positions in the input cloud when
+    it has none), everything else passed through. write_ply, write_glb and render_point_cloud accept the result as they are."""
+    if not isinstance(cloud, PointCloud):
+        raise ValueError("remove_statistical_outliers takes a PointCloud")
+    return _gather_cloud(cloud, statistical_outlier_mask(cloud, k=k, std_ratio=std_ratio, radius=radius, rel_radius=rel_radius))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -876,20 +1062,36 @@ def _host_cloud(cloud):
     return pts, col
 
 
-def write_ply(path, cloud, apply_transform=True):
+def write_ply(path, cloud, apply_transform=True, normals=None):
     """Binary little-endian PLY of the cloud: `x y z` float, `red green blue` uchar per vertex. apply_transform: the vertices are
     mapped by cloud.transform in float64 on the host and stored as float32 (as the aligned scene shows them); False stores them as
-    selected. An empty cloud (M = 0) writes a valid file with no vertices."""
+    selected. An empty cloud (M = 0) writes a valid file with no vertices.
+    normals: an optional (M, 3) float32 tensor (estimate_normals); the vertex then carries `nx ny nz` float after `x y z`. Under
+    apply_transform they are mapped by the inverse transpose of the transform's linear part in float64 and renormalised (zero
+    normals stay zero). Without normals the file is the same, byte for byte, as before they existed."""
     import numpy as np
     pts, col = _host_cloud(cloud)
+    nrm = None
+    if normals is not None:
+        if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != (len(pts), 3):
+            raise ValueError("normals must be a float32 tensor (%d, 3)" % len(pts))
+        nrm = normals.detach().cpu().numpy()
     if apply_transform and len(pts):
         T = np.asarray(cloud.transform, dtype=np.float64)
         pts = (pts.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
-    rec = np.empty(len(pts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+        if nrm is not None:
+            n64 = nrm.astype(np.float64) @ np.linalg.inv(T[:3, :3])          # rows n^T A^-1 = (A^-T n)^T
+            length = np.sqrt((n64 * n64).sum(1, keepdims=True))
+            nrm = np.where(length > 0, n64 / np.where(length > 0, length, 1.0), 0.0).astype(np.float32)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if nrm is not None else [])
+    rec = np.empty(len(pts), dtype=fields + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    if nrm is not None:
+        rec["nx"], rec["ny"], rec["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
-    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(pts))
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
+              % (len(pts), "property float nx\nproperty float ny\nproperty float nz\n" if nrm is not None else ""))
     with open(path, "wb") as fh:
         fh.write(header.encode("ascii"))
         fh.write(rec.tobytes())
