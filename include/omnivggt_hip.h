@@ -914,6 +914,97 @@ typedef struct {
 int ovg_knn_normals(const ovg_knn_normals_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Registration of point clouds (added under ABI 13): the least-squares rigid or similarity transform between paired points, as three
+ * entries that never read anything back -- the pair moments, the solve, the transform applied. tests/align_twin.py restates the
+ * moments and the apply operation for operation (byte-identical) and the solve by numpy's eigh and, independently, Umeyama's SVD.
+ *
+ * ovg_align_moments: source p [n][3] f32, target q [m][3] f32; pair i is (p[i], q[j]) with j = index[i] (int32 [n]), or j = i when
+ *   index is NULL (then n == m). Pair i is USED when 0 <= j < m, all six coordinates are finite, source_valid[i] and target_valid[j]
+ *   (u8, optional) are non-zero and, with OVG_ALIGN_GATE, sqdist[i] <= max_sqdist (f32 [n]; inclusive; a NaN on either side is not
+ *   used). centre: NULL or f64 [6] on the device, (cp, cq). Everything in float64, every operation rounded on its own (no fused
+ *   multiply-add): a = p - cp, b = q - cq, d = q - p (from the uncentred values) per coordinate, and the 18 TERMS of a pair
+ *     [0..2] a   [3..5] b   [6 + 3 r + c] a_r b_c   [15] (a0 a0 + a1 a1) + a2 a2   [16] the same of b   [17] the same of d.
+ *   out_count int64 [1]: the number of used pairs; out_sums f64 [18]: the sums of the terms over the used pairs, in THIS order:
+ *   1. tile g holds the pairs [OVG_ALIGN_TILE g, OVG_ALIGN_TILE (g + 1)); thread t of its OVG_ALIGN_THREADS threads adds the terms of
+ *      the pairs t, t + THREADS, t + 2 THREADS, ... of the tile in that order onto +0.0, skipping pairs that are not used or >= n;
+ *   2. inside a wave of 64 lanes v[l] = v[l] + v[l + s] for s = 32, 16, 8, 4, 2, 1 (lane 0 holds the wave's sum);
+ *   3. the four wave sums combine as (w0 + w1) + (w2 + w3): the tile's partial, written to ws;
+ *   4. a second launch of one workgroup folds the partials the same way: thread t adds the partials of the tiles t, t + THREADS, ...
+ *      in that order onto +0.0, then steps 2 and 3.
+ *   The order is part of the rule: no float atomics, no workgroup waits for another (stream order between the two launches is the
+ *   only synchronisation), so two calls give identical bytes. No used pair: count 0 and every sum +0.0.
+ *   ws: >= ovg_align_workspace_bytes(n) bytes, 16-byte aligned: 160 bytes (the count and 18 sums, padded) per tile, rounded up to 256;
+ *   the query returns -1 unless 1 <= n < 2^31.
+ *   OVG_E_ARG: NULL params / source / target / ws / out_count / out_sums, n or m outside [1, 2^31), n != m without an index, unknown
+ *   flags, OVG_ALIGN_GATE without sqdist or with a NaN max_sqdist, a pointer that is not 4-byte (centre, out_count, out_sums: 8-byte)
+ *   aligned, a misaligned or undersized workspace. Nothing is written then.
+ *
+ * ovg_align_solve: one workgroup, one thread: the moments (count int64 [1], sums f64 [18], centre as they were computed with) ->
+ *   the transform q ~ s R p + t that minimises the sum of |q - (s R p + t)|^2 over the used pairs (s = 1 without OVG_ALIGN_SCALE).
+ *   All in float64, N = count:
+ *   1. DEGENERATE when N < 3 (OVG_ALIGN_FEW_PAIRS), a sum or a centre entry is not finite (OVG_ALIGN_NOT_FINITE), or the source has
+ *      no spread: var = sums[15] - |sums[0..2]|^2 / N is not above OVG_ALIGN_SPREAD_EPS (2^-40) sums[15] (OVG_ALIGN_NO_SPREAD: all
+ *      source points coincide, or lie so far from the centre that the subtraction keeps fewer than 12 bits);
+ *   2. S[r][c] = sums[6 + 3 r + c] - sums[r] sums[3 + c] / N, the mean-corrected cross-covariance (times N);
+ *   3. rotation by Horn's quaternion method: the symmetric 4 x 4 matrix
+ *        [ Sxx+Syy+Szz   Syz-Szy        Szx-Sxz        Sxy-Syx      ]
+ *        [               Sxx-Syy-Szz    Sxy+Syx        Szx+Sxz      ]
+ *        [                              -Sxx+Syy-Szz   Syz+Szy      ]
+ *        [                                             -Sxx-Syy+Szz ]
+ *      is diagonalised by OVG_ALIGN_JACOBI_SWEEPS sweeps of cyclic Jacobi rotations (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) (the rotation
+ *      of ovg_knn_normals; a zero entry is skipped); the column of the accumulated rotations under the LARGEST diagonal entry (the
+ *      lowest column on ties), divided by its length, is the unit quaternion (w, x, y, z) of R -- always a proper rotation
+ *      (det +1), also where the best orthogonal fit is a reflection (it then equals Umeyama's reflection-corrected solution);
+ *   4. s = (sum of R[r][c] S[c][r]) / var with OVG_ALIGN_SCALE, else 1; t = (sums[3..5] / N + cq) - s R (sums[0..2] / N + cp);
+ *   5. step = [s R, t; 0 0 0 1]; a step with a non-finite entry is DEGENERATE too (OVG_ALIGN_NOT_FINITE). A degenerate step is the
+ *      identity with scale 1: a NaN is never written to the transform;
+ *   6. transform f64 [4][4] row-major: with OVG_ALIGN_COMPOSE transform <- step transform (read, multiplied, written back: the running
+ *      transform of an iteration), else transform <- step.
+ *   Optional outputs (NULL: not written): out_scale f64 [1] (s of this step), out_rms f64 [1] (sqrt(sums[17] / N): the root mean square
+ *   distance of the used pairs BEFORE the step; 0 when N < 1 or sums[17] is not finite), out_count int64 [1] (N), out_status int32 [1]
+ *   (the OVG_ALIGN_* status bits, 0 for a regular step).
+ *   OVG_E_ARG: NULL params / count / sums / transform, unknown flags, a pointer that is not 8-byte (out_status: 4-byte) aligned.
+ *
+ * ovg_align_apply: out[i][r] = f32(((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3]) for r < 3, (x, y, z) = points[i] widened to
+ *   float64, T the f64 [4][4] transform read from device memory; every operation rounded on its own, one rounding to f32. Non-finite
+ *   points pass through as the arithmetic gives them. points [n][3] f32, out [n][3] f32 (out == points is allowed).
+ *   OVG_E_ARG: NULL params / points / transform / out, n outside [1, 2^31), a pointer that is not 4-byte (transform: 8-byte) aligned.
+ * ------------------------------------------------------------------ */
+enum { OVG_ALIGN_THREADS = 256, OVG_ALIGN_TILE = 1024, OVG_ALIGN_JACOBI_SWEEPS = 12, OVG_ALIGN_SUMS = 18, OVG_ALIGN_PARTIAL_BYTES = 160 };
+enum { OVG_ALIGN_GATE = 1 };                                                         /* ovg_align_moments_params.flags */
+enum { OVG_ALIGN_SCALE = 1, OVG_ALIGN_COMPOSE = 2 };                                 /* ovg_align_solve_params.flags */
+enum { OVG_ALIGN_FEW_PAIRS = 1, OVG_ALIGN_NO_SPREAD = 2, OVG_ALIGN_NOT_FINITE = 4 }; /* out_status */
+#define OVG_ALIGN_SPREAD_EPS 9.094947017729282e-13                                   /* 2^-40 */
+typedef struct {
+  const float* source; const float* target;
+  const int32_t* index;
+  const uint8_t* source_valid; const uint8_t* target_valid;
+  const float* sqdist;
+  const double* centre;
+  int64_t n; int64_t m;
+  float max_sqdist; int32_t flags;
+  void* ws; int64_t ws_bytes;
+  int64_t* out_count; double* out_sums;
+} ovg_align_moments_params;
+int64_t ovg_align_workspace_bytes(int64_t n);
+int ovg_align_moments(const ovg_align_moments_params*, void* stream);
+
+typedef struct {
+  const int64_t* count; const double* sums; const double* centre;
+  int64_t flags;
+  double* transform;
+  double* out_scale; double* out_rms; int64_t* out_count; int32_t* out_status;
+} ovg_align_solve_params;
+int ovg_align_solve(const ovg_align_solve_params*, void* stream);
+
+typedef struct {
+  const float* points; const double* transform;
+  int64_t n;
+  float* out;
+} ovg_align_apply_params;
+int ovg_align_apply(const ovg_align_apply_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do
  * after PIL's convert("RGB"), for all frames of a call in one launch per pass.
  *

@@ -277,6 +277,27 @@ class KnnNormalsParams(C.Structure):
                 ("viewpoint_stride", i32), ("normal", vp), ("curvature", vp), ("covariance", vp), ("used", vp)]
 
 
+ALIGN_THREADS, ALIGN_TILE, ALIGN_JACOBI_SWEEPS, ALIGN_SUMS, ALIGN_PARTIAL_BYTES = 256, 1024, 12, 18, 160   # the order of ovg_align_moments' sums
+ALIGN_GATE = 1                                               # ovg_align_moments_params.flags
+ALIGN_SCALE, ALIGN_COMPOSE = 1, 2                            # ovg_align_solve_params.flags
+ALIGN_FEW_PAIRS, ALIGN_NO_SPREAD, ALIGN_NOT_FINITE = 1, 2, 4 # out_status of ovg_align_solve
+ALIGN_SPREAD_EPS = 2.0 ** -40
+
+
+class AlignMomentsParams(C.Structure):
+    _fields_ = [("source", vp), ("target", vp), ("index", vp), ("source_valid", vp), ("target_valid", vp), ("sqdist", vp), ("centre", vp),
+                ("n", i64), ("m", i64), ("max_sqdist", f32), ("flags", i32), ("ws", vp), ("ws_bytes", i64), ("out_count", vp), ("out_sums", vp)]
+
+
+class AlignSolveParams(C.Structure):
+    _fields_ = [("count", vp), ("sums", vp), ("centre", vp), ("flags", i64), ("transform", vp), ("out_scale", vp), ("out_rms", vp),
+                ("out_count", vp), ("out_status", vp)]
+
+
+class AlignApplyParams(C.Structure):
+    _fields_ = [("points", vp), ("transform", vp), ("n", i64), ("out", vp)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -356,6 +377,10 @@ SYMBOLS = {
     "ovg_radius_workspace_bytes": (i64, [i64, i64]),
     "ovg_knn_search": (i32, [C.POINTER(KnnParams), vp]),
     "ovg_knn_normals": (i32, [C.POINTER(KnnNormalsParams), vp]),
+    "ovg_align_moments": (i32, [C.POINTER(AlignMomentsParams), vp]),
+    "ovg_align_workspace_bytes": (i64, [i64]),
+    "ovg_align_solve": (i32, [C.POINTER(AlignSolveParams), vp]),
+    "ovg_align_apply": (i32, [C.POINTER(AlignApplyParams), vp]),
 }
 
 

@@ -1008,3 +1008,103 @@ def knn_normals(query, reference, index, viewpoint=None, normal=None, curvature=
     p.normal, p.curvature, p.covariance, p.used = (L.ptr(t) for t in outs)
     L.call("ovg_knn_normals", p, _stream())
     return tuple(outs)
+
+
+def align_workspace_bytes(n):
+    if not -(1 << 63) <= int(n) < (1 << 63):
+        raise L.OvgError("ovg_align_workspace_bytes: unsupported (n=%d)" % n)
+    b = L.load().ovg_align_workspace_bytes(int(n))
+    if b < 0:
+        raise L.OvgError("ovg_align_workspace_bytes: unsupported (n=%d)" % n)
+    return int(b)
+
+
+def _align_tensor(what, t, name, dtype, shape, optional=False):
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise L.OvgError("%s: %s must be a contiguous %s tensor %r" % (what, name, dtype, tuple(shape)))
+
+
+def align_moments(source, target, index=None, source_valid=None, target_valid=None, sqdist=None, max_sqdist=None, centre=None, ws=None,
+                  count=None, sums=None):
+    """ovg_align_moments on contiguous device tensors: source f32 [n, 3], target f32 [m, 3], index int32 [n] or None (pair i <-> i, n == m),
+    source_valid / target_valid u8 [n] / [m] or None, sqdist f32 [n] with the host float max_sqdist (both or neither: the inclusive gate),
+    centre f64 [6] (cp, cq) or None. -> (count int64 [1], sums f64 [18]) (allocated when None): the number of used pairs and the float64
+    sums of a, b, a b^T, |a|^2, |b|^2 and |q - p|^2 over them in the fixed order of include/omnivggt_hip.h, so two calls give identical
+    bytes. ws: an optional uint8 device tensor of at least align_workspace_bytes(n) bytes. Nothing is read back."""
+    what = "align_moments"
+    for t, name in ((source, "source"), (target, "target")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise L.OvgError("%s: %s must be a contiguous f32 tensor [n, 3], n >= 1" % (what, name))
+    n, m = int(source.shape[0]), int(target.shape[0])
+    _align_tensor(what, index, "index", torch.int32, (n,), True)
+    if index is None and n != m:
+        raise L.OvgError("%s: without an index the pairs are i <-> i and need n == m (got %d, %d)" % (what, n, m))
+    _align_tensor(what, source_valid, "source_valid", torch.uint8, (n,), True)
+    _align_tensor(what, target_valid, "target_valid", torch.uint8, (m,), True)
+    _align_tensor(what, sqdist, "sqdist", torch.float32, (n,), True)
+    if (sqdist is None) != (max_sqdist is None):
+        raise L.OvgError("%s: the gate needs both sqdist and max_sqdist" % what)
+    if max_sqdist is not None and not float(max_sqdist) == float(max_sqdist):
+        raise L.OvgError("%s: max_sqdist must be a number, not NaN" % what)
+    _align_tensor(what, centre, "centre", torch.float64, (6,), True)
+    _align_tensor(what, count, "count", torch.int64, (1,), True)
+    _align_tensor(what, sums, "sums", torch.float64, (L.ALIGN_SUMS,), True)
+    if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous()):
+        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    _chk_dev(source, target, index, source_valid, target_valid, sqdist, centre, ws, count, sums)
+    need = align_workspace_bytes(n)
+    if ws is None or nbytes(ws) < need:
+        ws = torch.empty(need, device=source.device, dtype=torch.uint8)
+    count = torch.empty(1, device=source.device, dtype=torch.int64) if count is None else count
+    sums = torch.empty(L.ALIGN_SUMS, device=source.device, dtype=torch.float64) if sums is None else sums
+    p = L.AlignMomentsParams()
+    p.source, p.target, p.index, p.source_valid, p.target_valid = L.ptr(source), L.ptr(target), L.ptr(index), L.ptr(source_valid), L.ptr(target_valid)
+    p.sqdist, p.centre, p.n, p.m = L.ptr(sqdist), L.ptr(centre), n, m
+    p.max_sqdist, p.flags = (0.0, 0) if sqdist is None else (float(max_sqdist), L.ALIGN_GATE)
+    p.ws, p.ws_bytes, p.out_count, p.out_sums = L.ptr(ws), nbytes(ws), L.ptr(count), L.ptr(sums)
+    L.call("ovg_align_moments", p, _stream())
+    return count, sums
+
+
+def align_solve(count, sums, transform, centre=None, with_scale=True, compose=False, scale=None, rms=None, out_count=None, status=None):
+    """ovg_align_solve on device tensors: the moments (count int64 [1], sums f64 [18], and the centre f64 [6] they were computed with, or
+    None) -> the least-squares similarity (with_scale) or rigid step q ~ s R p + t, written to transform f64 [4, 4], or multiplied onto
+    it from the left with compose=True. scale f64 [1], rms f64 [1] (of the used pairs before the step), out_count int64 [1] and status
+    int32 [1] (L.ALIGN_FEW_PAIRS | L.ALIGN_NO_SPREAD | L.ALIGN_NOT_FINITE: the step is then the identity) are written when given.
+    -> transform. Nothing is read back."""
+    what = "align_solve"
+    _align_tensor(what, count, "count", torch.int64, (1,))
+    _align_tensor(what, sums, "sums", torch.float64, (L.ALIGN_SUMS,))
+    _align_tensor(what, transform, "transform", torch.float64, (4, 4))
+    _align_tensor(what, centre, "centre", torch.float64, (6,), True)
+    _align_tensor(what, scale, "scale", torch.float64, (1,), True)
+    _align_tensor(what, rms, "rms", torch.float64, (1,), True)
+    _align_tensor(what, out_count, "out_count", torch.int64, (1,), True)
+    _align_tensor(what, status, "status", torch.int32, (1,), True)
+    _chk_dev(count, sums, transform, centre, scale, rms, out_count, status)
+    p = L.AlignSolveParams()
+    p.count, p.sums, p.centre, p.transform = L.ptr(count), L.ptr(sums), L.ptr(centre), L.ptr(transform)
+    p.flags = (L.ALIGN_SCALE if with_scale else 0) | (L.ALIGN_COMPOSE if compose else 0)
+    p.out_scale, p.out_rms, p.out_count, p.out_status = L.ptr(scale), L.ptr(rms), L.ptr(out_count), L.ptr(status)
+    L.call("ovg_align_solve", p, _stream())
+    return transform
+
+
+def align_apply(points, transform, out=None):
+    """ovg_align_apply on contiguous device tensors: points f32 [n, 3], transform f64 [4, 4] -> out f32 [n, 3] (allocated when None; may
+    be `points` itself): out[i] = f32(T p[i]) with every coordinate ((T0 x + T1 y) + T2 z) + T3 in float64. Nothing is read back."""
+    what = "align_apply"
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or \
+            points.shape[1] != 3 or points.shape[0] < 1:
+        raise L.OvgError("%s: points must be a contiguous f32 tensor [n, 3], n >= 1" % what)
+    n = int(points.shape[0])
+    _align_tensor(what, transform, "transform", torch.float64, (4, 4))
+    _align_tensor(what, out, "out", torch.float32, (n, 3), True)
+    _chk_dev(points, transform, out)
+    out = torch.empty(n, 3, device=points.device, dtype=torch.float32) if out is None else out
+    p = L.AlignApplyParams()
+    p.points, p.transform, p.n, p.out = L.ptr(points), L.ptr(transform), n, L.ptr(out)
+    L.call("ovg_align_apply", p, _stream())
+    return out

@@ -904,6 +904,205 @@ def remove_statistical_outliers(cloud, k=16, std_ratio=2.0, radius=None, rel_rad
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# Registration: the similarity / rigid transform between paired points, ICP, aligned scores (ovg_align_moments / _solve / _apply)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+ALIGN_FEW_PAIRS, ALIGN_NO_SPREAD, ALIGN_NOT_FINITE = ops.L.ALIGN_FEW_PAIRS, ops.L.ALIGN_NO_SPREAD, ops.L.ALIGN_NOT_FINITE
+
+
+class Similarity:
+    """A transform q ~ s R p + t between two frames, all on the device: matrix float64 (4, 4) = [s R, t; 0 0 0 1]; scale (0-d float64: s),
+    count (0-d int64: the pairs the last fit used), rms (0-d float64: their root mean square distance BEFORE that fit's step) and status
+    (0-d int32: 0, or ALIGN_FEW_PAIRS | ALIGN_NO_SPREAD | ALIGN_NOT_FINITE when the fit was degenerate and its step the identity)."""
+    __slots__ = ("matrix", "scale", "count", "rms", "status")
+
+    def __init__(self, matrix, scale, count, rms, status):
+        self.matrix, self.scale, self.count, self.rms, self.status = matrix, scale, count, rms, status
+
+    @classmethod
+    def identity(cls, device, status=0):
+        return cls(torch.eye(4, device=device, dtype=torch.float64), torch.ones((), device=device, dtype=torch.float64),
+                   torch.zeros((), device=device, dtype=torch.int64), torch.zeros((), device=device, dtype=torch.float64),
+                   torch.full((), status, device=device, dtype=torch.int32))
+
+    def apply(self, points_or_cloud):
+        """float32(matrix p) for every point (ovg_align_apply: float64 arithmetic, one rounding): a float32 tensor shaped like the input, or
+        for a PointCloud a new cloud with the moved points and every other field carried over."""
+        pts = _nn_points(points_or_cloud, "points_or_cloud")
+        if not (pts.is_cuda and self.matrix.is_cuda):
+            raise ops.L.OvgError("Similarity.apply needs HIP device tensors: there is no CPU fallback")
+        n = pts.numel() // 3
+        out = ops.align_apply(pts.reshape(n, 3).contiguous(), self.matrix.contiguous()).reshape(pts.shape) if n else pts.clone()
+        if isinstance(points_or_cloud, PointCloud):
+            c = points_or_cloud
+            return PointCloud(out, c.colors, c.conf_threshold, c.scene_scale, c.transform, c.extrinsic, c.indices, c.conf)
+        return out
+
+
+class ICPResult:
+    """Result of icp: transform (a Similarity: the final source -> target transform, with the last iteration's count, rms and status and
+    the scale of the whole matrix), and per iteration rms float64, count int64 and status int32 device tensors [iterations]: the used
+    pairs of each iteration and their root mean square distance before that iteration's step."""
+    __slots__ = ("transform", "rms", "count", "status")
+
+    def __init__(self, transform, rms, count, status):
+        self.transform, self.rms, self.count, self.status = transform, rms, count, status
+
+
+def _u8_flat(v):
+    return None if v is None else (v.to(torch.uint8) if v.dtype == torch.bool else v).reshape(-1).contiguous()
+
+
+def _align_step(src, tgt, with_scale, transform, compose, index=None, source_valid=None, target_valid=None, sqdist=None, max_sqdist=None,
+                scale=None, rms=None, count=None, status=None):
+    """Two moment passes and the solve for contiguous [n, 3] / [m, 3] device tensors: the first pass without a centre gives the means of
+    the used pairs, the second is centred on them (so no sum loses the cloud's extent against its offset), the solve adds them back."""
+    kw = dict(index=index, source_valid=source_valid, target_valid=target_valid, sqdist=sqdist, max_sqdist=max_sqdist)
+    ws = torch.empty(ops.align_workspace_bytes(src.shape[0]), device=src.device, dtype=torch.uint8)
+    n0, s0 = ops.align_moments(src, tgt, ws=ws, **kw)
+    centre = s0[:6] / n0.clamp_min(1).to(torch.float64)
+    n1, s1 = ops.align_moments(src, tgt, centre=centre, ws=ws, **kw)
+    return ops.align_solve(n1, s1, transform, centre=centre, with_scale=with_scale, compose=compose, scale=scale, rms=rms, out_count=count,
+                           status=status)
+
+
+def fit_similarity(source, target, source_valid=None, target_valid=None, with_scale=True):
+    """The least-squares similarity (with_scale=True: Umeyama's Sim(3) fit) or rigid transform that takes `source` onto `target`, point i
+    onto point i, on the device: the float64 moments of the pairs summed in a fixed order (ovg_align_moments: two calls give the same
+    bytes), first about the origin, then about the means of the first pass, and Horn's quaternion solve (ovg_align_solve), which
+    always returns a proper rotation -- for mirrored clouds the reflection-corrected Umeyama solution. A pair is used when its six
+    coordinates are finite and its valid entries (if given) are non-zero.
+
+    source, target: float32 device tensors (..., 3) with the same number of points, or PointClouds; source_valid / target_valid:
+    optional bool / uint8 tensors shaped like the points without the last dimension. -> Similarity. Fewer than three used pairs, a
+    source without spread or a non-finite sum give the identity with `status` set, never a NaN. No device -> host synchronisation.
+    CPU tensors raise OvgError (there is no CPU fallback); bad shapes or dtypes raise ValueError; empty sides return the identity with
+    count 0 and ALIGN_FEW_PAIRS."""
+    a, b = _nn_points(source, "source"), _nn_points(target, "target")
+    sv = _nn_valid(source_valid, tuple(a.shape[:-1]), "source_valid")
+    tv = _nn_valid(target_valid, tuple(b.shape[:-1]), "target_valid")
+    n, m = a.numel() // 3, b.numel() // 3
+    if n != m:
+        raise ValueError("fit_similarity pairs point i with point i: source and target must hold the same number of points (%d, %d)" % (n, m))
+    if not all(t is None or t.is_cuda for t in (a, b, sv, tv)):
+        raise ops.L.OvgError("fit_similarity needs HIP device tensors: there is no CPU fallback")
+    out = Similarity.identity(a.device, ALIGN_FEW_PAIRS)
+    if n == 0:
+        return out
+    scale, rms, count, status = (torch.empty(1, device=a.device, dtype=d) for d in (torch.float64, torch.float64, torch.int64, torch.int32))
+    _align_step(a.reshape(n, 3).contiguous(), b.reshape(n, 3).contiguous(), bool(with_scale), out.matrix, False, source_valid=_u8_flat(sv),
+                target_valid=_u8_flat(tv), scale=scale, rms=rms, count=count, status=status)
+    return Similarity(out.matrix, scale[0], count[0], rms[0], status[0])
+
+
+def _align_init(init):
+    """The matrix of icp's `init` (None: none), checked."""
+    m = init.matrix if isinstance(init, Similarity) else init
+    if m is not None and (not isinstance(m, torch.Tensor) or m.dtype != torch.float64 or tuple(m.shape) != (4, 4)):
+        raise ValueError("init must be None, a Similarity or a float64 tensor (4, 4)")
+    return m
+
+
+def icp(source, target, init=None, iterations=20, max_distance=None, with_scale=False, search="exhaustive"):
+    """Point-to-point ICP on the device: `iterations` times, the source is moved by the running transform (ovg_align_apply), every moved
+    point finds its nearest target point, the moments of those pairs -- gated at f32(f32(max_distance)^2) on the search's float32 squared
+    distance, inclusive -- give the rigid (with_scale=True: similarity) step as in fit_similarity, and the step is multiplied onto the
+    running float64 transform on the device. The iteration count is fixed: nothing is tested on the host, and an iteration that is left
+    with fewer than three pairs is an identity step with its status set.
+    search="exhaustive" uses nearest_neighbours (quadratic; max_distance may be None: no gate) and the whole loop runs without a device
+    -> host synchronisation. search="grid" uses radius_neighbours with radius max_distance (required), linear in the clouds for a sensible
+    radius; it builds the grid anew and reads the grid's statistics back ONCE PER ITERATION, as every radius_neighbours call does, and
+    raises that function's ValueError when the radius is too large for its work budget. Both searches return the same pairs wherever
+    the nearest point lies within max_distance.
+    source, target: float32 device tensors (..., 3) or PointClouds; init: None (identity), a Similarity or a float64 device tensor
+    (4, 4). -> ICPResult. CPU tensors raise OvgError; bad arguments raise ValueError; an empty side returns `init` with zero counts and
+    ALIGN_FEW_PAIRS in every iteration."""
+    a, b = _nn_points(source, "source"), _nn_points(target, "target")
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+        raise ValueError("iterations must be a positive integer, got %r" % (iterations,))
+    if search not in ("exhaustive", "grid"):
+        raise ValueError("search must be 'exhaustive' or 'grid', got %r" % (search,))
+    if max_distance is None:
+        if search == "grid":
+            raise ValueError("search='grid' needs max_distance: it is the radius of the search")
+        max_sq = None
+    else:
+        max_sq = _radius_sq(max_distance, "max_distance")
+    T = _align_init(init)
+    if not (a.is_cuda and b.is_cuda and (T is None or T.is_cuda)):
+        raise ops.L.OvgError("icp needs HIP device tensors: there is no CPU fallback")
+    dev = a.device
+    T = torch.eye(4, device=dev, dtype=torch.float64) if T is None else T.clone().contiguous()
+    n, m = a.numel() // 3, b.numel() // 3
+    rms = torch.zeros(iterations, device=dev, dtype=torch.float64)
+    count = torch.zeros(iterations, device=dev, dtype=torch.int64)
+    status = torch.full((iterations,), ALIGN_FEW_PAIRS, device=dev, dtype=torch.int32)
+    scale = torch.empty(1, device=dev, dtype=torch.float64)
+    if n and m:
+        src, tgt = a.reshape(n, 3).contiguous(), b.reshape(m, 3).contiguous()
+        moved = torch.empty_like(src)
+        for it in range(iterations):
+            ops.align_apply(src, T, out=moved)
+            if search == "exhaustive":
+                index, sqdist = ops.nearest_neighbours(moved, tgt)
+            else:
+                res = radius_neighbours(moved, tgt, max_distance)
+                index, sqdist = res.index, res.sqdist
+            _align_step(moved, tgt, bool(with_scale), T, True, index=index, sqdist=None if max_sq is None else sqdist, max_sqdist=max_sq,
+                        scale=scale, rms=rms[it:it + 1], count=count[it:it + 1], status=status[it:it + 1])
+    total = torch.linalg.vector_norm(T[:3, 0])
+    return ICPResult(Similarity(T, total, count[-1], rms[-1], status[-1]), rms, count, status)
+
+
+def aligned_cloud_distance(pred_points, gt_points, valid=None, threshold=None, with_scale=True, icp_iterations=0, max_distance=None):
+    """The scores of cloud_distance after the alignment they presuppose: a fit_similarity over corresponding points (pixel i of the
+    predicted point map against pixel i of the ground truth; with_scale=True is the Sim(3) Umeyama fit), optionally refined by
+    `icp_iterations` rigid ICP iterations (exhaustive search, gated at max_distance when given), then cloud_distance of the moved
+    prediction against the ground truth. valid: optional bool / uint8 tensor shaped like the points without the last dimension: only
+    those pixels are fitted and scored (selecting them synchronises once, as cloud_distance's own read does at the end).
+    pred_points, gt_points: float32 device tensors (..., 3) with the same number of points. -> (CloudDistance, Similarity)."""
+    a, b = _nn_points(pred_points, "pred_points"), _nn_points(gt_points, "gt_points")
+    if a.numel() != b.numel():
+        raise ValueError("aligned_cloud_distance pairs point i with point i: %d predicted, %d ground-truth points" % (a.numel() // 3, b.numel() // 3))
+    v = _nn_valid(valid, tuple(a.shape[:-1]), "valid")
+    if isinstance(icp_iterations, bool) or not isinstance(icp_iterations, int) or icp_iterations < 0:
+        raise ValueError("icp_iterations must be a non-negative integer, got %r" % (icp_iterations,))
+    if not all(t is None or t.is_cuda for t in (a, b, v)):
+        raise ops.L.OvgError("aligned_cloud_distance needs HIP device tensors: there is no CPU fallback")
+    a, b = a.reshape(-1, 3), b.reshape(-1, 3)
+    if v is not None:
+        keep = v.reshape(-1) != 0
+        a, b = a[keep], b[keep]
+    sim = fit_similarity(a, b, with_scale=with_scale)
+    if icp_iterations:
+        sim = icp(a, b, init=sim, iterations=icp_iterations, max_distance=max_distance, with_scale=False).transform
+    return cloud_distance(sim.apply(a), b, threshold=threshold), sim
+
+
+def trajectory_ate(pred_extrinsic, gt_extrinsic, with_scale=True):
+    """Absolute trajectory error of predicted cameras against ground truth after the alignment evo's align(correct_scale=True) makes:
+    the camera centres -R^T t of the world-to-camera matrices (float64 on the device, rounded to float32 for the fit), a fit_similarity
+    of the predicted centres onto the true ones (with_scale=False: rigid), and the root mean square distance of the moved centres in
+    float64. pred_extrinsic, gt_extrinsic: float32 / float64 device tensors (S, 3, 4) or (S, 4, 4) with the same S.
+    -> (ate_rms 0-d float64 device tensor, Similarity). Nothing is read back."""
+    cs = []
+    for e, name in ((pred_extrinsic, "pred_extrinsic"), (gt_extrinsic, "gt_extrinsic")):
+        if not isinstance(e, torch.Tensor) or e.dim() != 3 or tuple(e.shape[1:]) not in ((3, 4), (4, 4)) or e.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s must be a float32 / float64 tensor (S, 3, 4) or (S, 4, 4)" % name)
+        cs.append(e)
+    if cs[0].shape[0] != cs[1].shape[0]:
+        raise ValueError("trajectory_ate pairs camera i with camera i: %d predicted, %d ground-truth cameras" % (cs[0].shape[0], cs[1].shape[0]))
+    if not (cs[0].is_cuda and cs[1].is_cuda):
+        raise ops.L.OvgError("trajectory_ate needs HIP device tensors: there is no CPU fallback")
+    cp, cg = (-(e[:, :3, :3].double().transpose(1, 2) @ e[:, :3, 3:].double()).squeeze(-1) for e in cs)
+    sim = fit_similarity(cp.float(), cg.float(), with_scale=with_scale)
+    if cp.shape[0] == 0:
+        return torch.full((), float("nan"), device=cp.device, dtype=torch.float64), sim
+    moved = cp @ sim.matrix[:3, :3].T + sim.matrix[:3, 3]
+    return ((moved - cg) ** 2).sum(1).mean().sqrt(), sim
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # Farthest-point sampling: a fixed number of well-spread points (ovg_farthest_point_sample)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
