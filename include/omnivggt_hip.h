@@ -64,7 +64,8 @@ extern "C" {
  *     + farthest-point sampling of point clouds (ovg_farthest_point_sample, ovg_fps_workspace_bytes): added the same way
  *     + radius neighbour search on a hash grid (ovg_radius_search, ovg_radius_workspace_bytes): added the same way
  *     + k nearest neighbours within a radius on that grid, and PCA normals from the table (ovg_knn_search, ovg_knn_normals): added
- *       the same way */
+ *       the same way
+ *     + clustering on that grid: Euclidean connected components and DBSCAN (ovg_cluster): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -879,6 +880,63 @@ typedef struct {
   int32_t* count; int32_t* index; float* sqdist;
 } ovg_knn_params;
 int ovg_knn_search(const ovg_knn_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Clustering of a point cloud (added under ABI 13), on the grid ovg_radius_search builds: which points belong together -- Euclidean
+ * connected components, and DBSCAN with a deterministic border rule. Defined WITHOUT the grid and without the union-find;
+ * tests/cluster_twin.py restates it by brute force. One cloud points [n][3] f32, valid [n] u8 optional (NULL: all valid), radius_sq,
+ * min_neighbours >= 0:
+ *   1. USABLE and d = (dx dx + dy dy) + dz dz are those of ovg_radius_search: f32, one rounding per operation. d is symmetric bit for
+ *      bit (fl(a - b)^2 == fl(b - a)^2);
+ *   2. i and j are NEIGHBOURS when both are usable, i != j and bits(d) <= bits(radius_sq) (inclusive);
+ *   3. degree[i] (int32) = the number of neighbours of i: the count ovg_radius_search writes with OVG_RS_EXCLUDE_SAME_INDEX; 0 for an
+ *      unusable point;
+ *   4. CORE: usable and degree[i] >= min_neighbours. With min_neighbours = 0 every usable point is core and the result is the
+ *      plain Euclidean connected components (Open3D's cluster_dbscan counts the point itself: its min_points is min_neighbours + 1);
+ *   5. the clusters are the connected components of the graph whose vertices are the core points and whose edges are the neighbour
+ *      pairs of core points; root[i] (int32) of a core point is the LOWEST index in its component;
+ *   6. BORDER: usable, not core, with at least one core neighbour: it joins the cluster of the core neighbour j that minimises
+ *      (bits(d), j) -- the nearest core point, equal distances to the lowest index -- root[i] = root[j]. (Classic DBSCAN leaves a
+ *      border point between two clusters to the visiting order; this rule does not);
+ *   7. NOISE: every other usable point; UNUSABLE: the rest. Both: root -1;
+ *   8. kind[i] (u8) = OVG_CL_UNUSABLE / OVG_CL_NOISE / OVG_CL_BORDER / OVG_CL_CORE.
+ * A search only: it reads the grid ovg_radius_search(stage = OVG_RS_BUILD) left in ws for query == reference == points, the same
+ * valid on both sides, and the same radius_sq, cell and origin (ws_bytes >= ovg_radius_workspace_bytes(n, n)); with the walk of
+ * OVG_RS_SEARCH over the same box the grid never changes a byte of this either. No further workspace: `root` is the union-find's
+ * parent array while the launches run (one word of ws's header carries OVG_CL_INTERNAL between them). One launch per pass, one
+ * point per thread in workgroups of OVG_RS_QUERY_BLOCK, the kernel boundary the only ordering between passes:
+ *   degree   the walk, counting: degree, kind (CORE, or NOISE for what border decides later), parent = i for a core point, else -1;
+ *   link     every core i unites itself with each core neighbour j < i. Lock-free union-find: parent[x] <= x, a slot only ever
+ *            decreases, every value stored in parent[x] is a member of x's component; a hook is a 32-bit compare-and-swap that makes a
+ *            root point to a smaller root (on failure: retry from the value returned), paths are halved through an atomic min
+ *            with an ancestor. Hence the final root is the component's lowest index whatever the schedule. Every access to the
+ *            parent array is a relaxed agent-scope atomic; no thread waits for a value another workgroup must produce;
+ *   flatten  root[i] = find(i) for the core points;
+ *   border   every usable non-core i takes the minimum of (bits(d), j) over its core neighbours: root[i] = root[j] and BORDER, or NOISE.
+ *   A record's index j is followed only when j < n. Every device loop has a hard trip bound (2 n steps suffice, 4 n + 4 are
+ *   allowed); an overrun or a parent outside [0, x] raises OVG_CL_INTERNAL in out_stats[0] and ends the thread: root / kind are
+ *   then not a result. Integer atomics only; nothing is allocated or read back.
+ * WORK GUARD and OVG_RS_NOT_BUILT as in ovg_knn_search: nothing is written to root / kind / degree when the candidate pairs BUILD
+ * counted exceed max_pairs or ws holds no BUILD of this n; out_stats int64[4] (optional) reports as it does there.
+ *   root [n] int32, kind [n] u8, degree [n] int32 (optional, NULL: not written).
+ *   OVG_E_ARG: NULL params / points / ws / root / kind, n outside [1, 2^31), radius_sq not finite or < 2^-100, cell not finite or
+ *   < REACH, flags != 0 (none is defined), min_neighbours < 0, max_pairs < 0, a pointer that is not 4-byte (out_stats: 8-byte)
+ *   aligned (points, origin, root, degree), a misaligned or undersized workspace.
+ * ------------------------------------------------------------------ */
+enum { OVG_CL_UNUSABLE = 0, OVG_CL_NOISE = 1, OVG_CL_BORDER = 2, OVG_CL_CORE = 3 };       /* kind */
+enum { OVG_CL_INTERNAL = 8 };                                                          /* out_stats[0], next to the OVG_RS_ flags */
+typedef struct {
+  const float* points; const uint8_t* valid;
+  const float* origin;
+  int64_t n;
+  float radius_sq; float cell;
+  int32_t min_neighbours; int32_t flags;
+  int64_t max_pairs;
+  void* ws; int64_t ws_bytes;
+  int64_t* out_stats;
+  int32_t* root; uint8_t* kind; int32_t* degree;
+} ovg_cluster_params;
+int ovg_cluster(const ovg_cluster_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * PCA normals from a neighbour table (added under ABI 13): for every query the normal of the plane through the reference points

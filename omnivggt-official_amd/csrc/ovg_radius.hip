@@ -5,6 +5,7 @@
 // into cell order, and a cost pass that sums the cell counts of every query's box. SEARCH: one query per thread walks its box of
 // cells and runs the exact rule over each cell's records. The box covers every candidate for any cell edge and origin (header), so
 // the grid changes the cost and never a byte. The table is bound by random 64-bit atomics, the search by its gather of records.
+// ovg_knn_search and ovg_cluster (connected components / DBSCAN: a lock-free union-find over the neighbour pairs) walk the same grid.
 #include <math.h>
 #include "ovg_common.h"
 
@@ -23,7 +24,8 @@ constexpr uint64_t kNoneKey = ~0ull;                   // above every (bits(d) <
 constexpr float kCellLo = -1048576.0f, kCellHi = 1048575.0f;   // -2^20, 2^20 - 1
 constexpr float kMinRadiusSq = 0x1p-100f;
 
-struct RsHead { uint32_t flags, max_cell; uint64_t occupied, pairs; int64_t nr; };   // nr: 0 after the clear, the cloud's once BUILD is through
+// nr: 0 after the clear, the cloud's once BUILD is through; cl_flags: ovg_cluster's own (OVG_CL_INTERNAL), the one word a search writes
+struct RsHead { uint32_t flags, max_cell; uint64_t occupied, pairs; int64_t nr; uint32_t cl_flags; };
 struct RsSlot { uint64_t key; uint32_t count, end; };  // end: the cell's first record after the scan, one past its last after the scatter
 struct RsWs { RsHead* head; RsSlot* table; int64_t nslots; u32x4* rec; uint32_t* tile; int64_t ntiles; };
 
@@ -122,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void rs_clear(RsWs ws) {
   u32x4* tab = reinterpret_cast<u32x4*>(ws.table);
   const u32x4 empty = {0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u};
   for (int64_t i = t0; i < ws.nslots; i += step) tab[i] = empty;
-  if (t0 == 0) *ws.head = {0u, 0u, 0ull, 0ull, 0ll};
+  if (t0 == 0) *ws.head = {0u, 0u, 0ull, 0ull, 0ll, 0u};
 }
 
 // every usable reference claims the slot of its cell and counts itself
@@ -382,6 +384,162 @@ __global__ __launch_bounds__(kThreads) void knn_search(ovg_radius_params p, RsWs
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// ovg_cluster: connected components / DBSCAN over the grid (the rule: include/omnivggt_hip.h). Four launches, the kernel boundary the
+// only ordering between them: degree (rs_search's walk, counting; kind and the parent array), link (a lock-free union-find over the
+// neighbour pairs of core points), flatten (root = find), border (non-core points join their nearest core neighbour's cluster).
+// `root` IS the union-find's parent array while the launches run.
+//
+// The union-find. parent[x] of a core point x, read and written in cl_link / cl_flatten ONLY through relaxed agent-scope atomics (a
+// plain load may be served from a CU's L1 or another XCD's L2 and go stale). Writes are of two kinds: a HOOK, the 32-bit
+// compare-and-swap parent[hi]: hi -> lo with lo < hi, and a HALVING, the atomic min of parent[x] with a value read from parent[parent[x]].
+// Invariants, by induction over the writes in the order the memory system performs them on each slot (cl_degree left parent[x] = x):
+//   (a) parent[x] <= x. A hook stores lo < hi; a min never raises a slot.
+//   (b) a slot only ever decreases: a hook replaces hi by lo < hi, a min is a min.
+//   (c) every value ever stored in parent[x] is a member of x's component (of the graph of rule 5). A hook stores lo, a point reached
+//       by following parents from b, where a, b are neighbours and hi was reached from a: by (c) for the slots followed, lo ~ b ~ a ~ hi.
+//       A halving stores a value once held by parent[p], p once held by parent[x]: a member of p's component, which is x's.
+//   (d) the parents form a forest: a non-root slot holds a strictly smaller index, so following parents descends and ends, after at most
+//       x steps, at an r with parent[r] == r; a hook succeeds only on a slot that still holds its own index, a root at that instant,
+//       and so hangs hi's whole tree under lo: under the root of another tree, or (when lo has been hooked itself since it was
+//       read) under an inner node of one -- one tree fewer either way; a halving moves x under a former ancestor g, which by (b)
+//       and (d) is still in x's tree. Trees only ever merge.
+// After cl_link has ended every neighbour pair of core points is in one tree: cl_unite returns only after a successful hook between
+// the two trees or after both walks ended at the same root. With (c) the trees are exactly the components, and by (a) along the path
+// a tree's root is <= every member and is a member: the component's LOWEST index, whatever the schedule.
+// Termination: nothing waits. cl_find descends by at least one index per step. A failed compare-and-swap returns the slot's new
+// value, < hi by (a) and (b): another thread's hook or halving made progress, and this thread's cursor moves down to that value. So
+// the two cursors of a cl_unite only move down from a0, b0 < n: find steps plus failed swaps < 2 n, and the step budget 4 n + 4
+// (every outer round spends at least two steps) is never met by correct code. A value outside [0, x], or a spent budget, sets
+// OVG_CL_INTERNAL and leaves: a bug ends as an error, never as a hang, and no index outside [0, n) is ever followed.
+OVG_DEV int32_t cl_ld(int32_t* a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x's tree at some instant during the call, halving the path on the way; -1 on a broken invariant or a spent budget
+OVG_DEV int32_t cl_find(int32_t* parent, int32_t x, uint64_t& budget) {
+  while (budget) {
+    --budget;
+    const int32_t p = cl_ld(parent + x);
+    if (p == x) return x;
+    if ((uint32_t)p > (uint32_t)x) return -1;
+    const int32_t g = cl_ld(parent + p);
+    if ((uint32_t)g > (uint32_t)p) return -1;
+    if (g != p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = p;
+  }
+  return -1;
+}
+
+OVG_DEV bool cl_unite(int32_t* parent, int32_t a, int32_t b, uint64_t budget) {
+  for (;;) {
+    a = cl_find(parent, a, budget);
+    b = cl_find(parent, b, budget);
+    if ((a | b) < 0) return false;
+    if (a == b) return true;
+    const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+    int32_t seen = hi;
+    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return true;
+    if ((uint32_t)seen >= (uint32_t)hi) return false;
+    a = seen, b = lo;                                  // hi is no root any more: go on from what it points to now
+  }
+}
+
+// rs_search's walk over the box of point i of the one cloud: visit(bits(d), j) for every neighbour record (rule 2: j != i)
+template <class Visit>
+OVG_DEV void cl_walk(const ovg_radius_params& p, const RsWs& ws, float reach, uint32_t i, const float (&q)[3], Visit&& visit) {
+  const uint32_t rbits = __float_as_uint(p.radius_sq), nr = (uint32_t)p.nr;
+  const RsBox b = rs_box(q, p.origin, p.cell, reach);
+  for (uint32_t cx = b.lo[0]; cx <= b.hi[0]; ++cx)
+    for (uint32_t cy = b.lo[1]; cy <= b.hi[1]; ++cy)
+      for (uint32_t cz = b.lo[2]; cz <= b.hi[2]; ++cz) {
+        uint32_t count, end;
+        if (rs_find(ws, rs_key(cx, cy, cz), count, end) < 0) continue;
+        end = min(end, nr);
+        const uint32_t first = end - min(count, end);
+        for (uint32_t r = first; r < end; ++r) {
+          const u32x4 e = ws.rec[r];
+          const float dx = q[0] - __uint_as_float(e[0]), dy = q[1] - __uint_as_float(e[1]), dz = q[2] - __uint_as_float(e[2]);
+          const float d = (dx * dx + dy * dy) + dz * dz;
+          const uint32_t bits = __float_as_uint(d);
+          if (bits <= rbits && e[3] != i) visit(bits, e[3]);
+        }
+      }
+}
+
+OVG_DEV void cl_fail(const RsWs& ws) {
+  __hip_atomic_fetch_or(&ws.head->cl_flags, (uint32_t)OVG_CL_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// degree, kind (CORE, or NOISE for a usable point not yet decided: cl_border raises it to BORDER) and parent (i for a core point)
+__global__ __launch_bounds__(kThreads) void cl_degree(ovg_radius_params p, RsWs ws, float reach, int32_t min_neighbours, int32_t* root,
+                                                      uint8_t* kind, int32_t* degree) {
+  if (rs_refusal(p, *ws.head)) return;                 // the work guard, the same in every thread: nothing is written
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i == 0) ws.head->cl_flags = 0u;                  // no thread of this launch raises it
+  if (i >= (uint32_t)p.nr) return;
+  float q[3];
+  int32_t cnt = 0;
+  const bool usable = rs_point(p.query, p.query_valid, i, q);
+  if (usable) cl_walk(p, ws, reach, i, q, [&](uint32_t, uint32_t) { ++cnt; });
+  const bool core = usable && cnt >= min_neighbours;
+  root[i] = core ? (int32_t)i : -1;
+  kind[i] = (uint8_t)(!usable ? OVG_CL_UNUSABLE : (core ? OVG_CL_CORE : OVG_CL_NOISE));
+  if (degree) degree[i] = cnt;
+}
+
+// every core i unites itself with every core neighbour j < i (the relation is symmetric bit for bit: the pair is met from its
+// higher end). kind is read plainly: cl_degree wrote it in an earlier launch and nothing writes it here
+__global__ __launch_bounds__(kThreads) void cl_link(ovg_radius_params p, RsWs ws, float reach, int32_t* parent, const uint8_t* kind) {
+  if (rs_refusal(p, *ws.head)) return;
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x, n = (uint32_t)p.nr;
+  float q[3];
+  if (i >= n || kind[i] != OVG_CL_CORE || !rs_point(p.query, p.query_valid, i, q)) return;
+  const uint64_t budget = 4ull * n + 4;
+  bool fine = true;
+  cl_walk(p, ws, reach, i, q, [&](uint32_t, uint32_t j) {
+    // a record's index is followed here: one from a workspace another call has scribbled over must not leave the arrays
+    if (j < i && kind[j] == OVG_CL_CORE && fine) fine = cl_unite(parent, (int32_t)i, (int32_t)j, budget);
+  });
+  if (!fine) cl_fail(ws);
+}
+
+// root[i] = find(i) for the core points. No hook runs in this launch, so the roots are final: the min stores the tree's root
+__global__ __launch_bounds__(kThreads) void cl_flatten(ovg_radius_params p, RsWs ws, int32_t* parent, const uint8_t* kind) {
+  if (rs_refusal(p, *ws.head)) return;
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x, n = (uint32_t)p.nr;
+  if (i >= n || kind[i] != OVG_CL_CORE) return;
+  uint64_t budget = 4ull * n + 4;
+  const int32_t r = cl_find(parent, (int32_t)i, budget);
+  if (r < 0) { cl_fail(ws); return; }
+  __hip_atomic_fetch_min(parent + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// every usable non-core i joins the core neighbour that minimises (bits(d), j), or stays NOISE. root and kind of CORE points are
+// final and read plainly; a thread writes only its own non-core entries, and a reader that meets NOISE or BORDER there sees "not
+// CORE" either way
+__global__ __launch_bounds__(kThreads) void cl_border(ovg_radius_params p, RsWs ws, float reach, int32_t* root, uint8_t* kind) {
+  if (rs_refusal(p, *ws.head)) return;
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x, n = (uint32_t)p.nr;
+  float q[3];
+  if (i >= n || kind[i] != OVG_CL_NOISE || !rs_point(p.query, p.query_valid, i, q)) return;
+  uint64_t best = kNoneKey;
+  cl_walk(p, ws, reach, i, q, [&](uint32_t bits, uint32_t j) {
+    const uint64_t key = ((uint64_t)bits << 32) | j;
+    if (j < n && key < best && kind[j] == OVG_CL_CORE) best = key;
+  });
+  if (best == kNoneKey) return;
+  root[i] = root[(uint32_t)best];
+  kind[i] = (uint8_t)OVG_CL_BORDER;
+}
+
+__global__ void cl_done(ovg_radius_params p, RsWs ws) {
+  const RsHead& h = *ws.head;
+  const uint32_t no = rs_refusal(p, h);
+  p.out_stats[0] = (int64_t)(no == OVG_RS_NOT_BUILT ? no : (h.flags | no | (no ? 0u : h.cl_flags)));
+  p.out_stats[1] = no == OVG_RS_NOT_BUILT ? 0 : (int64_t)h.occupied;
+  p.out_stats[2] = no == OVG_RS_NOT_BUILT ? 0 : (int64_t)h.max_cell;
+  p.out_stats[3] = no == OVG_RS_NOT_BUILT ? 0 : (int64_t)h.pairs;
+}
+
 bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 unsigned grid_for(int64_t work, int64_t per_block, int64_t cap) {
@@ -470,6 +628,36 @@ extern "C" int ovg_knn_search(const ovg_knn_params* p, void* stream) {
   OVG_CHECK_LAUNCH();
   if (p->out_stats) {
     OVG_LAUNCH(rs_searched, dim3(1), dim3(1), 0, st, rp, ws);
+    OVG_CHECK_LAUNCH();
+  }
+  return OVG_OK;
+}
+
+extern "C" int ovg_cluster(const ovg_cluster_params* p, void* stream) {
+  if (!p || !p->points || !p->ws) return OVG_E_ARG;
+  if (!rs_shape_ok(p->n, p->n) || p->flags != 0 || p->min_neighbours < 0) return OVG_E_ARG;
+  if (!(p->radius_sq >= kMinRadiusSq) || !isfinite(p->radius_sq)) return OVG_E_ARG;
+  const float reach = rs_reach(p->radius_sq);
+  if (!(p->cell >= reach) || !isfinite(p->cell)) return OVG_E_ARG;
+  if (!p->root || !p->kind || p->max_pairs < 0) return OVG_E_ARG;
+  if (!al(p->points, 4) || !al(p->origin, 4) || !al(p->root, 4) || !al(p->degree, 4) || !al(p->out_stats, 8)) return OVG_E_ARG;
+  if (!al(p->ws, 16) || p->ws_bytes < rs_ws_bytes(p->n)) return OVG_E_ARG;
+  // the search stage of ovg_radius_search inside one cloud over the same workspace: its params carry the grid's description and the guard
+  const ovg_radius_params rp = {p->points, p->points, p->valid, p->valid, p->origin, p->n, p->n, p->radius_sq, p->cell,
+                                OVG_RS_EXCLUDE_SAME_INDEX, OVG_RS_SEARCH, p->max_pairs, p->ws, p->ws_bytes, p->out_stats, nullptr, nullptr, nullptr};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const RsWs ws = rs_ws(&rp);
+  const dim3 block(kThreads), per_point((unsigned)((p->n + kThreads - 1) / kThreads));
+  OVG_LAUNCH(cl_degree, per_point, block, 0, st, rp, ws, reach, p->min_neighbours, p->root, p->kind, p->degree);
+  OVG_CHECK_LAUNCH();
+  OVG_LAUNCH(cl_link, per_point, block, 0, st, rp, ws, reach, p->root, p->kind);
+  OVG_CHECK_LAUNCH();
+  OVG_LAUNCH(cl_flatten, per_point, block, 0, st, rp, ws, p->root, p->kind);
+  OVG_CHECK_LAUNCH();
+  OVG_LAUNCH(cl_border, per_point, block, 0, st, rp, ws, reach, p->root, p->kind);
+  OVG_CHECK_LAUNCH();
+  if (p->out_stats) {
+    OVG_LAUNCH(cl_done, dim3(1), dim3(1), 0, st, rp, ws);
     OVG_CHECK_LAUNCH();
   }
   return OVG_OK;

@@ -272,6 +272,16 @@ class KnnParams(C.Structure):
                 ("out_stats", vp), ("count", vp), ("index", vp), ("sqdist", vp)]
 
 
+CL_UNUSABLE, CL_NOISE, CL_BORDER, CL_CORE = 0, 1, 2, 3           # ovg_cluster's kind
+CL_INTERNAL = 8                                              # out_stats[0] of ovg_cluster, next to the RS_ flags
+
+
+class ClusterParams(C.Structure):
+    _fields_ = [("points", vp), ("valid", vp), ("origin", vp), ("n", i64), ("radius_sq", f32), ("cell", f32), ("min_neighbours", i32),
+                ("flags", i32), ("max_pairs", i64), ("ws", vp), ("ws_bytes", i64), ("out_stats", vp), ("root", vp), ("kind", vp),
+                ("degree", vp)]
+
+
 class KnnNormalsParams(C.Structure):
     _fields_ = [("query", vp), ("reference", vp), ("index", vp), ("viewpoint", vp), ("nq", i64), ("nr", i64), ("k", i32),
                 ("viewpoint_stride", i32), ("normal", vp), ("curvature", vp), ("covariance", vp), ("used", vp)]
@@ -377,6 +387,7 @@ SYMBOLS = {
     "ovg_radius_workspace_bytes": (i64, [i64, i64]),
     "ovg_knn_search": (i32, [C.POINTER(KnnParams), vp]),
     "ovg_knn_normals": (i32, [C.POINTER(KnnNormalsParams), vp]),
+    "ovg_cluster": (i32, [C.POINTER(ClusterParams), vp]),
     "ovg_align_moments": (i32, [C.POINTER(AlignMomentsParams), vp]),
     "ovg_align_workspace_bytes": (i64, [i64]),
     "ovg_align_solve": (i32, [C.POINTER(AlignSolveParams), vp]),

@@ -972,6 +972,45 @@ def knn_search(query, reference, radius_sq, cell, ws, k, query_valid=None, refer
     return out_stats, count, index, sqdist
 
 
+def cluster(points, radius_sq, cell, ws, min_neighbours, valid=None, origin=None, max_pairs=0, out_stats=None, root=None, kind=None,
+            degree=None):
+    """ovg_cluster on contiguous device tensors: points f32 [n, 3], valid u8 [n] or None, origin f32 [3] or None; min_neighbours >= 0
+    (0: plain Euclidean connected components). ws must hold what radius_search(L.RS_BUILD, points, points, ..., query_valid=valid,
+    reference_valid=valid) left there for the same radius_sq, cell and origin. Writes root int32 [n] (the lowest index of the point's
+    cluster, -1 for noise and unusable points), kind u8 [n] (L.CL_UNUSABLE / CL_NOISE / CL_BORDER / CL_CORE) and degree int32 [n]
+    (the neighbours within the radius, the point itself not counted) -- allocated when None; degree=False: not written -- or nothing
+    at all when the candidate pairs exceed max_pairs or ws holds no grid, which out_stats (int64 [4], if given) then reports as
+    L.RS_OVER_BUDGET / L.RS_NOT_BUILT; L.CL_INTERNAL there means the union-find broke its own bounds (a bug: no result).
+    -> (out_stats, root, kind, degree). Nothing is read back."""
+    deg = None if isinstance(degree, bool) else degree
+    _chk_dev(points, ws, valid, origin, out_stats, root, kind, deg)
+    if points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3:
+        raise L.OvgError("cluster: points must be a contiguous f32 tensor [n, 3]")
+    n = int(points.shape[0])
+    if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, int) or not 0 <= min_neighbours < 1 << 31:
+        raise L.OvgError("cluster: min_neighbours must be an integer in [0, 2^31), got %r" % (min_neighbours,))
+    if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or tuple(valid.shape) != (n,)):
+        raise L.OvgError("cluster: valid must be a contiguous u8 tensor [%d]" % n)
+    if origin is not None and (origin.dtype != torch.float32 or not origin.is_contiguous() or origin.numel() != 3):
+        raise L.OvgError("cluster: origin must be a contiguous f32 tensor of three elements")
+    if out_stats is not None and (out_stats.dtype != torch.int64 or out_stats.numel() != 4 or not out_stats.is_contiguous()):
+        raise L.OvgError("cluster: out_stats must be a contiguous int64 tensor of four elements")
+    root = torch.empty(n, device=points.device, dtype=torch.int32) if root is None else root
+    kind = torch.empty(n, device=points.device, dtype=torch.uint8) if kind is None else kind
+    if degree is None or degree is True:
+        deg = torch.empty(n, device=points.device, dtype=torch.int32)
+    for t, dt in ((root, torch.int32), (kind, torch.uint8), (deg, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise L.OvgError("cluster: root / kind / degree must be contiguous int32 / u8 / int32 tensors [%d]" % n)
+    p = L.ClusterParams()
+    p.points, p.valid, p.origin, p.n, p.radius_sq, p.cell = L.ptr(points), L.ptr(valid), L.ptr(origin), n, float(radius_sq), float(cell)
+    p.min_neighbours, p.flags, p.max_pairs = min_neighbours, 0, int(max_pairs)
+    p.ws, p.ws_bytes, p.out_stats = L.ptr(ws), nbytes(ws), L.ptr(out_stats)
+    p.root, p.kind, p.degree = L.ptr(root), L.ptr(kind), L.ptr(deg)
+    L.call("ovg_cluster", p, _stream())
+    return out_stats, root, kind, deg
+
+
 def knn_normals(query, reference, index, viewpoint=None, normal=None, curvature=None, covariance=None, used=None):
     """ovg_knn_normals on contiguous device tensors: query f32 [nq, 3], reference f32 [nr, 3], index int32 [nq, k] (a neighbour table
     as knn_search writes it), viewpoint None, f32 [3] (shared) or f32 [nq, 3] (one per query). -> (normal f32 [nq, 3], curvature,

@@ -904,6 +904,144 @@ def remove_statistical_outliers(cloud, k=16, std_ratio=2.0, radius=None, rel_rad
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# Clustering on the same grid: Euclidean connected components and DBSCAN, "keep the main structure" (ovg_cluster)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+CL_UNUSABLE, CL_NOISE, CL_BORDER, CL_CORE = ops.L.CL_UNUSABLE, ops.L.CL_NOISE, ops.L.CL_BORDER, ops.L.CL_CORE
+
+
+class ClusterResult:
+    """Result of cluster_points. Shaped like the points without their last dimension, device tensors: labels int32 (the dense cluster
+    number, -1 for noise and unusable points), kind uint8 (CL_UNUSABLE / CL_NOISE / CL_BORDER / CL_CORE), root int32 (the lowest
+    point index of the point's cluster, -1 where labels is -1) and degree int32 (the other points within the radius). Per cluster,
+    in label order: roots int32 [C] and sizes int64 [C] (core and border points). num_clusters: C, a host int."""
+    __slots__ = ("labels", "kind", "root", "degree", "roots", "sizes", "num_clusters")
+
+    def __init__(self, labels, kind, root, degree, roots, sizes, num_clusters):
+        self.labels, self.kind, self.root, self.degree = labels, kind, root, degree
+        self.roots, self.sizes, self.num_clusters = roots, sizes, num_clusters
+
+
+def _min_neighbours(min_neighbours):
+    if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, int) or not 0 <= min_neighbours < 1 << 31:
+        raise ValueError("min_neighbours must be a non-negative integer, got %r" % (min_neighbours,))
+    return min_neighbours
+
+
+def cluster_points(cloud_or_points, radius=None, rel_radius=None, min_neighbours=0, valid=None, order="size", cell_size=None, origin=None,
+                   max_pairs=None):
+    """Which points of a cloud belong together, on the device (ovg_cluster over the hash grid of radius_neighbours): Euclidean
+    connected components (min_neighbours = 0) or DBSCAN. The result is defined WITHOUT the grid and without the union-find that
+    computes it (tests/cluster_twin.py restates it by brute force), with radius_neighbours' float32 d, usable points and inclusive
+    d <= radius_sq: two usable points are neighbours when they are within the radius of each other; a point with at least
+    min_neighbours OTHER points within the radius is a core point (Open3D's cluster_dbscan counts the point itself: its min_points is
+    min_neighbours + 1); the clusters are the connected components of the core points under the neighbour relation; a usable point
+    that is not core but has a core neighbour is a border point and joins the cluster of its NEAREST core neighbour, equal distances
+    going to the lowest index (classic DBSCAN leaves this to the visiting order; here two calls, and any schedule, give identical
+    bytes); every other usable point is noise. A cluster is named by its lowest point index (`root`).
+
+    Exactly one of radius (in the cloud's units) and rel_radius (a PointCloud only: f32(rel_radius) * scene_scale) must be given, as
+    in radius_outlier_mask. valid: optional bool / uint8 tensor; a point that is not valid or not finite is no neighbour of anything.
+    order: "size" (default) numbers the clusters by descending size, equal sizes by ascending root, so label 0 is the largest
+    cluster; "index" numbers them by ascending root. cell_size, origin and max_pairs are radius_neighbours': they move work, never a
+    result, and the budget's one device -> host read and ValueError are the same (the dense labels read the number of clusters back
+    as well).
+
+    -> ClusterResult. An empty cloud returns empty results without a launch. CPU tensors raise OvgError (there is no CPU fallback);
+    a bad radius, cell, order or shape raises ValueError."""
+    if (radius is None) == (rel_radius is None):
+        raise ValueError("cluster_points: give exactly one of radius and rel_radius")
+    min_neighbours = _min_neighbours(min_neighbours)
+    if order not in ("size", "index"):
+        raise ValueError("order must be \"size\" or \"index\", got %r" % (order,))
+    pts = _nn_points(cloud_or_points, "cloud_or_points")
+    _nn_valid(valid, tuple(pts.shape[:-1]), "valid")
+    radius = _cloud_radius("cluster_points", cloud_or_points, pts, radius, rel_radius)
+    lead, dev, args, max_pairs = _radius_grid("cluster_points", pts, pts, radius, valid, valid, True, cell_size, origin, max_pairs)
+    if args is None:
+        none = torch.full(lead, -1, device=dev, dtype=torch.int32)
+        return ClusterResult(none, torch.zeros(lead, device=dev, dtype=torch.uint8), none.clone(), torch.zeros(lead, device=dev, dtype=torch.int32),
+                             torch.zeros(0, device=dev, dtype=torch.int32), torch.zeros(0, device=dev, dtype=torch.int64), 0)
+    stats = torch.zeros(4, device=dev, dtype=torch.int64)
+    _, root, kind, degree = ops.cluster(args["query"], args["radius_sq"], args["cell"], args["ws"], min_neighbours, valid=args["query_valid"],
+                                        origin=args["origin"], max_pairs=max_pairs, out_stats=stats)
+    member = root >= 0
+    roots, inverse, sizes = torch.unique(root[member], return_inverse=True, return_counts=True)       # ascending root
+    if int(stats[0]) & ops.L.CL_INTERNAL:
+        raise ops.L.OvgError("cluster_points: the union-find left its bounds (OVG_CL_INTERNAL): no result")
+    if order == "size":
+        by_size = torch.sort(sizes, descending=True, stable=True).indices                            # equal sizes: ascending root
+        rank = torch.empty_like(by_size)
+        rank[by_size] = torch.arange(by_size.numel(), device=dev)
+        roots, sizes, inverse = roots[by_size], sizes[by_size], rank[inverse]
+    labels = torch.full_like(root, -1)
+    labels[member] = inverse.to(torch.int32)
+    return ClusterResult(labels.reshape(lead), kind.reshape(lead), root.reshape(lead), degree.reshape(lead), roots, sizes.to(torch.int64),
+                         int(roots.numel()))
+
+
+def _cluster_result(result):
+    if not isinstance(result, ClusterResult):
+        raise ValueError("expected the ClusterResult of cluster_points")
+    return result
+
+
+def largest_cluster_mask(result):
+    """True at the points (core and border) of the largest cluster of a ClusterResult, equal sizes going to the lowest root; all
+    False when there is no cluster. -> bool tensor shaped like result.labels."""
+    res = _cluster_result(result)
+    if res.num_clusters == 0:
+        return torch.zeros_like(res.labels, dtype=torch.bool)
+    top = res.roots[res.sizes == res.sizes.max()].min()                          # whatever the order of the labels
+    return res.root == top
+
+
+def cluster_size_mask(result, min_size):
+    """True at the points of the clusters of a ClusterResult that hold at least min_size points (core and border); noise and unusable
+    points are False. -> bool tensor shaped like result.labels."""
+    res = _cluster_result(result)
+    if isinstance(min_size, bool) or not isinstance(min_size, int) or min_size < 1:
+        raise ValueError("min_size must be a positive integer, got %r" % (min_size,))
+    if res.num_clusters == 0:
+        return torch.zeros_like(res.labels, dtype=torch.bool)
+    return (res.labels >= 0) & (res.sizes[res.labels.clamp_min(0).long()] >= min_size)
+
+
+def remove_small_clusters(cloud, radius=None, rel_radius=None, min_size=None, keep_largest=None, min_neighbours=0):
+    """A PointCloud without its detached islands, in input order: the points of the clusters (cluster_points) with at least min_size
+    points, or with keep_largest=True the largest cluster alone -- the floater islands that radius_outlier_mask and
+    statistical_outlier_mask pass, because inside an island every point has neighbours. Exactly one of min_size / keep_largest and
+    exactly one of radius / rel_radius must be given. Gathered as remove_radius_outliers gathers: points, colors and conf at the
+    kept points, `indices` the input cloud's there (or the positions in the input cloud when it has none), everything else passed
+    through. write_ply, write_glb and render_point_cloud accept the result as they are."""
+    if not isinstance(cloud, PointCloud):
+        raise ValueError("remove_small_clusters takes a PointCloud")
+    if keep_largest is not None and not isinstance(keep_largest, bool):
+        raise ValueError("keep_largest must be True, False or None, got %r" % (keep_largest,))
+    if (min_size is None) == (not keep_largest):
+        raise ValueError("remove_small_clusters: give exactly one of min_size and keep_largest")
+    if min_size is not None and (isinstance(min_size, bool) or not isinstance(min_size, int) or min_size < 1):
+        raise ValueError("min_size must be a positive integer, got %r" % (min_size,))
+    res = cluster_points(cloud, radius=radius, rel_radius=rel_radius, min_neighbours=min_neighbours)
+    return _gather_cloud(cloud, largest_cluster_mask(res) if keep_largest else cluster_size_mask(res, min_size))
+
+
+def cluster_colors(labels):
+    """A colour per cluster label for write_ply, write_glb and render_point_cloud: uint8 [..., 3] from an integer tensor of labels, a
+    fixed integer hash of the label (the same label is the same colour in every call, channels in [56, 255]); noise (a negative
+    label) is grey (128, 128, 128). A few torch integer operations on the labels' device."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError("labels must be an int32 / int64 tensor")
+    h = ((labels.to(torch.int64) + 1) * 2654435761) & 0xFFFFFFFF
+    h = ((h ^ (h >> 15)) * 0x2C1B3C6D) & 0xFFFFFFFF
+    h = ((h ^ (h >> 12)) * 0x297A2D39) & 0xFFFFFFFF
+    h = h ^ (h >> 15)
+    rgb = torch.stack([h & 255, (h >> 8) & 255, (h >> 16) & 255], -1)
+    rgb = 56 + ((rgb * 200) >> 8)
+    return torch.where((labels < 0).unsqueeze(-1), torch.full_like(rgb, 128), rgb).to(torch.uint8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # Registration: the similarity / rigid transform between paired points, ICP, aligned scores (ovg_align_moments / _solve / _apply)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
