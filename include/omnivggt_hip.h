@@ -65,7 +65,9 @@ extern "C" {
  *     + radius neighbour search on a hash grid (ovg_radius_search, ovg_radius_workspace_bytes): added the same way
  *     + k nearest neighbours within a radius on that grid, and PCA normals from the table (ovg_knn_search, ovg_knn_normals): added
  *       the same way
- *     + clustering on that grid: Euclidean connected components and DBSCAN (ovg_cluster): added the same way */
+ *     + clustering on that grid: Euclidean connected components and DBSCAN (ovg_cluster): added the same way
+ *     + plane segmentation by RANSAC (ovg_plane_hypotheses, ovg_plane_score, ovg_plane_select, ovg_plane_mask, ovg_plane_fit): added
+ *       the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -1061,6 +1063,122 @@ typedef struct {
   float* out;
 } ovg_align_apply_params;
 int ovg_align_apply(const ovg_align_apply_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Plane segmentation by RANSAC (added under ABI 13): five entries that never read anything back -- seeded hypotheses, their inlier
+ * counts over the whole cloud (the hot path: H hypotheses x n points), the winner, its inlier mask, and a least-squares refit from
+ * the moments of ovg_align_moments. The rule names no schedule; tests/plane_twin.py restates it in numpy by brute force and the
+ * device returns its bytes (the refit: within a bound, against numpy's eigh).
+ *
+ * A PLANE is four float32 values (nx, ny, nz, w) with |n| = 1; its points satisfy n.p + w = 0. The VOID plane is four NaNs.
+ * RESIDUAL of a point (x, y, z), in float32 with every operation rounded on its own (no fused multiply-add):
+ *     e = ((nx x + ny y) + nz z) + w
+ * A point is USABLE when its valid byte (u8 [n], optional) is non-zero and its three coordinates are finite. It is an INLIER of a
+ * plane at the threshold t (float32, finite, >= 0) iff it is usable and |e| <= t (inclusive). A NaN e is never an inlier, so the
+ * void plane has none; neither has a plane with an infinite value.
+ *
+ * ovg_plane_hypotheses: one thread per hypothesis h < H.
+ *   DRAWS: pos_j = ((mix(seed + 3 h + j) >> 32) * m) >> 32 for j = 0, 1, 2 in unsigned 64-bit arithmetic that wraps, mix = splitmix64:
+ *     z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31
+ *   (mix(0) = 0xE220A8397B1DCDAF). m is the number of candidates: the point index is i_j = candidates[pos_j] (int32 [m]), or pos_j
+ *   itself without a candidate list (then m = n). index int32 [H][3] receives (i_0, i_1, i_2) as drawn, also for void hypotheses.
+ *   PLANE: float64, one rounding per operation, a, b, c the points i_0, i_1, i_2 widened: u = b - a, v = c - a,
+ *   n = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0), l2 = (n0 n0 + n1 n1) + n2 n2, uu and vv the same of u and v. The hypothesis
+ *   is VOID when an index is outside [0, n), two indices are equal, a point is not usable, l2 is not above (2^-20 uu) vv (a
+ *   near-collinear triple: the sine of the angle at a is at most 2^-10) or, with an axis (f32 [3] on the device, used as given: the
+ *   caller normalises it), |d| >= min_abs_cos does not hold for d = (nh0 a0 + nh1 a1) + nh2 a2, nh = n / sqrt(l2) per component
+ *   (a NaN axis voids every hypothesis). Otherwise nh is ORIENTED: with an axis and d != 0 so that d > 0; without one, or at
+ *   d == 0, so that its component of largest magnitude is positive, the lowest component on ties (ovg_knn_normals' rule);
+ *   w = -((nh0 a0 + nh1 a1) + nh2 a2) with the oriented nh and the point a; the four values are rounded to float32 once.
+ *   planes f32 [H][4]: the plane, or four NaNs (bits 0x7FC00000) for a void hypothesis.
+ *   OVG_E_ARG: NULL params / points / planes / index, n or H outside [1, 2^31), with candidates m outside [1, 2^31), without m != n
+ *   and m != 0, min_abs_cos outside [0, 1] or NaN (it must be 0 without an axis), a pointer that is not 4-byte aligned.
+ *
+ * ovg_plane_score: count int32 [H] = the number of inliers of planes[h] among the n points. A grid of (hypothesis tiles of
+ *   OVG_PLANE_HYP_TILE) x (point splits); a workgroup keeps its planes and counters in registers, stages tiles of
+ *   OVG_PLANE_POINT_TILE points in LDS (an unusable point as NaN) and every split adds its counters with one 32-bit integer atomic
+ *   add per hypothesis onto the zeros a fill launch of the same call wrote. Integer sums do not depend on the order of arrival: two
+ *   calls, and every `splits` (0: chosen by the entry; otherwise the number of point splits, clamped to the number of point
+ *   tiles), give identical bytes.
+ *   OVG_E_ARG: NULL params / points / planes / count, n or H outside [1, 2^31), threshold negative, infinite or NaN, splits < 0,
+ *   a pointer that is not 4-byte aligned.
+ *
+ * ovg_plane_select: one workgroup. The WINNER is the hypothesis with the largest count, ties to the lowest h. There is NO PLANE when
+ *   that count is below min_inliers (>= 3) or the winner's plane holds a non-finite value: best = -1, plane = four zeros and
+ *   status = OVG_PLANE_NONE; otherwise best = h, plane = planes[h], status = 0. best_count receives the largest count either way
+ *   (a negative count is read as 0). A NaN is never written to `plane`.
+ *   OVG_E_ARG: NULL params / count / planes / best / plane / best_count / status, H outside [1, 2^31), min_inliers < 3, a pointer
+ *   that is not 4-byte aligned.
+ *
+ * ovg_plane_mask: inlier u8 [n] (1 / 0) for the plane read from device memory (f32 [4]); distance (f32 [n], optional): the signed
+ *   residual e, NaN (0x7FC00000) for an unusable point; out_count int64 [1]: the number of inliers, summed with integer atomics
+ *   onto a zero the call writes itself. gate (int32 [1], optional): when it holds OVG_PLANE_NONE there is no plane -- no inlier,
+ *   every distance NaN, count 0 -- whatever `plane` holds (ovg_plane_select's zeros would make every usable point an inlier).
+ *   OVG_E_ARG: NULL params / points / plane / inlier / out_count, n outside [1, 2^31), a bad threshold, a pointer that is not
+ *   4-byte (out_count: 8-byte) aligned.
+ *
+ * ovg_plane_fit: one thread: the least-squares plane through the inliers from their moments (count int64 [1], sums f64 [18],
+ *   centre f64 [6] or NULL for zeros: ovg_align_moments with source == target == the points, source_valid = the inlier mask and
+ *   centre = (g0, g0), so that a == b bit for bit). All float64, N = count:
+ *   1. DEGENERATE when N < 3 (OVG_PLANE_FEW) or a sum or centre entry is not finite (OVG_PLANE_NOT_FINITE);
+ *   2. C[r][c] = sums[6 + 3 r + c] - (sums[r] sums[c]) / N for r <= c: the scatter matrix of the inliers (their covariance times N);
+ *      the centroid g[r] = sums[r] / N + centre[r];
+ *   3. ovg_knn_normals' cyclic Jacobi: OVG_KNN_NORMALS_SWEEPS sweeps of the rotations (0,1) (0,2) (1,2); the column of the
+ *      accumulated rotations under the smallest diagonal entry, the lowest on ties, divided by its length;
+ *   4. DEGENERATE when the middle diagonal entry is not above 2^-40 times the largest (OVG_PLANE_NO_SPREAD: the inliers are
+ *      collinear or coincide), or when the new plane holds a non-finite value (OVG_PLANE_NOT_FINITE);
+ *   5. oriented as a hypothesis is (d from the axis f32 [3] when given; no min_abs_cos here), w = -((nh0 g0 + nh1 g1) + nh2 g2),
+ *      rounded to float32 once and written over `plane`. A degenerate step leaves `plane` as it was.
+ *   Optional outputs: out_rms f64 [1] = sqrt(max(smallest entry, 0) / N), the root mean square distance of the inliers to the new
+ *   plane; out_eigen f64 [3], the diagonal entries ascending (both zeros for a degenerate step); status int32 [1], the OVG_PLANE_FEW
+ *   / NO_SPREAD / NOT_FINITE bits of this step, 0 for a regular one.
+ *   OVG_E_ARG: NULL params / count / sums / plane, a pointer that is not 8-byte (plane, axis, status: 4-byte) aligned.
+ * Nothing is written when an entry returns OVG_E_ARG.
+ * ------------------------------------------------------------------ */
+enum { OVG_PLANE_HYP_TILE = 512, OVG_PLANE_POINT_TILE = 512 };
+enum { OVG_PLANE_NONE = 1, OVG_PLANE_FEW = 2, OVG_PLANE_NO_SPREAD = 4, OVG_PLANE_NOT_FINITE = 8 };   /* status bits */
+#define OVG_PLANE_COLLINEAR_EPS 9.5367431640625e-07                                  /* 2^-20 */
+#define OVG_PLANE_SPREAD_EPS 9.094947017729282e-13                                   /* 2^-40 */
+typedef struct {
+  const float* points; const uint8_t* valid;
+  const int32_t* candidates; const float* axis;
+  int64_t n; int64_t m; int64_t H;
+  uint64_t seed;
+  float min_abs_cos; int32_t pad;
+  float* planes; int32_t* index;
+} ovg_plane_hypotheses_params;
+int ovg_plane_hypotheses(const ovg_plane_hypotheses_params*, void* stream);
+
+typedef struct {
+  const float* points; const uint8_t* valid; const float* planes;
+  int64_t n; int64_t H;
+  float threshold; int32_t splits;
+  int32_t* count;
+} ovg_plane_score_params;
+int ovg_plane_score(const ovg_plane_score_params*, void* stream);
+
+typedef struct {
+  const int32_t* count; const float* planes;
+  int64_t H;
+  int32_t min_inliers; int32_t pad;
+  int32_t* best; float* plane; int32_t* best_count; int32_t* status;
+} ovg_plane_select_params;
+int ovg_plane_select(const ovg_plane_select_params*, void* stream);
+
+typedef struct {
+  const float* points; const uint8_t* valid; const float* plane; const int32_t* gate;
+  int64_t n;
+  float threshold; int32_t pad;
+  uint8_t* inlier; float* distance; int64_t* out_count;
+} ovg_plane_mask_params;
+int ovg_plane_mask(const ovg_plane_mask_params*, void* stream);
+
+typedef struct {
+  const int64_t* count; const double* sums; const double* centre; const float* axis;
+  float* plane;
+  double* out_rms; double* out_eigen; int32_t* status;
+} ovg_plane_fit_params;
+int ovg_plane_fit(const ovg_plane_fit_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

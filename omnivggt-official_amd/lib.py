@@ -308,6 +308,34 @@ class AlignApplyParams(C.Structure):
     _fields_ = [("points", vp), ("transform", vp), ("n", i64), ("out", vp)]
 
 
+PLANE_HYP_TILE, PLANE_POINT_TILE = 512, 512                  # hypotheses per workgroup, points per LDS tile of ovg_plane_score (tests place shapes around them)
+PLANE_NONE, PLANE_FEW, PLANE_NO_SPREAD, PLANE_NOT_FINITE = 1, 2, 4, 8   # status bits of ovg_plane_select (NONE) and ovg_plane_fit
+PLANE_COLLINEAR_EPS, PLANE_SPREAD_EPS = 2.0 ** -20, 2.0 ** -40
+
+
+class PlaneHypothesesParams(C.Structure):
+    _fields_ = [("points", vp), ("valid", vp), ("candidates", vp), ("axis", vp), ("n", i64), ("m", i64), ("H", i64), ("seed", C.c_uint64),
+                ("min_abs_cos", f32), ("pad", i32), ("planes", vp), ("index", vp)]
+
+
+class PlaneScoreParams(C.Structure):
+    _fields_ = [("points", vp), ("valid", vp), ("planes", vp), ("n", i64), ("H", i64), ("threshold", f32), ("splits", i32), ("count", vp)]
+
+
+class PlaneSelectParams(C.Structure):
+    _fields_ = [("count", vp), ("planes", vp), ("H", i64), ("min_inliers", i32), ("pad", i32), ("best", vp), ("plane", vp),
+                ("best_count", vp), ("status", vp)]
+
+
+class PlaneMaskParams(C.Structure):
+    _fields_ = [("points", vp), ("valid", vp), ("plane", vp), ("gate", vp), ("n", i64), ("threshold", f32), ("pad", i32), ("inlier", vp),
+                ("distance", vp), ("out_count", vp)]
+
+
+class PlaneFitParams(C.Structure):
+    _fields_ = [("count", vp), ("sums", vp), ("centre", vp), ("axis", vp), ("plane", vp), ("out_rms", vp), ("out_eigen", vp), ("status", vp)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -392,6 +420,11 @@ SYMBOLS = {
     "ovg_align_workspace_bytes": (i64, [i64]),
     "ovg_align_solve": (i32, [C.POINTER(AlignSolveParams), vp]),
     "ovg_align_apply": (i32, [C.POINTER(AlignApplyParams), vp]),
+    "ovg_plane_hypotheses": (i32, [C.POINTER(PlaneHypothesesParams), vp]),
+    "ovg_plane_score": (i32, [C.POINTER(PlaneScoreParams), vp]),
+    "ovg_plane_select": (i32, [C.POINTER(PlaneSelectParams), vp]),
+    "ovg_plane_mask": (i32, [C.POINTER(PlaneMaskParams), vp]),
+    "ovg_plane_fit": (i32, [C.POINTER(PlaneFitParams), vp]),
 }
 
 

@@ -1147,3 +1147,151 @@ def align_apply(points, transform, out=None):
     p.points, p.transform, p.n, p.out = L.ptr(points), L.ptr(transform), n, L.ptr(out)
     L.call("ovg_align_apply", p, _stream())
     return out
+
+
+def _plane_points(what, points):
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or \
+            points.shape[1] != 3 or not 1 <= points.shape[0] < 1 << 31:
+        raise L.OvgError("%s: points must be a contiguous f32 tensor [n, 3], 1 <= n < 2^31" % what)
+    return int(points.shape[0])
+
+
+def _plane_threshold(what, threshold):
+    import math
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not (threshold >= 0 and math.isfinite(threshold)) or \
+            threshold > 3.4028234663852886e38:
+        raise L.OvgError("%s: threshold must be a finite float32 number >= 0, got %r" % (what, threshold))
+    return float(threshold)
+
+
+def _plane_out(what, t, name, dtype, shape, device):
+    _align_tensor(what, t, name, dtype, shape, True)
+    return torch.empty(shape, device=device, dtype=dtype) if t is None else t
+
+
+def plane_hypotheses(points, hypotheses, seed=0, valid=None, candidates=None, axis=None, min_abs_cos=0.0, planes=None, index=None):
+    """ovg_plane_hypotheses on contiguous device tensors: points f32 [n, 3], valid u8 [n] or None, candidates int32 [m] or None (draw
+    from all n points), axis f32 [3] or None (a unit vector: used as given) with min_abs_cos in [0, 1]; hypotheses = H, seed in
+    [0, 2^64). -> (planes f32 [H, 4], index int32 [H, 3]) (allocated when None): hypothesis h through the three points its seeded
+    draws name, four NaNs where the rule of include/omnivggt_hip.h voids it; index holds the draws either way. Nothing is read back."""
+    what = "plane_hypotheses"
+    n = _plane_points(what, points)
+    if isinstance(hypotheses, bool) or not isinstance(hypotheses, int) or not 1 <= hypotheses < 1 << 31:
+        raise L.OvgError("%s: hypotheses must be an integer in [1, 2^31), got %r" % (what, hypotheses))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise L.OvgError("%s: seed must be an integer in [0, 2^64), got %r" % (what, seed))
+    _align_tensor(what, valid, "valid", torch.uint8, (n,), True)
+    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int32 or candidates.dim() != 1 or
+                                   not candidates.is_contiguous() or not 1 <= candidates.shape[0] < 1 << 31):
+        raise L.OvgError("%s: candidates must be a contiguous int32 tensor [m], 1 <= m < 2^31" % what)
+    _align_tensor(what, axis, "axis", torch.float32, (3,), True)
+    if isinstance(min_abs_cos, bool) or not isinstance(min_abs_cos, (int, float)) or not 0.0 <= min_abs_cos <= 1.0:
+        raise L.OvgError("%s: min_abs_cos must be a number in [0, 1], got %r" % (what, min_abs_cos))
+    if axis is None and min_abs_cos != 0:
+        raise L.OvgError("%s: min_abs_cos needs an axis" % what)
+    _chk_dev(points, valid, candidates, axis, planes, index)
+    planes = _plane_out(what, planes, "planes", torch.float32, (hypotheses, 4), points.device)
+    index = _plane_out(what, index, "index", torch.int32, (hypotheses, 3), points.device)
+    p = L.PlaneHypothesesParams()
+    p.points, p.valid, p.candidates, p.axis = L.ptr(points), L.ptr(valid), L.ptr(candidates), L.ptr(axis)
+    p.n, p.m, p.H, p.seed = n, n if candidates is None else int(candidates.shape[0]), hypotheses, seed
+    p.min_abs_cos, p.pad, p.planes, p.index = float(min_abs_cos), 0, L.ptr(planes), L.ptr(index)
+    L.call("ovg_plane_hypotheses", p, _stream())
+    return planes, index
+
+
+def plane_score(points, planes, threshold, valid=None, splits=0, count=None):
+    """ovg_plane_score on contiguous device tensors: points f32 [n, 3], planes f32 [H, 4], valid u8 [n] or None, threshold a host float
+    (finite, >= 0; used as float32). -> count int32 [H] (allocated when None): the points with |((nx x + ny y) + nz z) + w| <= threshold
+    per plane, usable points only; a void (NaN) plane counts 0. splits: 0 lets the entry choose, otherwise the number of point splits
+    of its grid -- the bytes are the same for every value. Nothing is read back."""
+    what = "plane_score"
+    n = _plane_points(what, points)
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.float32 or not planes.is_contiguous() or planes.dim() != 2 or \
+            planes.shape[1] != 4 or not 1 <= planes.shape[0] < 1 << 31:
+        raise L.OvgError("%s: planes must be a contiguous f32 tensor [H, 4], 1 <= H < 2^31" % what)
+    H = int(planes.shape[0])
+    threshold = _plane_threshold(what, threshold)
+    _align_tensor(what, valid, "valid", torch.uint8, (n,), True)
+    if isinstance(splits, bool) or not isinstance(splits, int) or not 0 <= splits < 1 << 31:
+        raise L.OvgError("%s: splits must be an integer in [0, 2^31), got %r" % (what, splits))
+    _chk_dev(points, planes, valid, count)
+    count = _plane_out(what, count, "count", torch.int32, (H,), points.device)
+    p = L.PlaneScoreParams()
+    p.points, p.valid, p.planes, p.n, p.H = L.ptr(points), L.ptr(valid), L.ptr(planes), n, H
+    p.threshold, p.splits, p.count = threshold, splits, L.ptr(count)
+    L.call("ovg_plane_score", p, _stream())
+    return count
+
+
+def plane_select(count, planes, min_inliers=3, best=None, plane=None, best_count=None, status=None):
+    """ovg_plane_select on device tensors: count int32 [H], planes f32 [H, 4] -> (best int32 [1], plane f32 [4], best_count int32 [1],
+    status int32 [1]) (allocated when None): the hypothesis with the most inliers, ties to the lowest index, or -1 / four zeros /
+    L.PLANE_NONE when that count is below min_inliers (>= 3). Nothing is read back."""
+    what = "plane_select"
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.dim() != 1 or not count.is_contiguous() or \
+            not 1 <= count.shape[0] < 1 << 31:
+        raise L.OvgError("%s: count must be a contiguous int32 tensor [H], 1 <= H < 2^31" % what)
+    H = int(count.shape[0])
+    _align_tensor(what, planes, "planes", torch.float32, (H, 4))
+    if isinstance(min_inliers, bool) or not isinstance(min_inliers, int) or not 3 <= min_inliers < 1 << 31:
+        raise L.OvgError("%s: min_inliers must be an integer in [3, 2^31), got %r" % (what, min_inliers))
+    _chk_dev(count, planes, best, plane, best_count, status)
+    dev = count.device
+    best = _plane_out(what, best, "best", torch.int32, (1,), dev)
+    plane = _plane_out(what, plane, "plane", torch.float32, (4,), dev)
+    best_count = _plane_out(what, best_count, "best_count", torch.int32, (1,), dev)
+    status = _plane_out(what, status, "status", torch.int32, (1,), dev)
+    p = L.PlaneSelectParams()
+    p.count, p.planes, p.H, p.min_inliers, p.pad = L.ptr(count), L.ptr(planes), H, min_inliers, 0
+    p.best, p.plane, p.best_count, p.status = L.ptr(best), L.ptr(plane), L.ptr(best_count), L.ptr(status)
+    L.call("ovg_plane_select", p, _stream())
+    return best, plane, best_count, status
+
+
+def plane_mask(points, plane, threshold, valid=None, gate=None, inlier=None, distance=None, out_count=None):
+    """ovg_plane_mask on contiguous device tensors: points f32 [n, 3], plane f32 [4] (read on the device), valid u8 [n] or None, gate
+    int32 [1] or None (a status: with L.PLANE_NONE in it nothing is an inlier). -> (inlier u8 [n], distance, out_count int64 [1]):
+    the inlier mask of the plane at the threshold, the signed residual f32 [n] (NaN for unusable points) when distance is a tensor or
+    True (allocated), else None, and the number of inliers. Nothing is read back."""
+    what = "plane_mask"
+    n = _plane_points(what, points)
+    _align_tensor(what, plane, "plane", torch.float32, (4,))
+    threshold = _plane_threshold(what, threshold)
+    _align_tensor(what, valid, "valid", torch.uint8, (n,), True)
+    _align_tensor(what, gate, "gate", torch.int32, (1,), True)
+    dist = None if isinstance(distance, bool) else distance
+    _chk_dev(points, plane, valid, gate, inlier, dist, out_count)
+    inlier = _plane_out(what, inlier, "inlier", torch.uint8, (n,), points.device)
+    if distance is True:
+        dist = torch.empty(n, device=points.device, dtype=torch.float32)
+    _align_tensor(what, dist, "distance", torch.float32, (n,), True)
+    out_count = _plane_out(what, out_count, "out_count", torch.int64, (1,), points.device)
+    p = L.PlaneMaskParams()
+    p.points, p.valid, p.plane, p.gate, p.n = L.ptr(points), L.ptr(valid), L.ptr(plane), L.ptr(gate), n
+    p.threshold, p.pad, p.inlier, p.distance, p.out_count = threshold, 0, L.ptr(inlier), L.ptr(dist), L.ptr(out_count)
+    L.call("ovg_plane_mask", p, _stream())
+    return inlier, dist, out_count
+
+
+def plane_fit(count, sums, plane, centre=None, axis=None, rms=None, eigen=None, status=None):
+    """ovg_plane_fit on device tensors: the moments of the inliers (count int64 [1], sums f64 [18] and the centre f64 [6] they were
+    computed with, or None: align_moments with source == target == the points and source_valid = the inlier mask) -> the
+    least-squares plane through them, written over plane f32 [4]; axis f32 [3] or None orients it. A degenerate step (fewer than three
+    inliers, collinear inliers, non-finite sums) leaves the plane as it was. rms f64 [1], eigen f64 [3] (ascending) and status int32 [1]
+    (L.PLANE_FEW | L.PLANE_NO_SPREAD | L.PLANE_NOT_FINITE) are written when given. -> plane. Nothing is read back."""
+    what = "plane_fit"
+    _align_tensor(what, count, "count", torch.int64, (1,))
+    _align_tensor(what, sums, "sums", torch.float64, (L.ALIGN_SUMS,))
+    _align_tensor(what, plane, "plane", torch.float32, (4,))
+    _align_tensor(what, centre, "centre", torch.float64, (6,), True)
+    _align_tensor(what, axis, "axis", torch.float32, (3,), True)
+    _align_tensor(what, rms, "rms", torch.float64, (1,), True)
+    _align_tensor(what, eigen, "eigen", torch.float64, (3,), True)
+    _align_tensor(what, status, "status", torch.int32, (1,), True)
+    _chk_dev(count, sums, plane, centre, axis, rms, eigen, status)
+    p = L.PlaneFitParams()
+    p.count, p.sums, p.centre, p.axis, p.plane = L.ptr(count), L.ptr(sums), L.ptr(centre), L.ptr(axis), L.ptr(plane)
+    p.out_rms, p.out_eigen, p.status = L.ptr(rms), L.ptr(eigen), L.ptr(status)
+    L.call("ovg_plane_fit", p, _stream())
+    return plane

@@ -1241,6 +1241,269 @@ def trajectory_ate(pred_extrinsic, gt_extrinsic, with_scale=True):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# Plane segmentation: RANSAC over seeded hypotheses, least-squares refit, floor alignment (ovg_plane_*)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+PLANE_NONE, PLANE_FEW, PLANE_NO_SPREAD, PLANE_NOT_FINITE = ops.L.PLANE_NONE, ops.L.PLANE_FEW, ops.L.PLANE_NO_SPREAD, ops.L.PLANE_NOT_FINITE
+PLANE_MAX_HYPOTHESES = 1 << 24
+
+
+class PlaneResult:
+    """Result of segment_plane, all on the device: plane float32 (4,) = (nx, ny, nz, w) with |n| = 1 and n.p + w = 0 on the plane (zeros
+    when there is none); inlier bool, shaped like the points without their last dimension; count (0-d int64: the inliers), hypothesis
+    (0-d int32: the winning hypothesis, -1 for none), rms (0-d float64: the root mean square distance of the last refit's inliers to
+    its plane, 0 without a refit) and status (0-d int32: 0, or PLANE_NONE when no hypothesis reached min_inliers, with PLANE_FEW |
+    PLANE_NO_SPREAD | PLANE_NOT_FINITE from a refit round that kept the previous plane). distance: the signed residual float32 shaped
+    like `inlier` (NaN at unusable points), None unless asked for."""
+    __slots__ = ("plane", "inlier", "count", "hypothesis", "rms", "status", "distance")
+
+    def __init__(self, plane, inlier, count, hypothesis, rms, status, distance=None):
+        self.plane, self.inlier, self.count, self.hypothesis, self.rms, self.status, self.distance = plane, inlier, count, hypothesis, rms, status, distance
+
+
+def _plane_int(value, name, lo, hi):
+    if isinstance(value, bool) or not isinstance(value, int) or not lo <= value < hi:
+        raise ValueError("%s must be an integer in [%d, %d), got %r" % (name, lo, hi, value))
+    return value
+
+
+def _plane_args(what, cloud_or_points, threshold, rel_threshold, hypotheses, seed, refit, min_inliers, valid, axis, max_angle_deg, candidates):
+    """The argument checks segment_plane and segment_planes share, ValueErrors first, then the device check.
+    -> (pts, lead, valid, threshold float32 as a host float, axis float32 [3] device tensor or None, min_abs_cos, candidates)"""
+    import math
+    if (threshold is None) == (rel_threshold is None):
+        raise ValueError("%s: give exactly one of threshold and rel_threshold" % what)
+    pts = _nn_points(cloud_or_points, "cloud_or_points")
+    lead = tuple(pts.shape[:-1])
+    valid = _nn_valid(valid, lead, "valid")
+    if threshold is not None:
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not (threshold >= 0 and math.isfinite(threshold)):
+            raise ValueError("threshold must be a finite number >= 0, got %r" % (threshold,))
+        try:
+            threshold = _f32(float(threshold))
+        except OverflowError:
+            threshold = float("inf")
+        if not math.isfinite(threshold):
+            raise ValueError("threshold %r is not finite in float32" % (threshold,))
+    _plane_int(hypotheses, "hypotheses", 1, PLANE_MAX_HYPOTHESES + 1)
+    _plane_int(seed, "seed", 0, 1 << 64)
+    _plane_int(refit, "refit", 0, 65)
+    _plane_int(min_inliers, "min_inliers", 3, 1 << 31)
+    if max_angle_deg is not None:
+        if axis is None:
+            raise ValueError("max_angle_deg needs an axis")
+        if isinstance(max_angle_deg, bool) or not isinstance(max_angle_deg, (int, float)) or not 0 < max_angle_deg <= 90:
+            raise ValueError("max_angle_deg must be a number in (0, 90], got %r" % (max_angle_deg,))
+    min_abs_cos = 0.0 if max_angle_deg is None else max(0.0, min(1.0, _f32(math.cos(math.radians(float(max_angle_deg))))))
+    host_axis = None
+    if isinstance(axis, torch.Tensor):
+        if axis.numel() != 3 or axis.dtype not in (torch.float32, torch.float64):
+            raise ValueError("axis must hold three float32 / float64 values")
+    elif axis is not None:
+        try:
+            host_axis = [float(v) for v in axis]
+        except (TypeError, ValueError):
+            raise ValueError("axis must be three finite numbers or a tensor of three, got %r" % (axis,)) from None
+        if len(host_axis) != 3 or not all(math.isfinite(v) for v in host_axis):
+            raise ValueError("axis must be three finite numbers, got %r" % (axis,))
+        x, y, z = host_axis
+        length = math.sqrt((x * x + y * y) + z * z)
+        if not (length > 0 and math.isfinite(length)):
+            raise ValueError("axis must have a finite non-zero length, got %r" % (axis,))
+        host_axis = [x / length, y / length, z / length]
+    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dim() != 1 or
+                                   candidates.dtype not in (torch.int32, torch.int64) or candidates.numel() >= 1 << 31):
+        raise ValueError("candidates must be a one-dimensional int32 / int64 tensor of point indices")
+    if rel_threshold is not None:
+        threshold = _cloud_radius(what, cloud_or_points, pts, None, rel_threshold)       # reads scene_scale back: the one synchronisation
+    tensors = (pts, valid, candidates, axis if isinstance(axis, torch.Tensor) else None)
+    if not all(t is None or t.is_cuda for t in tensors):
+        raise ops.L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
+    if host_axis is not None:
+        axis = torch.tensor(host_axis, dtype=torch.float64).to(torch.float32).to(pts.device)
+    elif axis is not None:
+        a = axis.reshape(3).to(torch.float64)
+        axis = (a / ((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]).sqrt()).to(torch.float32).contiguous()
+    if candidates is not None:
+        candidates = candidates.to(torch.int32).contiguous()
+    return pts, lead, valid, threshold, axis, min_abs_cos, candidates
+
+
+def _segment_plane(pts, valid, threshold, hypotheses, seed, refit, min_inliers, axis, min_abs_cos, candidates, want_distance):
+    """segment_plane for contiguous [n, 3] points, u8 [n] valid, int32 candidates (None or non-empty): launches only."""
+    dev = pts.device
+    planes, _ = ops.plane_hypotheses(pts, hypotheses, seed, valid=valid, candidates=candidates, axis=axis, min_abs_cos=min_abs_cos)
+    count = ops.plane_score(pts, planes, threshold, valid=valid)
+    best, plane, _, status = ops.plane_select(count, planes, min_inliers)
+    want = True if want_distance else None
+    inlier, distance, total = ops.plane_mask(pts, plane, threshold, valid=valid, gate=status, distance=want)
+    rms = torch.zeros(1, device=dev, dtype=torch.float64)
+    if refit:
+        ws = torch.empty(ops.align_workspace_bytes(pts.shape[0]), device=dev, dtype=torch.uint8)
+        step = torch.empty(1, device=dev, dtype=torch.int32)
+    for _ in range(refit):
+        n0, s0 = ops.align_moments(pts, pts, source_valid=inlier, ws=ws)
+        centre = s0[:6] / n0.clamp_min(1).to(torch.float64)
+        n1, s1 = ops.align_moments(pts, pts, source_valid=inlier, centre=centre, ws=ws)
+        ops.plane_fit(n1, s1, plane, centre=centre, axis=axis, rms=rms, status=step)
+        status = status | step
+        inlier, distance, total = ops.plane_mask(pts, plane, threshold, valid=valid, gate=status, inlier=inlier, distance=distance, out_count=total)
+    return PlaneResult(plane, inlier, total[0], best[0], rms[0], status[0], distance)
+
+
+def _empty_plane(lead, dev, want_distance):
+    return PlaneResult(torch.zeros(4, device=dev, dtype=torch.float32), torch.zeros(lead, device=dev, dtype=torch.bool),
+                       torch.zeros((), device=dev, dtype=torch.int64), torch.full((), -1, device=dev, dtype=torch.int32),
+                       torch.zeros((), device=dev, dtype=torch.float64), torch.full((), PLANE_NONE, device=dev, dtype=torch.int32),
+                       torch.full(lead, float("nan"), device=dev, dtype=torch.float32) if want_distance else None)
+
+
+def segment_plane(cloud_or_points, threshold=None, rel_threshold=None, hypotheses=1024, seed=0, refit=2, min_inliers=3, valid=None,
+                  axis=None, max_angle_deg=None, candidates=None, return_distance=False):
+    """The dominant plane of a cloud -- the floor, a wall, a table top -- by RANSAC on the device (ovg_plane_hypotheses, _score,
+    _select, _mask, _fit; what Open3D's segment_plane and PCL's SACSegmentation do on the host). The result is defined without a
+    schedule (include/omnivggt_hip.h; tests/plane_twin.py restates it by brute force), so two calls give identical bytes:
+
+      a plane is (nx, ny, nz, w) in float32 with |n| = 1; a point is an INLIER when it is usable (valid and finite) and
+      |((nx x + ny y) + nz z) + w| <= threshold in float32 without fused multiply-adds (inclusive);
+      hypothesis h < `hypotheses` is the plane through three points drawn by a splitmix64 hash of (seed, h) from `candidates` (int32 /
+      int64 point indices; default: every point), void when a draw repeats, is unusable or out of range, when the three are
+      near-collinear, or, with `axis` and max_angle_deg, when its normal is more than max_angle_deg away from +-axis;
+      the WINNER has the most inliers over all usable points, ties to the lowest h; none reaching min_inliers (>= 3) gives no plane;
+      `refit` rounds then replace the plane by the least-squares plane through its inliers (the float64 moments of ovg_align_moments,
+      the Jacobi solve of estimate_normals) and recompute the inliers; a degenerate round keeps the plane and sets a status bit.
+
+    Exactly one of threshold (in the cloud's units) and rel_threshold (a PointCloud only: f32(rel_threshold) * scene_scale, as
+    radius_outlier_mask's rel_radius, read back from the device: the only synchronisation) must be given. axis: three numbers or a
+    tensor of three, normalised here; the normal then points to the axis' side (n.axis >= 0) -- pass the scene's up direction to get
+    a floor normal that points up -- and without it the normal's largest component is positive.
+
+    -> PlaneResult. An empty cloud returns a result with status PLANE_NONE without a launch. CPU tensors raise OvgError (there is no
+    CPU fallback); bad arguments raise ValueError."""
+    if not isinstance(return_distance, bool):
+        raise ValueError("return_distance must be True or False, got %r" % (return_distance,))
+    pts, lead, valid, threshold, axis, min_abs_cos, candidates = _plane_args(
+        "segment_plane", cloud_or_points, threshold, rel_threshold, hypotheses, seed, refit, min_inliers, valid, axis, max_angle_deg, candidates)
+    n = pts.numel() // 3
+    if n == 0 or (candidates is not None and candidates.numel() == 0):
+        return _empty_plane(lead, pts.device, return_distance)
+    res = _segment_plane(pts.reshape(n, 3).contiguous(), _u8_flat(valid), threshold, hypotheses, seed, refit, min_inliers, axis, min_abs_cos,
+                         candidates, return_distance)
+    res.inlier = res.inlier.reshape(lead).to(torch.bool)
+    if res.distance is not None:
+        res.distance = res.distance.reshape(lead)
+    return res
+
+
+def segment_planes(cloud_or_points, max_planes=4, min_inliers=None, threshold=None, rel_threshold=None, hypotheses=1024, seed=0, refit=2,
+                   valid=None, axis=None, max_angle_deg=None, candidates=None):
+    """The dominant planes of a cloud one after the other (segment_plane's arguments and rule): plane k is searched among the points no
+    earlier plane took -- it draws from the candidates still unlabelled (every unlabelled point without a list) with seed + k and is
+    scored over the unlabelled points only -- and the extraction stops at the first plane below min_inliers (default: a twentieth of
+    the cloud, at least 3) or after max_planes. Extraction is sequential: it synchronises with the device once per plane, to read
+    the plane's status and the length of the next candidate list back.
+
+    -> (planes float32 (P, 4), labels int32 shaped like the points without their last dimension): the plane's rank in extraction
+    order at its inliers, -1 elsewhere; cluster_colors(labels) colours them. Errors as segment_plane."""
+    n_all = _nn_points(cloud_or_points, "cloud_or_points").numel() // 3
+    if min_inliers is None:
+        min_inliers = max(3, n_all // 20)
+    _plane_int(max_planes, "max_planes", 1, 1 << 16)
+    pts, lead, valid, threshold, axis, min_abs_cos, candidates = _plane_args(
+        "segment_planes", cloud_or_points, threshold, rel_threshold, hypotheses, seed, refit, min_inliers, valid, axis, max_angle_deg, candidates)
+    dev, n = pts.device, n_all
+    labels = torch.full((n,), -1, device=dev, dtype=torch.int32)
+    planes = []
+    if n:
+        flat = pts.reshape(n, 3).contiguous()
+        base = torch.ones(n, device=dev, dtype=torch.uint8) if valid is None else (_u8_flat(valid) != 0).to(torch.uint8)
+        cand = candidates
+        for k in range(max_planes):
+            free = labels < 0
+            if k > 0 or cand is not None:
+                if candidates is None:
+                    cand = torch.nonzero(free).reshape(-1).to(torch.int32)
+                else:
+                    inside = (cand >= 0) & (cand < n)
+                    cand = cand[inside & free[cand.clamp(0, n - 1).long()]]
+                if cand.numel() == 0:
+                    break
+            res = _segment_plane(flat, base & free.to(torch.uint8), threshold, hypotheses, (seed + k) & ((1 << 64) - 1), refit, min_inliers, axis,
+                                 min_abs_cos, cand, False)
+            if int(res.status) & PLANE_NONE:
+                break
+            labels = torch.where(res.inlier != 0, torch.full_like(labels, k), labels)
+            planes.append(res.plane)
+    out = torch.stack(planes) if planes else torch.zeros(0, 4, device=dev, dtype=torch.float32)
+    return out, labels.reshape(lead)
+
+
+def remove_plane(cloud, result, keep="outliers"):
+    """A PointCloud without the inliers of a PlaneResult (keep="outliers": the scene without its floor, for cluster_points, where the
+    floor would join every object into one component) or with them alone (keep="inliers"), in input order. Points that are not
+    usable are no inliers and stay with the outliers. Gathered as remove_radius_outliers gathers: points, colors and conf at the kept
+    points, `indices` the input cloud's there (or the positions in the input cloud when it has none), everything else passed through."""
+    if not isinstance(cloud, PointCloud):
+        raise ValueError("remove_plane takes a PointCloud")
+    if not isinstance(result, PlaneResult):
+        raise ValueError("expected the PlaneResult of segment_plane")
+    if keep not in ("outliers", "inliers"):
+        raise ValueError("keep must be \"outliers\" or \"inliers\", got %r" % (keep,))
+    if result.inlier.numel() != len(cloud):
+        raise ValueError("the PlaneResult holds %d points, the cloud %d" % (result.inlier.numel(), len(cloud)))
+    inl = result.inlier.reshape(-1).to(torch.bool)
+    return _gather_cloud(cloud, inl if keep == "inliers" else ~inl)
+
+
+def floor_alignment(plane, up=(0.0, 1.0, 0.0)):
+    """The rigid transform that puts a plane on the ground: a Similarity (scale 1, float64) whose rotation takes the plane's normal onto
+    `up` by the shortest arc -- an antiparallel normal is turned by half a turn about the axis perpendicular to it that the first
+    coordinate axis not parallel to it gives -- and whose translation puts the plane at height 0, so that up . (moved point) is the
+    point's signed distance to the plane. plane: a PlaneResult or a tensor of four (nx, ny, nz, w); up: three numbers.
+    Similarity.apply(cloud) then moves a cloud for write_glb and render_point_cloud. A few float64 torch operations on the plane's
+    device; nothing is read back. A plane of zeros (no plane) gives a matrix of NaNs."""
+    import math
+    if isinstance(plane, PlaneResult):
+        plane = plane.plane
+    if not isinstance(plane, torch.Tensor) or plane.numel() != 4 or plane.dtype not in (torch.float32, torch.float64):
+        raise ValueError("plane must be a PlaneResult or a float32 / float64 tensor of four values")
+    try:
+        u = [float(v) for v in up]
+    except (TypeError, ValueError):
+        raise ValueError("up must be three finite numbers, got %r" % (up,)) from None
+    length = math.sqrt(sum(v * v for v in u)) if len(u) == 3 else 0.0
+    if len(u) != 3 or not (length > 0 and math.isfinite(length)):
+        raise ValueError("up must be three finite numbers with a non-zero length, got %r" % (up,))
+    dev = plane.device
+    q = plane.reshape(4).to(torch.float64)
+    norm = (q[:3] * q[:3]).sum().sqrt()
+    n, w = q[:3] / norm, q[3] / norm
+    u = torch.tensor([v / length for v in u], dtype=torch.float64, device=dev)
+    eye = torch.eye(3, dtype=torch.float64, device=dev)
+
+    def cross_matrix(v):
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        return torch.stack([torch.stack([zero, -v[2], v[1]]), torch.stack([v[2], zero, -v[0]]), torch.stack([-v[1], v[0], zero])])
+
+    c = (n * u).sum()
+    K = cross_matrix(torch.linalg.cross(n, u))
+    near = K @ K / (1.0 + c).clamp_min(1e-300)
+    R = eye + K + near                                                          # Rodrigues with sin = |n x u|, (1 - cos) / sin^2 = 1 / (1 + cos)
+    # antiparallel: half a turn about a = e x n / |e x n|, e the first coordinate axis not parallel to n; R = 2 a a^T - I
+    first = (n[0].abs() < 0.9).to(torch.float64)
+    e = torch.stack([first, 1.0 - first, torch.zeros((), dtype=torch.float64, device=dev)])
+    a = torch.linalg.cross(e, n)
+    a = a / (a * a).sum().sqrt()
+    half = 2.0 * torch.outer(a, a) - eye
+    R = torch.where(1.0 + c < 1e-12, half, R)
+    M = torch.eye(4, dtype=torch.float64, device=dev)
+    M[:3, :3] = R
+    M[:3, 3] = w * u
+    return Similarity(M, torch.ones((), device=dev, dtype=torch.float64), torch.zeros((), device=dev, dtype=torch.int64),
+                      torch.zeros((), device=dev, dtype=torch.float64), torch.zeros((), device=dev, dtype=torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # Farthest-point sampling: a fixed number of well-spread points (ovg_farthest_point_sample)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
