@@ -67,7 +67,9 @@ extern "C" {
  *       the same way
  *     + clustering on that grid: Euclidean connected components and DBSCAN (ovg_cluster): added the same way
  *     + plane segmentation by RANSAC (ovg_plane_hypotheses, ovg_plane_score, ovg_plane_select, ovg_plane_mask, ovg_plane_fit): added
- *       the same way */
+ *       the same way
+ *     + volumetric fusion: depth maps into a TSDF volume and a surface-nets mesh of its zero level (ovg_tsdf_integrate,
+ *       ovg_tsdf_extract, ovg_tsdf_extract_workspace_bytes): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -1179,6 +1181,99 @@ typedef struct {
   double* out_rms; double* out_eigen; int32_t* status;
 } ovg_plane_fit_params;
 int ovg_plane_fit(const ovg_plane_fit_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Volumetric fusion (added under ABI 13): S depth maps with their cameras are averaged into a dense truncated signed-distance (TSDF)
+ * volume, and one mesh is extracted from its zero level by naive surface nets. Both rules are exact: tests/tsdf_twin.py restates
+ * them in numpy float32 and the device returns its bytes. Every step is one f32 operation rounded on its own (no fused
+ * multiply-add); min(a, b) is `a < b ? a : b`; divisions and the square root are correctly rounded.
+ *
+ * The VOLUME is dense and caller-owned: tsdf [nz][ny][nx] f32 and weight [nz][ny][nx] f32, optionally color [nz][ny][nx][4] f32
+ * (r, g, b in [0, 255] and the colour weight). Lattice point (i, j, k) lies at origin + voxel * (i, j, k). A FRESH volume is
+ * tsdf = 1 and everything else 0.
+ *
+ * ovg_tsdf_integrate: one thread per lattice point, the views view_first .. view_first + view_count - 1 in ascending order.
+ *   depth [S][H][W] f32 z-depth; cams [S][16] f32 packed as for ovg_render_points; valid [S][H][W] u8, obs_weight [S][H][W] f32 and
+ *   colors [S][H][W][3] u8 are optional (NULL). Per lattice point and view:
+ *   1. p = origin + voxel * (f32) index per axis: one multiply, one add;
+ *   2. rules 1-3 of ovg_render_points give zc and the pixel (u, w); the view is skipped when the point is culled (a camera
+ *      coordinate is not finite, zc <= near) or unless 0 <= u <= W - 1 and 0 <= w <= H - 1 (compared in f32: NaN fails);
+ *   3. d = depth[s][w][u]; skipped unless valid[s][w][u] != 0 (when given), d is finite and d > near. wobs = obs_weight[s][w][u]
+ *      when given (skipped unless it is finite and > 0), else 1;
+ *   4. sdf = d - zc; skipped when sdf < -trunc (the point is hidden behind the surface). t = min(sdf / trunc, 1);
+ *   5. Wn = W + wobs; T = (T * W + t * wobs) / Wn; W = min(Wn, max_weight);
+ *   6. with colors and a colour volume, and sdf <= trunc (free-space observations do not colour a voxel): Cn = Cw + wobs;
+ *      ch = (ch * Cw + (f32) colour * wobs) / Cn for r, g, b; Cw = min(Cn, max_weight).
+ *   The state of a lattice point is read once, kept in registers across the view loop and written once; there are no atomics, no
+ *   workspace, no LDS and no scratch. Two calls give identical bytes, and a call over the views [0, S) gives the bytes of two
+ *   calls over [0, k) and [k, S): that is the incremental form. Camera rows are wave-uniform scalar loads.
+ *   tile: the 256 lattice points of a workgroup as an x x y x z brick (OVG_TSDF_TILE_DEFAULT is the brick DESIGN.md names). It
+ *   changes speed only, never a byte.
+ *   Nearest-pixel depth lookup only: no bilinear depth, no de-integration, no hashed or sparse volume.
+ *   OVG_E_ARG (before the first HIP call; nothing is written): NULL params / tsdf / weight / depth / cams, colors without a colour
+ *   volume, nx, ny, nz, S, H, W <= 0, nx ny nz >= 2^31, S H W >= 2^31, a view range outside [0, S) or empty, voxel / trunc /
+ *   max_weight / near not positive and finite, an origin that is not finite, an unknown tile, a pointer that is not 4-byte (the
+ *   colour volume: 16-byte) aligned.
+ *
+ * ovg_tsdf_extract: the mesh of the zero level by naive surface nets; no case table.
+ *   A lattice point is OBSERVED when W >= min_weight (min_weight > 0, finite) and INSIDE when T < 0 (so -0 and NaN are outside).
+ *   Corner c = dx + 2 dy + 4 dz of the cell (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, is the lattice point (i + dx, j + dy,
+ *   k + dz). The 12 EDGES of a cell in their fixed order, as (lower corner a, upper corner b): the x edges (0,1) (2,3) (4,5) (6,7),
+ *   the y edges (0,2) (1,3) (4,6) (5,7), the z edges (0,4) (1,5) (2,6) (3,7).
+ *   A cell is ACTIVE when its 8 corners are observed and their insides are mixed. It owns one vertex:
+ *   - every edge whose endpoints differ in `inside` contributes its crossing r = Ta / (Ta - Tb) as the local offset of a with r
+ *     in place of the edge's axis; the offsets are summed per component in f32 in edge order (from 0) and divided by their number;
+ *     position = origin + voxel * ((f32) index + offset) per axis;
+ *   - normal: g = per axis the four differences Tb - Ta of that axis' edges, ((d0 + d1) + d2) + d3; l = sqrt((gx gx + gy gy) +
+ *     gz gz); g / l when l > 0, else (0, 0, 0). It points from inside to outside;
+ *   - colour: the corners c = 0 .. 7 with colour weight > 0, their r, g, b summed in f32 in that order and divided by their
+ *     number, then floor(x + 0.5) clamped to [0, 255] (NaN gives 0); OVG_TSDF_GREY in all three channels when there are none or
+ *     the volume has no colours.
+ *   Vertices leave in ascending cell index (k ny + j) nx + i. Every lattice EDGE from the point (i, j, k) along the axis a, in
+ *   ascending (lattice index, axis), with two observed endpoints that differ in `inside`, whose four surrounding cells exist and
+ *   are active, emits one quad: with b = (a + 1) % 3, c = (a + 2) % 3 the vertices v0 .. v3 of the cells at the offsets (-1, -1),
+ *   (0, -1), (0, 0), (-1, 0) along (b, c) -- counter-clockwise seen from +a -- in that order when the lower endpoint is the
+ *   inside one, else as (v0, v3, v2, v1); the quad (q0, q1, q2, q3) leaves as the triangles (q0, q1, q2), (q0, q2, q3). The triangle
+ *   normals point from inside to outside: the signed volume of an enclosed solid is positive.
+ *   stage OVG_TSDF_COUNT: the active cells, the quads of every lattice point, per-workgroup counts and their scans into ws;
+ *   out_count[0] = M vertices, out_count[1] = Q quads (two int64, device). stage OVG_TSDF_SCATTER reads what COUNT left in ws and
+ *   writes vertices [M][3] f32, normals [M][3] f32, colors [M][3] u8 and faces [2 Q][3] int32; vertices at positions >=
+ *   vertex_capacity and quads at positions >= quad_capacity are dropped (a face may then name a dropped vertex). Both stages in
+ *   one call need the capacities known in advance; the usual form is COUNT, read the counts, allocate, SCATTER with the same ws.
+ *   A volume without a crossing, or with an axis of length 1, gives M = Q = 0 and OVG_OK. No atomics: two calls give identical bytes.
+ *   ws: >= ovg_tsdf_extract_workspace_bytes(nx, ny, nz) bytes (an int32 vertex-index volume, one byte per lattice point and two
+ *   int64 per 256 lattice points, each part rounded up to 256), 16-byte aligned; the query returns -1 for nx, ny, nz <= 0 or
+ *   nx ny nz >= 2^31.
+ *   OVG_E_ARG (nothing is written): NULL params / tsdf / weight / ws / out_count, bad nx, ny, nz, voxel not positive and finite,
+ *   an origin that is not finite, min_weight not positive and finite, an unknown stage, in SCATTER a negative capacity or a NULL
+ *   vertices / normals / colors (vertex_capacity > 0) or faces (quad_capacity > 0), a misaligned pointer or an undersized workspace.
+ *   Not in it: marching cubes, ray-casting the volume, mesh smoothing or decimation.
+ * ------------------------------------------------------------------ */
+enum { OVG_TSDF_TILE_DEFAULT = 0, OVG_TSDF_TILE_256x1x1 = 1, OVG_TSDF_TILE_8x8x4 = 2, OVG_TSDF_TILE_16x4x4 = 3, OVG_TSDF_TILE_32x8x1 = 4 };
+enum { OVG_TSDF_COUNT = 1, OVG_TSDF_SCATTER = 2 };
+enum { OVG_TSDF_GREY = 128, OVG_TSDF_EXTRACT_BLOCK = 256 };
+typedef struct {
+  float* tsdf; float* weight; float* color;
+  int32_t nx; int32_t ny; int32_t nz;
+  float origin[3]; float voxel; float trunc; float max_weight; float near;
+  const float* depth; const float* cams; const uint8_t* valid; const float* obs_weight; const uint8_t* colors;
+  int32_t S; int32_t H; int32_t W;
+  int32_t view_first; int32_t view_count;
+  int32_t tile;
+} ovg_tsdf_integrate_params;
+int ovg_tsdf_integrate(const ovg_tsdf_integrate_params*, void* stream);
+
+typedef struct {
+  const float* tsdf; const float* weight; const float* color;
+  int32_t nx; int32_t ny; int32_t nz;
+  float origin[3]; float voxel; float min_weight;
+  int32_t stage; int32_t pad;
+  int64_t vertex_capacity; int64_t quad_capacity;
+  float* vertices; float* normals; uint8_t* colors; int32_t* faces; int64_t* out_count;
+  void* ws; int64_t ws_bytes;
+} ovg_tsdf_extract_params;
+int64_t ovg_tsdf_extract_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int ovg_tsdf_extract(const ovg_tsdf_extract_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

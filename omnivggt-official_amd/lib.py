@@ -336,6 +336,23 @@ class PlaneFitParams(C.Structure):
     _fields_ = [("count", vp), ("sums", vp), ("centre", vp), ("axis", vp), ("plane", vp), ("out_rms", vp), ("out_eigen", vp), ("status", vp)]
 
 
+TSDF_TILE_DEFAULT, TSDF_TILE_256x1x1, TSDF_TILE_8x8x4, TSDF_TILE_16x4x4, TSDF_TILE_32x8x1 = 0, 1, 2, 3, 4   # ovg_tsdf_integrate_params.tile
+TSDF_COUNT, TSDF_SCATTER = 1, 2                              # ovg_tsdf_extract_params.stage
+TSDF_GREY, TSDF_EXTRACT_BLOCK = 128, 256                     # colour of a vertex without one; lattice points per extraction workgroup
+
+
+class TsdfIntegrateParams(C.Structure):
+    _fields_ = [("tsdf", vp), ("weight", vp), ("color", vp), ("nx", i32), ("ny", i32), ("nz", i32), ("origin", f32 * 3), ("voxel", f32),
+                ("trunc", f32), ("max_weight", f32), ("near", f32), ("depth", vp), ("cams", vp), ("valid", vp), ("obs_weight", vp),
+                ("colors", vp), ("S", i32), ("H", i32), ("W", i32), ("view_first", i32), ("view_count", i32), ("tile", i32)]
+
+
+class TsdfExtractParams(C.Structure):
+    _fields_ = [("tsdf", vp), ("weight", vp), ("color", vp), ("nx", i32), ("ny", i32), ("nz", i32), ("origin", f32 * 3), ("voxel", f32),
+                ("min_weight", f32), ("stage", i32), ("pad", i32), ("vertex_capacity", i64), ("quad_capacity", i64), ("vertices", vp),
+                ("normals", vp), ("colors", vp), ("faces", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -425,6 +442,9 @@ SYMBOLS = {
     "ovg_plane_select": (i32, [C.POINTER(PlaneSelectParams), vp]),
     "ovg_plane_mask": (i32, [C.POINTER(PlaneMaskParams), vp]),
     "ovg_plane_fit": (i32, [C.POINTER(PlaneFitParams), vp]),
+    "ovg_tsdf_integrate": (i32, [C.POINTER(TsdfIntegrateParams), vp]),
+    "ovg_tsdf_extract": (i32, [C.POINTER(TsdfExtractParams), vp]),
+    "ovg_tsdf_extract_workspace_bytes": (i64, [i32, i32, i32]),
 }
 
 

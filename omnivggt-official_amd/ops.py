@@ -1295,3 +1295,112 @@ def plane_fit(count, sums, plane, centre=None, axis=None, rms=None, eigen=None, 
     p.out_rms, p.out_eigen, p.status = L.ptr(rms), L.ptr(eigen), L.ptr(status)
     L.call("ovg_plane_fit", p, _stream())
     return plane
+
+
+def _tsdf_scalar(what, name, value):
+    import math
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (value > 0 and math.isfinite(value)) or value > 3.4028234663852886e38:
+        raise L.OvgError("%s: %s must be a positive finite float32 number, got %r" % (what, name, value))
+    return float(value)
+
+
+def _tsdf_volume(what, tsdf, weight, color, origin):
+    if not isinstance(tsdf, torch.Tensor) or tsdf.dtype != torch.float32 or tsdf.dim() != 3 or not tsdf.is_contiguous() or \
+            0 in tsdf.shape or tsdf.numel() >= 1 << 31:
+        raise L.OvgError("%s: tsdf must be a contiguous f32 tensor [nz, ny, nx], 1 <= nx ny nz < 2^31" % what)
+    _align_tensor(what, weight, "weight", torch.float32, tuple(tsdf.shape))
+    _align_tensor(what, color, "color", torch.float32, tuple(tsdf.shape) + (4,), True)
+    try:
+        origin = [float(v) for v in origin]
+    except (TypeError, ValueError):
+        origin = []
+    if len(origin) != 3 or not all(abs(v) <= 3.4028234663852886e38 for v in origin):
+        raise L.OvgError("%s: origin must be three finite float32 numbers" % what)
+    nz, ny, nx = (int(v) for v in tsdf.shape)
+    return nx, ny, nz, origin
+
+
+def tsdf_integrate(tsdf, weight, depth, cams, origin, voxel, trunc, max_weight=64.0, near=1e-3, color=None, valid=None, obs_weight=None,
+                   colors=None, view_first=0, view_count=None, tile=L.TSDF_TILE_DEFAULT):
+    """ovg_tsdf_integrate on contiguous device tensors, in place: tsdf, weight f32 [nz, ny, nx] and color f32 [nz, ny, nx, 4] or None
+    (the volume; fresh: tsdf 1, the rest 0), depth f32 [S, H, W] z-depth, cams f32 [S, 16] (packed as for render_points), valid u8
+    [S, H, W], obs_weight f32 [S, H, W] and colors u8 [S, H, W, 3] or None; origin three host floats, voxel / trunc / max_weight / near
+    host floats (positive, finite; used as float32). The views view_first .. view_first + view_count - 1 (all S by default) are
+    averaged into every lattice point in ascending order by the rule of include/omnivggt_hip.h; a range and then the rest give the
+    bytes of one call. tile: L.TSDF_TILE_*, speed only. -> (tsdf, weight, color). Nothing is read back."""
+    what = "tsdf_integrate"
+    nx, ny, nz, origin = _tsdf_volume(what, tsdf, weight, color, origin)
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 3 or not depth.is_contiguous() or \
+            0 in depth.shape or depth.numel() >= 1 << 31:
+        raise L.OvgError("%s: depth must be a contiguous f32 tensor [S, H, W], 1 <= S H W < 2^31" % what)
+    S, H, W = (int(v) for v in depth.shape)
+    _align_tensor(what, cams, "cams", torch.float32, (S, 16))
+    _align_tensor(what, valid, "valid", torch.uint8, (S, H, W), True)
+    _align_tensor(what, obs_weight, "obs_weight", torch.float32, (S, H, W), True)
+    _align_tensor(what, colors, "colors", torch.uint8, (S, H, W, 3), True)
+    if colors is not None and color is None:
+        raise L.OvgError("%s: colors need a colour volume" % what)
+    voxel, trunc = _tsdf_scalar(what, "voxel", voxel), _tsdf_scalar(what, "trunc", trunc)
+    max_weight, near = _tsdf_scalar(what, "max_weight", max_weight), _tsdf_scalar(what, "near", near)
+    n = S - view_first if view_count is None else view_count
+    if isinstance(view_first, bool) or isinstance(n, bool) or not isinstance(view_first, int) or not isinstance(n, int) or \
+            not (0 <= view_first < S and 0 < n <= S - view_first):
+        raise L.OvgError("%s: views %r .. outside [0, %d)" % (what, view_first, S))
+    if isinstance(tile, bool) or not isinstance(tile, int) or not L.TSDF_TILE_DEFAULT <= tile <= L.TSDF_TILE_32x8x1:
+        raise L.OvgError("%s: unknown tile %r" % (what, tile))
+    _chk_dev(tsdf, weight, color, depth, cams, valid, obs_weight, colors)
+    p = L.TsdfIntegrateParams()
+    p.tsdf, p.weight, p.color, p.nx, p.ny, p.nz = L.ptr(tsdf), L.ptr(weight), L.ptr(color), nx, ny, nz
+    for k in range(3):
+        p.origin[k] = origin[k]
+    p.voxel, p.trunc, p.max_weight, p.near = voxel, trunc, max_weight, near
+    p.depth, p.cams, p.valid, p.obs_weight, p.colors = L.ptr(depth), L.ptr(cams), L.ptr(valid), L.ptr(obs_weight), L.ptr(colors)
+    p.S, p.H, p.W, p.view_first, p.view_count, p.tile = S, H, W, view_first, n, tile
+    L.call("ovg_tsdf_integrate", p, _stream())
+    return tsdf, weight, color
+
+
+def tsdf_extract_workspace_bytes(nx, ny, nz):
+    for v in (nx, ny, nz):
+        if not -(1 << 31) <= int(v) < (1 << 31):
+            raise L.OvgError("ovg_tsdf_extract_workspace_bytes: unsupported (nx=%d, ny=%d, nz=%d)" % (nx, ny, nz))
+    b = L.load().ovg_tsdf_extract_workspace_bytes(int(nx), int(ny), int(nz))
+    if b < 0:
+        raise L.OvgError("ovg_tsdf_extract_workspace_bytes: unsupported (nx=%d, ny=%d, nz=%d)" % (nx, ny, nz))
+    return int(b)
+
+
+def tsdf_extract(stage, tsdf, weight, origin, voxel, ws, min_weight=1.0, color=None, out_count=None, vertex_capacity=0, quad_capacity=0,
+                 vertices=None, normals=None, colors=None, faces=None):
+    """ovg_tsdf_extract on contiguous device tensors: the volume as for tsdf_integrate; ws a uint8 tensor of at least
+    tsdf_extract_workspace_bytes(nx, ny, nz) bytes. stage L.TSDF_COUNT writes (vertices M, quads Q) to the two int64 of out_count;
+    L.TSDF_SCATTER writes the first vertex_capacity vertices to vertices / normals f32 [., 3] and colors u8 [., 3] and the first
+    quad_capacity quads to faces int32 [2 ., 3] (two triangles each) from what the COUNT stage left in ws."""
+    what = "tsdf_extract"
+    nx, ny, nz, origin = _tsdf_volume(what, tsdf, weight, color, origin)
+    voxel, min_weight = _tsdf_scalar(what, "voxel", voxel), _tsdf_scalar(what, "min_weight", min_weight)
+    if stage not in (L.TSDF_COUNT, L.TSDF_SCATTER, L.TSDF_COUNT | L.TSDF_SCATTER):
+        raise L.OvgError("%s: unknown stage %r" % (what, stage))
+    for name, v in (("vertex_capacity", vertex_capacity), ("quad_capacity", quad_capacity)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 62:
+            raise L.OvgError("%s: %s must be a non-negative integer, got %r" % (what, name, v))
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    if stage & L.TSDF_SCATTER:
+        outs = ((vertices, torch.float32, 3 * vertex_capacity), (normals, torch.float32, 3 * vertex_capacity),
+                (colors, torch.uint8, 3 * vertex_capacity), (faces, torch.int32, 6 * quad_capacity))
+        for t, dt, need in outs:
+            if need and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < need):
+                raise L.OvgError("%s: output buffers must be contiguous and hold the capacities" % what)
+    if not isinstance(out_count, torch.Tensor) or out_count.dtype != torch.int64 or out_count.numel() < 2 or not out_count.is_contiguous():
+        raise L.OvgError("%s: out_count must be a contiguous int64 device tensor of two elements" % what)
+    _chk_dev(tsdf, weight, color, ws, out_count, vertices, normals, colors, faces)
+    p = L.TsdfExtractParams()
+    p.tsdf, p.weight, p.color, p.nx, p.ny, p.nz = L.ptr(tsdf), L.ptr(weight), L.ptr(color), nx, ny, nz
+    for k in range(3):
+        p.origin[k] = origin[k]
+    p.voxel, p.min_weight, p.stage, p.pad = voxel, min_weight, int(stage), 0
+    p.vertex_capacity, p.quad_capacity = vertex_capacity, quad_capacity
+    p.vertices, p.normals, p.colors, p.faces, p.out_count = L.ptr(vertices), L.ptr(normals), L.ptr(colors), L.ptr(faces), L.ptr(out_count)
+    p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
+    L.call("ovg_tsdf_extract", p, _stream())

@@ -1716,6 +1716,52 @@ def camera_frusta(extrinsic, height):
     return centre[:, None, :] + np.einsum("sij,vj->svi", Rt, local)
 
 
+def _glb_add_cameras(gltf, node, binary, extrinsic, height):
+    """One TRIANGLES primitive per camera (camera_frusta of the given height, CAMERA_COLORS cycled, double-sided) appended to mesh 0
+    of `gltf` under `node`. -> the binary chunk with the cameras' buffers behind what it held."""
+    import numpy as np
+    ext = extrinsic
+    ext = ext.detach().cpu().numpy() if isinstance(ext, torch.Tensor) else np.asarray(ext)
+    verts = camera_frusta(ext, height).astype("<f4")
+    S = len(verts)
+    if S:
+        binary += b"\0" * (-len(binary) % 4)
+        rgba = np.array([CAMERA_COLORS[i % len(CAMERA_COLORS)] + (255,) for i in range(S)], np.uint8)
+        parts = [verts.tobytes(), np.repeat(rgba[:, None, :], 5, axis=1).tobytes(), np.tile(np.array(_FRUSTUM_FACES, "<u2"), S).tobytes()]
+        views, accs = gltf.setdefault("bufferViews", []), gltf.setdefault("accessors", [])
+        prims = gltf.setdefault("meshes", [{"primitives": []}])[0]["primitives"]
+        v0 = len(views)
+        for part, target in zip(parts, (34962, 34962, 34963)):
+            views.append({"buffer": 0, "byteOffset": len(binary), "byteLength": len(part), "target": target})
+            binary += part
+        gltf["materials"] = [{"doubleSided": True}]
+        for i in range(S):
+            a0 = len(accs)
+            accs += [{"bufferView": v0, "byteOffset": 60 * i, "componentType": 5126, "count": 5, "type": "VEC3",
+                      "min": [float(v) for v in verts[i].min(axis=0)], "max": [float(v) for v in verts[i].max(axis=0)]},
+                     {"bufferView": v0 + 1, "byteOffset": 20 * i, "componentType": 5121, "normalized": True, "count": 5, "type": "VEC4"},
+                     {"bufferView": v0 + 2, "byteOffset": 36 * i, "componentType": 5123, "count": 18, "type": "SCALAR"}]
+            prims.append({"attributes": {"POSITION": a0, "COLOR_0": a0 + 1}, "indices": a0 + 2, "mode": 4, "material": 0})
+        node["mesh"] = 0
+        gltf["buffers"] = [{"byteLength": len(binary)}]
+    return binary
+
+
+def _glb_write(path, gltf, binary):
+    """The GLB container: header, the JSON chunk padded with spaces, the binary chunk padded with zeros (when there is one)."""
+    import json
+    import struct
+    js = json.dumps(gltf, separators=(",", ":")).encode("utf-8")
+    js += b" " * (-len(js) % 4)
+    binary += b"\0" * (-len(binary) % 4)
+    chunks = struct.pack("<II", len(js), 0x4E4F534A) + js
+    if binary:
+        chunks += struct.pack("<II", len(binary), 0x004E4942) + binary
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<III", 0x46546C67, 2, 12 + len(chunks)))
+        fh.write(chunks)
+
+
 def write_glb(path, cloud, cameras=False, camera_scale=0.05):
     """glTF 2.0 binary of the cloud: one POINTS primitive with POSITION (f32 VEC3, with the min / max the spec requires) and COLOR_0
     (normalized u8 VEC4, alpha 255), under one node whose `matrix` is cloud.transform (column-major, as glTF stores it). The vertices
@@ -1728,8 +1774,6 @@ def write_glb(path, cloud, cameras=False, camera_scale=0.05):
     camera_scale * cloud.scene_scale, in one flat colour per camera from CAMERA_COLORS (cycled), double-sided. This follows the
     reference's placement and size rule (visual_util.py:270-318); the reference builds its cones with trimesh, so the files are not
     compared byte-wise. With cameras=False the file is what it was without the argument."""
-    import json
-    import struct
     import numpy as np
     pts, col = _host_cloud(cloud)
     M = len(pts)
@@ -1750,39 +1794,8 @@ def write_glb(path, cloud, cameras=False, camera_scale=0.05):
                               "min": [float(v) for v in pts.min(axis=0)], "max": [float(v) for v in pts.max(axis=0)]},
                              {"bufferView": 1, "componentType": 5121, "normalized": True, "count": M, "type": "VEC4"}]
     if cameras:
-        ext = cloud.extrinsic
-        ext = ext.detach().cpu().numpy() if isinstance(ext, torch.Tensor) else np.asarray(ext)
-        verts = camera_frusta(ext, float(camera_scale) * float(cloud.scene_scale)).astype("<f4")
-        S = len(verts)
-        if S:
-            binary += b"\0" * (-len(binary) % 4)
-            rgba = np.array([CAMERA_COLORS[i % len(CAMERA_COLORS)] + (255,) for i in range(S)], np.uint8)
-            parts = [verts.tobytes(), np.repeat(rgba[:, None, :], 5, axis=1).tobytes(), np.tile(np.array(_FRUSTUM_FACES, "<u2"), S).tobytes()]
-            views, accs = gltf.setdefault("bufferViews", []), gltf.setdefault("accessors", [])
-            prims = gltf.setdefault("meshes", [{"primitives": []}])[0]["primitives"]
-            v0 = len(views)
-            for part, target in zip(parts, (34962, 34962, 34963)):
-                views.append({"buffer": 0, "byteOffset": len(binary), "byteLength": len(part), "target": target})
-                binary += part
-            gltf["materials"] = [{"doubleSided": True}]
-            for i in range(S):
-                a0 = len(accs)
-                accs += [{"bufferView": v0, "byteOffset": 60 * i, "componentType": 5126, "count": 5, "type": "VEC3",
-                          "min": [float(v) for v in verts[i].min(axis=0)], "max": [float(v) for v in verts[i].max(axis=0)]},
-                         {"bufferView": v0 + 1, "byteOffset": 20 * i, "componentType": 5121, "normalized": True, "count": 5, "type": "VEC4"},
-                         {"bufferView": v0 + 2, "byteOffset": 36 * i, "componentType": 5123, "count": 18, "type": "SCALAR"}]
-                prims.append({"attributes": {"POSITION": a0, "COLOR_0": a0 + 1}, "indices": a0 + 2, "mode": 4, "material": 0})
-            node["mesh"] = 0
-            gltf["buffers"] = [{"byteLength": len(binary)}]
-    js = json.dumps(gltf, separators=(",", ":")).encode("utf-8")
-    js += b" " * (-len(js) % 4)
-    binary += b"\0" * (-len(binary) % 4)
-    chunks = struct.pack("<II", len(js), 0x4E4F534A) + js
-    if binary:
-        chunks += struct.pack("<II", len(binary), 0x004E4942) + binary
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<III", 0x46546C67, 2, 12 + len(chunks)))
-        fh.write(chunks)
+        binary = _glb_add_cameras(gltf, node, binary, cloud.extrinsic, float(camera_scale) * float(cloud.scene_scale))
+    _glb_write(path, gltf, binary)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -1916,3 +1929,394 @@ def write_png(path, image):
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
         raise ValueError("write_png: expected one (H, W, 3) uint8 image, got %s %r" % (a.dtype, a.shape))
     Image.fromarray(np.ascontiguousarray(a)).save(path, format="PNG")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Volumetric fusion: depth maps into a TSDF volume, one mesh from its zero level (ovg_tsdf_integrate, ovg_tsdf_extract)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+TSDF_MAX_VOXELS = 1 << 28          # lattice points tsdf_volume allocates at most: 2 GiB of tsdf + weight, 4 GiB more with colours
+TSDF_TRUNC_VOXELS = 4.0            # the default truncation distance in voxels
+TSDF_MAX_WEIGHT = 64.0             # the default clamp of a lattice point's weight
+
+
+class TSDFVolume:
+    """A dense truncated signed-distance volume on the device: tsdf, weight (nz,ny,nx) f32 and color (nz,ny,nx,4) f32 (r, g, b in
+    [0, 255] and the colour weight) or None; origin (three floats, float32 values: the position of lattice point (0, 0, 0)),
+    voxel_size and trunc (floats, float32 values), dims = (nx, ny, nz). Lattice point (i, j, k) lies at origin + voxel_size (i, j, k).
+    transform ((4,4) float64 numpy or None), extrinsic and scene_scale travel to the meshes extracted from it, for the writers."""
+    __slots__ = ("tsdf", "weight", "color", "origin", "voxel_size", "trunc", "dims", "transform", "extrinsic", "scene_scale")
+
+    def __init__(self, tsdf, weight, color, origin, voxel_size, trunc, dims, transform=None, extrinsic=None, scene_scale=None):
+        self.tsdf, self.weight, self.color, self.origin, self.voxel_size, self.trunc, self.dims = tsdf, weight, color, origin, voxel_size, trunc, dims
+        self.transform, self.extrinsic, self.scene_scale = transform, extrinsic, scene_scale
+
+
+class Mesh:
+    """Result of tsdf_extract: vertices (M,3) f32, faces (F,3) int32 (indices into vertices, triangle normals pointing from inside to
+    outside), normals (M,3) f32 and colors (M,3) u8 device tensors; transform the (4,4) float64 numpy alignment the writers apply
+    (identity when the volume carries none); extrinsic (S,3,4) and scene_scale for write_mesh_glb's cameras, or None."""
+    __slots__ = ("vertices", "faces", "normals", "colors", "transform", "extrinsic", "scene_scale")
+
+    def __init__(self, vertices, faces, normals, colors, transform, extrinsic=None, scene_scale=None):
+        self.vertices, self.faces, self.normals, self.colors, self.transform = vertices, faces, normals, colors, transform
+        self.extrinsic, self.scene_scale = extrinsic, scene_scale
+
+
+def _tsdf_positive(what, name, value):
+    import math
+    import numpy as np
+    try:
+        with np.errstate(over="ignore"):
+            v = float(np.float32(value))
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (v > 0.0 and math.isfinite(v)):
+        raise ValueError("%s: %s must be positive and finite in float32, got %r" % (what, name, value))
+    return v
+
+
+def tsdf_volume(origin, voxel_size, dims, trunc=None, color=True, device="cuda", max_voxels=TSDF_MAX_VOXELS):
+    """A fresh TSDFVolume (tsdf 1, everything else 0) of dims = (nx, ny, nz) lattice points with its point (0, 0, 0) at `origin`.
+    trunc: the truncation distance in world units, TSDF_TRUNC_VOXELS voxels by default. A volume above max_voxels lattice points
+    (TSDF_MAX_VOXELS by default; 2^31 - 1 at the most) is refused with a ValueError that names its size."""
+    import math
+    import numpy as np
+    what = "tsdf_volume"
+    try:
+        o = [float(np.float32(v)) for v in origin]
+    except (TypeError, ValueError):
+        o = []
+    if len(o) != 3 or not all(math.isfinite(v) for v in o):
+        raise ValueError("%s: origin must be three finite numbers, got %r" % (what, origin))
+    voxel = _tsdf_positive(what, "voxel_size", voxel_size)
+    trunc = _tsdf_positive(what, "trunc", TSDF_TRUNC_VOXELS * voxel if trunc is None else trunc)
+    try:
+        d = tuple(dims)
+    except TypeError:
+        d = ()
+    if len(d) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in d):
+        raise ValueError("%s: dims must be three positive integers (nx, ny, nz), got %r" % (what, dims))
+    nx, ny, nz = (int(v) for v in d)
+    if isinstance(max_voxels, bool) or not isinstance(max_voxels, int) or max_voxels < 1:
+        raise ValueError("%s: max_voxels must be a positive integer, got %r" % (what, max_voxels))
+    if nx * ny * nz > min(max_voxels, (1 << 31) - 1):
+        raise ValueError("%s: %d x %d x %d = %d lattice points exceed max_voxels = %d (%.1f GiB of volume state): use a larger voxel_size "
+                         "or a smaller resolution" % (what, nx, ny, nz, nx * ny * nz, min(max_voxels, (1 << 31) - 1),
+                                                       nx * ny * nz * (24 if color else 8) / 2.0 ** 30))
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ops.L.OvgError("tsdf_volume needs a HIP device: there is no CPU fallback")
+    return TSDFVolume(torch.ones(nz, ny, nx, device=dev, dtype=torch.float32), torch.zeros(nz, ny, nx, device=dev, dtype=torch.float32),
+                      torch.zeros(nz, ny, nx, 4, device=dev, dtype=torch.float32) if color else None, tuple(o), voxel, trunc, (nx, ny, nz))
+
+
+def tsdf_volume_for(points_or_cloud, voxel_size=None, resolution=256, margin=TSDF_TRUNC_VOXELS, valid=None, trunc=None, color=True,
+                    max_voxels=TSDF_MAX_VOXELS):
+    """A fresh TSDFVolume round a PointCloud or a (..., 3) f32 device tensor of points (e.g. world_points_from_depth): the bounds of
+    the finite points (those with valid != 0 when a bool / u8 tensor of the leading shape is given) by torch reductions, `margin`
+    voxels (rounded up to whole voxels) added on every side so that the free space in front of a surface is part of the volume.
+    voxel_size None: the longest side, margins included, spans `resolution` lattice points. One device -> host read-back: the six
+    bounds. A PointCloud hands its transform, cameras and scene scale on to the volume. ValueError for bad arguments, no finite
+    point, or a volume above max_voxels; OvgError for CPU tensors."""
+    import math
+    import numpy as np
+    what = "tsdf_volume_for"
+    cloud = points_or_cloud if isinstance(points_or_cloud, PointCloud) else None
+    pts = cloud.points if cloud is not None else points_or_cloud
+    if not isinstance(pts, torch.Tensor) or pts.dtype != torch.float32 or pts.dim() < 2 or pts.shape[-1] != 3:
+        raise ValueError("%s: expected a PointCloud or a float32 tensor (..., 3)" % what)
+    if valid is not None and (not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8)
+                              or tuple(valid.shape) != tuple(pts.shape[:-1])):
+        raise ValueError("%s: valid must be a bool / uint8 tensor %r" % (what, tuple(pts.shape[:-1])))
+    if voxel_size is not None:
+        voxel_size = _tsdf_positive(what, "voxel_size", voxel_size)
+    if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not (0 <= margin <= 1024):
+        raise ValueError("%s: margin must be a number of voxels in [0, 1024], got %r" % (what, margin))
+    pad = int(math.ceil(margin))
+    if isinstance(resolution, bool) or not isinstance(resolution, (int, np.integer)) or not 2 * pad + 2 <= resolution < 1 << 31:
+        raise ValueError("%s: resolution must be an integer >= 2 * margin + 2 = %d, got %r" % (what, 2 * pad + 2, resolution))
+    if not pts.is_cuda or (valid is not None and not valid.is_cuda):
+        raise ops.L.OvgError("tsdf_volume_for needs HIP device tensors: there is no CPU fallback")
+    p = pts.reshape(-1, 3)
+    ok = torch.isfinite(p).all(dim=1)
+    if valid is not None:
+        ok = ok & (valid.reshape(-1) != 0)
+    inf = torch.full((), float("inf"), device=p.device, dtype=torch.float32)
+    lo = torch.where(ok[:, None], p, inf).amin(dim=0) if p.shape[0] else inf.expand(3)
+    hi = torch.where(ok[:, None], p, -inf).amax(dim=0) if p.shape[0] else (-inf).expand(3)
+    b = torch.cat([lo, hi]).double().cpu().numpy()                          # the one read-back
+    if not np.isfinite(b).all():
+        raise ValueError("%s: no finite point to bound the volume with" % what)
+    lo, extent = b[:3], b[3:] - b[:3]
+    if voxel_size is None:
+        voxel_size = float(np.float32(max(float(extent.max()), 1e-30) / (int(resolution) - 1 - 2 * pad)))
+        voxel_size = _tsdf_positive(what, "the voxel size derived from the bounds", voxel_size)
+    # 1e-4 of a voxel of slack: a voxel size derived from the longest side (and rounded to float32) spans exactly `resolution` points
+    dims = tuple(int(math.ceil(float(e) / voxel_size - 1e-4)) + 1 + 2 * pad for e in extent)
+    vol = tsdf_volume([float(v) - pad * voxel_size for v in lo], voxel_size, dims, trunc=trunc, color=color, device=p.device,
+                      max_voxels=max_voxels)
+    if cloud is not None:
+        vol.transform, vol.extrinsic, vol.scene_scale = cloud.transform, cloud.extrinsic, cloud.scene_scale
+    return vol
+
+
+def _tsdf_colors(images, S, H, W):
+    """(S,H,W,3) u8 from (S,3,H,W) floats in [0, 1] by ovg_point_filter's colour rule u8(trunc(clamp(x * 255f, 0, 255))), NaN as 0;
+    (S,H,W,3) u8 as it is."""
+    if isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and tuple(images.shape) == (S, H, W, 3):
+        return images.contiguous()
+    if isinstance(images, torch.Tensor) and images.is_floating_point() and tuple(images.shape) == (S, 3, H, W):
+        x = torch.nan_to_num(images.float() * 255.0, nan=0.0, posinf=255.0, neginf=0.0).clamp(0.0, 255.0)
+        return x.to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+    raise ValueError("tsdf_integrate: images must be (S, 3, H, W) = (%d, 3, %d, %d) floats in [0, 1] or (S, H, W, 3) uint8" % (S, H, W))
+
+
+def tsdf_integrate(volume, depth, extrinsic, intrinsic, images=None, weight=None, valid=None, near=1e-3, max_weight=TSDF_MAX_WEIGHT,
+                   views=None):
+    """Averages S depth maps with their cameras into the volume on the device (ovg_tsdf_integrate), in place; -> the volume.
+    Every lattice point is projected into each view (the projection of render_point_cloud, nearest pixel) and compared with the
+    z-depth d the view holds there: sdf = d - zc. A point more than `trunc` behind the surface is hidden and left alone; otherwise
+    min(sdf / trunc, 1) enters the running weighted mean of the point, so a view that sees through a point (a floater of another
+    view) pulls it towards free space. The rule is exact (tests/tsdf_twin.py restates it in numpy float32): views are taken in
+    ascending order, two calls give identical bytes, and integrating views [0, k) and then [k, S) gives the bytes of one call.
+
+    depth: (S,H,W) or (S,H,W,1) f32 device tensor (predictions["depth"][b]). extrinsic (S,3,4) world-to-camera, intrinsic (S,3,3) or
+    one (3,3): device tensors, numpy arrays or lists, rounded to f32. images: (S,3,H,W) floats in [0, 1] or (S,H,W,3) u8 colours for a
+    volume with colours; only observations within `trunc` of the surface colour a point. weight: optional (S,H,W) f32 per-pixel
+    observation weights (pixels whose weight is not finite and > 0 are skipped); valid: optional (S,H,W) bool / u8; pixels with a
+    depth that is not finite or <= near are skipped as well. max_weight clamps a point's accumulated weight. views: None for all, or
+    (first, count) / a range of consecutive views. ValueError for shapes and values, OvgError for CPU tensors: no CPU fallback."""
+    import numpy as np
+    what = "tsdf_integrate"
+    if not isinstance(volume, TSDFVolume):
+        raise ValueError("%s: expected a TSDFVolume" % what)
+    if isinstance(depth, torch.Tensor) and depth.dim() == 4 and depth.shape[-1] == 1:
+        depth = depth[..., 0]
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or 0 in depth.shape or not depth.is_floating_point():
+        raise ValueError("%s: depth must be a (S, H, W) or (S, H, W, 1) float tensor" % what)
+    S, H, W = (int(v) for v in depth.shape)
+    if S * H * W >= 1 << 31:
+        raise ValueError("%s: S = %d views of %d x %d exceed S * H * W < 2^31" % (what, S, H, W))
+    ext, intr = torch.as_tensor(extrinsic).detach(), torch.as_tensor(intrinsic).detach()
+    if tuple(ext.shape) != (S, 3, 4):
+        raise ValueError("%s: extrinsic must be (S, 3, 4) = (%d, 3, 4), got %r" % (what, S, tuple(ext.shape)))
+    if tuple(intr.shape) not in ((3, 3), (S, 3, 3)):
+        raise ValueError("%s: intrinsic must be (3, 3) or (S, 3, 3) = (%d, 3, 3), got %r" % (what, S, tuple(intr.shape)))
+    if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (S, H, W)
+                              or valid.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError("%s: valid must be a bool / uint8 tensor (S, H, W) = %r" % (what, (S, H, W)))
+    if weight is not None and (not isinstance(weight, torch.Tensor) or tuple(weight.shape) != (S, H, W) or not weight.is_floating_point()):
+        raise ValueError("%s: weight must be a float tensor (S, H, W) = %r" % (what, (S, H, W)))
+    colors = None
+    if images is not None:
+        if volume.color is None:
+            raise ValueError("%s: images need a volume with colours" % what)
+        colors = _tsdf_colors(images, S, H, W)
+    near32, max_weight32 = _tsdf_positive(what, "near", near), _tsdf_positive(what, "max_weight", max_weight)
+    if views is None:
+        first, count = 0, S
+    else:
+        if isinstance(views, range):
+            views = (views.start, len(views)) if views.step == 1 else None
+        if not isinstance(views, (tuple, list)) or len(views) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in views):
+            raise ValueError("%s: views must be None, (first, count) or a range of consecutive views" % what)
+        first, count = int(views[0]), int(views[1])
+        if not (0 <= first < S and 0 < count <= S - first):
+            raise ValueError("%s: views %d .. %d outside [0, %d)" % (what, first, first + count - 1, S))
+    for t in (volume.tsdf, depth, valid, weight, colors):
+        if t is not None and not t.is_cuda:
+            raise ops.L.OvgError("tsdf_integrate needs HIP device tensors: there is no CPU fallback")
+    dev = volume.tsdf.device
+    cams = _pack_cams(ext, intr, S, dev)
+    if valid is not None:
+        valid = (valid.to(torch.uint8) if valid.dtype == torch.bool else valid).contiguous()
+    ops.tsdf_integrate(volume.tsdf, volume.weight, depth.float().contiguous(), cams, volume.origin, volume.voxel_size, volume.trunc,
+                       max_weight=max_weight32, near=near32, color=volume.color, valid=valid,
+                       obs_weight=None if weight is None else weight.float().contiguous(), colors=colors, view_first=first, view_count=count)
+    return volume
+
+
+def tsdf_extract(volume, min_weight=1.0):
+    """The mesh of the volume's zero level by naive surface nets on the device (ovg_tsdf_extract): one vertex per cell whose 8 corners
+    carry at least `min_weight` and differ in sign, at the mean of the cell's edge crossings, one quad (two triangles) per
+    sign-changing lattice edge whose four cells are all there. Normals are the normalised gradient of the cell (inside to outside),
+    colours the mean of the coloured corners (128 grey without any). Deterministic: vertices in ascending cell index, faces in
+    ascending (lattice index, axis); tests/tsdf_twin.py restates the rule. One device -> host read-back: the two counts.
+    -> Mesh; a volume without a crossing, or with an axis of length 1, gives an empty one."""
+    import numpy as np
+    L = ops.L
+    if not isinstance(volume, TSDFVolume):
+        raise ValueError("tsdf_extract: expected a TSDFVolume")
+    min_weight = _tsdf_positive("tsdf_extract", "min_weight", min_weight)
+    if not volume.tsdf.is_cuda:
+        raise L.OvgError("tsdf_extract needs HIP device tensors: there is no CPU fallback")
+    dev = volume.tsdf.device
+    nx, ny, nz = volume.dims
+    ws = torch.empty(ops.tsdf_extract_workspace_bytes(nx, ny, nz), device=dev, dtype=torch.uint8)
+    count = torch.empty(2, device=dev, dtype=torch.int64)
+    args = dict(tsdf=volume.tsdf, weight=volume.weight, origin=volume.origin, voxel=volume.voxel_size, ws=ws, min_weight=min_weight,
+                color=volume.color, out_count=count)
+    ops.tsdf_extract(L.TSDF_COUNT, **args)
+    M, Q = (int(v) for v in count.cpu().numpy())                            # the one synchronisation
+    vertices = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    normals = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    colors = torch.empty(M, 3, device=dev, dtype=torch.uint8)
+    faces = torch.empty(2 * Q, 3, device=dev, dtype=torch.int32)
+    if M:
+        ops.tsdf_extract(L.TSDF_SCATTER, vertex_capacity=M, quad_capacity=Q, vertices=vertices, normals=normals, colors=colors, faces=faces,
+                         **args)
+    transform = np.eye(4) if volume.transform is None else np.asarray(volume.transform, dtype=np.float64)
+    return Mesh(vertices, faces, normals, colors, transform, volume.extrinsic, volume.scene_scale)
+
+
+def mesh_to_point_cloud(mesh):
+    """A PointCloud of the mesh's vertices and colours (its transform and cameras carried over), for every function that takes a
+    cloud: normals, filters, clustering, registration, rendering, the point writers. scene_scale is the mesh's, else ||P95 - P5|| of
+    the vertices as predictions_to_point_cloud computes it (1 for an empty mesh)."""
+    if not isinstance(mesh, Mesh):
+        raise ValueError("mesh_to_point_cloud: expected a Mesh")
+    pts = mesh.vertices
+    if not pts.is_cuda:
+        raise ops.L.OvgError("mesh_to_point_cloud needs HIP device tensors: there is no CPU fallback")
+    M = int(pts.shape[0])
+    scale = mesh.scene_scale
+    if scale is None:
+        scale = ops.percentile(pts, M, 3, 1, 3, [5.0, 95.0], norm=True)[1] if M else torch.ones((), device=pts.device, dtype=torch.float32)
+    return PointCloud(pts, mesh.colors, torch.zeros((), device=pts.device, dtype=torch.float32), scale, mesh.transform, mesh.extrinsic)
+
+
+def fuse_predictions(predictions, batch_index=0, voxel_size=None, resolution=256, conf_thres=50.0, keep_mask=None, trunc=None,
+                     near=1e-3, max_weight=TSDF_MAX_WEIGHT, min_weight=1.0, min_conf=1e-5, color=True, margin=TSDF_TRUNC_VOXELS,
+                     max_voxels=TSDF_MAX_VOXELS):
+    """Fuses the S depth maps of the dict OmniVGGT.forward returns into one surface: tsdf_volume_for round the un-projected depth,
+    tsdf_integrate of `depth` with the cameras, tsdf_extract. -> (TSDFVolume, Mesh).
+    The choices are prediction_consistency's for the depth branch: `depth`, `depth_conf`, the cameras from `extrinsic` / `intrinsic`
+    of the dict, else decoded from pose_enc; world_points_from_depth (un-projected here when absent) bounds the volume. A pixel is
+    used when its confidence is >= the conf_thres-th percentile of depth_conf (numpy's linear percentile, as
+    predictions_to_point_cloud computes it; 0 or a dict without depth_conf skips the percentile) and > min_conf, and, with keep_mask
+    (an (S,H,W) bool device tensor, e.g. consistency_mask(...)), where that is True. Colours come from `images`. The mesh carries the
+    alignment inv(E0) @ diag(1,-1,-1,1) @ R_y(180) of the first camera, the cameras, and ||P95 - P5|| of its vertices as scene scale.
+    ValueError for bad arguments, OvgError for CPU tensors: there is no CPU fallback."""
+    what = "fuse_predictions"
+    if not isinstance(predictions, dict):
+        raise ValueError("predictions must be a dictionary")
+    images = predictions["images"]
+    if images.dim() == 4:
+        images = images.unsqueeze(0)
+    B = images.shape[0]
+    if not isinstance(batch_index, int) or not 0 <= batch_index < B:
+        raise ValueError("batch_index %r out of range for a batch of %d" % (batch_index, B))
+    b = batch_index
+    S, H, W = images.shape[1], images.shape[-2], images.shape[-1]
+    if keep_mask is not None and (not isinstance(keep_mask, torch.Tensor) or keep_mask.dtype != torch.bool or tuple(keep_mask.shape) != (S, H, W)):
+        raise ValueError("keep_mask must be a bool tensor (S, H, W) = %r at the map size" % ((S, H, W),))
+    if conf_thres is None:
+        conf_thres = 10.0
+    if isinstance(conf_thres, bool) or not isinstance(conf_thres, (int, float)) or not 0.0 <= conf_thres <= 100.0:
+        raise ValueError("%s: conf_thres must be a percentile in [0, 100], got %r" % (what, conf_thres))
+    if "depth" not in predictions:
+        raise ValueError("%s: predictions carry no `depth`" % what)
+    if not images.is_cuda or (keep_mask is not None and not keep_mask.is_cuda):
+        raise ops.L.OvgError("fuse_predictions needs HIP device tensors: there is no CPU fallback")
+    pts, conf, extrinsic, intrinsic = _prediction_geometry(predictions, "Depthmap and Camera Branch", b, images, want_intrinsic=True)
+    depth = predictions["depth"][b].reshape(S, H, W).float().contiguous()
+    valid = torch.isfinite(depth) & (depth > float(near))
+    if conf is not None:
+        cf = conf[b].reshape(-1).float().contiguous()
+        ok = cf > float(min_conf)
+        if conf_thres != 0.0:
+            ok = ok & (cf >= ops.percentile(cf, cf.numel(), 1, 0, 1, [float(conf_thres)]).reshape(()))
+        valid = valid & ok.reshape(S, H, W)
+    if keep_mask is not None:
+        valid = valid & keep_mask
+    volume = tsdf_volume_for(pts.reshape(S, H, W, 3).float(), voxel_size=voxel_size, resolution=resolution, margin=margin, valid=valid,
+                             trunc=trunc, color=color, max_voxels=max_voxels)
+    volume.extrinsic = extrinsic
+    volume.transform = scene_alignment(extrinsic[0].detach().double().cpu().numpy())
+    tsdf_integrate(volume, depth, extrinsic, intrinsic, images=images[b].reshape(S, 3, H, W) if color else None, valid=valid, near=near,
+                   max_weight=max_weight)
+    mesh = tsdf_extract(volume, min_weight=min_weight)
+    M = int(mesh.vertices.shape[0])
+    scale = ops.percentile(mesh.vertices, M, 3, 1, 3, [5.0, 95.0], norm=True)[1] if M else torch.ones((), device=depth.device, dtype=torch.float32)
+    volume.scene_scale = mesh.scene_scale = scale
+    return volume, mesh
+
+
+def _host_mesh(mesh, apply_transform):
+    """Host arrays of a mesh: vertices f32, normals f32, colours u8, faces int32; under apply_transform the vertices are mapped by
+    mesh.transform in float64 and the normals by the inverse transpose of its linear part, renormalised (write_ply's rule)."""
+    import numpy as np
+    if not isinstance(mesh, Mesh):
+        raise ValueError("expected a Mesh")
+    pts = mesh.vertices.detach().cpu().numpy().astype(np.float32).reshape(-1, 3)
+    nrm = mesh.normals.detach().cpu().numpy().astype(np.float32).reshape(-1, 3)
+    col = mesh.colors.detach().cpu().numpy().astype(np.uint8).reshape(-1, 3)
+    faces = mesh.faces.detach().cpu().numpy().astype(np.int32).reshape(-1, 3)
+    if apply_transform and len(pts):
+        T = np.asarray(mesh.transform, dtype=np.float64)
+        pts = (pts.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+        n64 = nrm.astype(np.float64) @ np.linalg.inv(T[:3, :3])
+        length = np.sqrt((n64 * n64).sum(1, keepdims=True))
+        nrm = np.where(length > 0, n64 / np.where(length > 0, length, 1.0), 0.0).astype(np.float32)
+    return pts, nrm, col, faces
+
+
+def write_mesh_ply(path, mesh, apply_transform=True):
+    """Binary little-endian PLY of the mesh: `x y z nx ny nz` float and `red green blue` uchar per vertex, then one
+    `list uchar int vertex_indices` of three per face. apply_transform as in write_ply: vertices by mesh.transform in float64, normals
+    by the inverse transpose of its linear part. An empty mesh writes a valid file with no vertices and no faces."""
+    import numpy as np
+    pts, nrm, col, faces = _host_mesh(mesh, apply_transform)
+    if apply_transform and len(faces) and np.linalg.det(np.asarray(mesh.transform, dtype=np.float64)[:3, :3]) < 0:
+        faces = faces[:, ::-1]                                              # a mirroring transform turns the winding round
+    rec = np.empty(len(pts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                                    ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    for k, name in enumerate(("x", "y", "z")):
+        rec[name], rec["n" + name] = pts[:, k], nrm[:, k]
+    rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    frec = np.empty(len(faces), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec["n"], frec["v"] = 3, faces
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+              "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(pts), len(faces)))
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(rec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def write_mesh_glb(path, mesh, cameras=False, camera_scale=0.05):
+    """glTF 2.0 binary of the mesh: one indexed TRIANGLES primitive with POSITION (f32 VEC3 with min / max), NORMAL (f32 VEC3),
+    COLOR_0 (normalized u8 VEC4, alpha 255) and u32 indices, under one node whose `matrix` is mesh.transform (column-major), as
+    write_glb places its cloud: the vertices stay untransformed. An empty mesh writes a node without a mesh. cameras=True adds
+    write_glb's pyramids for mesh.extrinsic, of height camera_scale * mesh.scene_scale, to the same mesh under the same node."""
+    import numpy as np
+    pts, nrm, col, faces = _host_mesh(mesh, False)
+    M = len(pts)
+    node = {"matrix": [float(v) for v in np.asarray(mesh.transform, dtype=np.float64).T.reshape(-1)]}
+    gltf = {"asset": {"version": "2.0", "generator": "omnivggt_official_amd.postprocess"}, "scene": 0, "scenes": [{"nodes": [0]}],
+            "nodes": [node]}
+    binary = b""
+    if M and len(faces):
+        rgba = np.concatenate([col, np.full((M, 1), 255, np.uint8)], axis=1)
+        parts = [pts.astype("<f4").tobytes(), nrm.astype("<f4").tobytes(), rgba.tobytes(), faces.astype("<u4").tobytes()]
+        views, off = [], 0
+        for part, target in zip(parts, (34962, 34962, 34962, 34963)):
+            views.append({"buffer": 0, "byteOffset": off, "byteLength": len(part), "target": target})
+            off += len(part)                                                # every part is a multiple of 4 bytes long
+        binary = b"".join(parts)
+        node["mesh"] = 0
+        gltf["meshes"] = [{"primitives": [{"attributes": {"POSITION": 0, "NORMAL": 1, "COLOR_0": 2}, "indices": 3, "mode": 4}]}]
+        gltf["buffers"] = [{"byteLength": len(binary)}]
+        gltf["bufferViews"] = views
+        gltf["accessors"] = [{"bufferView": 0, "componentType": 5126, "count": M, "type": "VEC3",
+                              "min": [float(v) for v in pts.min(axis=0)], "max": [float(v) for v in pts.max(axis=0)]},
+                             {"bufferView": 1, "componentType": 5126, "count": M, "type": "VEC3"},
+                             {"bufferView": 2, "componentType": 5121, "normalized": True, "count": M, "type": "VEC4"},
+                             {"bufferView": 3, "componentType": 5125, "count": 3 * len(faces), "type": "SCALAR"}]
+    if cameras:
+        if mesh.extrinsic is None or mesh.scene_scale is None:
+            raise ValueError("write_mesh_glb: cameras=True needs a mesh with extrinsic and scene_scale")
+        binary = _glb_add_cameras(gltf, node, binary, mesh.extrinsic, float(camera_scale) * float(mesh.scene_scale))
+    _glb_write(path, gltf, binary)
