@@ -69,7 +69,8 @@ extern "C" {
  *     + plane segmentation by RANSAC (ovg_plane_hypotheses, ovg_plane_score, ovg_plane_select, ovg_plane_mask, ovg_plane_fit): added
  *       the same way
  *     + volumetric fusion: depth maps into a TSDF volume and a surface-nets mesh of its zero level (ovg_tsdf_integrate,
- *       ovg_tsdf_extract, ovg_tsdf_extract_workspace_bytes): added the same way */
+ *       ovg_tsdf_extract, ovg_tsdf_extract_workspace_bytes): added the same way
+ *     + mesh rasterisation: z-buffered, shaded triangles (ovg_render_mesh, ovg_render_mesh_workspace_bytes): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -657,6 +658,63 @@ typedef struct {
 } ovg_render_params;
 int64_t ovg_render_workspace_bytes(int32_t V, int32_t H, int32_t W);
 int ovg_render_points(const ovg_render_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Mesh rasterisation (added under ABI 13): z-buffered triangles of a mesh into V pinhole views with per-pixel shading, by an exact
+ * rule that tests/raster_twin.py restates in numpy bit for bit. Every float operation below is one IEEE operation rounded on its own
+ * (no fused multiply-add); the divisions and the square root are correctly rounded.
+ *   vertices [M][3] f32, faces [F][3] int32, normals [M][3] f32 or NULL, colors [M][3] u8 or NULL, M and F < 2^31 (vertices may be
+ *   NULL when M == 0, faces when F == 0); cams [V][16] f32 packed as for ovg_render_points. Per view v and face f:
+ *   1. a face with a vertex index outside [0, M) is skipped (checked on the device: never an out-of-bounds read);
+ *   2. per vertex xc, yc, zc by rules 1-2 of ovg_render_points (f32; the vertex is usable when they are finite and zc > near), then
+ *      sx = fx (xc / zc) + cx, sy = fy (yc / zc) + cy in f32; usable only when -16384 <= sx, sy <= 16384 (compared in f32: NaN
+ *      fails). X = (int) floor(sx 256 + 0.5), Y likewise: 8 bits of sub-pixel fixed point (the scaling is exact, the addition is the
+ *      one rounding). A face with an unusable vertex is not drawn in that view: there is no near-plane and no guard-band clipping;
+ *   3. in int64: area = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0); area == 0 is skipped. With x to the right and y down a face whose
+ *      outward normal looks at the camera has area < 0. cull: OVG_MESH_CULL_NONE draws both sides, OVG_MESH_CULL_BACK drops area > 0,
+ *      OVG_MESH_CULL_FRONT drops area < 0. The box is ceil(min / 256) .. floor(max / 256) per axis, intersected with the frame;
+ *   4. the centre of pixel (px, py) is (256 px, 256 py). w0 is the edge function over edge 1 -> 2, w1 over 2 -> 0, w2 over 0 -> 1
+ *      (w2 = (X1 - X0)(py' - Y0) - (Y1 - Y0)(px' - X0), the others by rotating the indices), negated when area < 0, so that
+ *      w0 + w1 + w2 = |area|. A pixel of the box is covered when all three are >= 0, inclusive: pixels on a shared edge are covered
+ *      by both faces, and depth, then the face index decide. Inside the box every difference is below 2^23 + 2 and every product
+ *      below 2^47: exact in int64 and in f64;
+ *   5. in f64: li = (double) wi / (double) |area|, ri = 1.0 / (double) zci, ai = li ri, iz = (a0 + a1) + a2, zf = 1.0 / iz,
+ *      z = (float) zf: positive and finite, so its bits never reach 0xFFFFFFFF. key = bits(z) << 32 | f; every covered pixel takes
+ *      the minimum of its keys by one 64-bit unsigned atomic min; ~0 means "empty";
+ *   6. per non-empty pixel steps 2-5 are computed again for the winning face. bi = ai zf are the perspective-correct weights and an
+ *      attribute q interpolates as (b0 q0 + b1 q1) + b2 q2 in f64. c: the interpolated vertex colour, 128 per channel when colors is
+ *      NULL. n: the interpolated vertex normal; when normals is NULL the face normal e1 x e2 of e1 = p1 - p0, e2 = p2 - p0 (f64
+ *      differences of the f32 world vertices, each component two products and one subtraction). len = sqrt((nx nx + ny ny) + nz nz);
+ *      s = |(nx c6 + ny c7) + nz c8| / len with (c6, c7, c8) the camera's optical axis (the third rotation row), s = 1 unless len is
+ *      finite and > 0. OVG_MESH_SHADE_COLOR: floor(c + 0.5); OVG_MESH_SHADE_HEADLIGHT: floor((0.25 + 0.75 s) c + 0.5);
+ *      OVG_MESH_SHADE_NORMAL: floor((0.5 (nk / len) + 0.5) 255 + 0.5) per component k, or 128 when len is not finite and > 0; all
+ *      clamped to [0, 255]. depth = z, index = f; an empty pixel takes the background colour, depth 0 and index -1.
+ *   Three launches (fill, draw, resolve); nothing is allocated and nothing is read back. The draw kernel runs one thread per face: a
+ *   face whose clipped box holds at most coop_threshold pixels (0: the library's default) is walked by its own lane, a larger one by
+ *   the 64 lanes of its wave together. The images do not depend on coop_threshold.
+ *   ws: >= ovg_render_mesh_workspace_bytes(V, H, W) bytes (the u64 z-buffer, 8 V H W rounded up to 16), 16-byte aligned; the query
+ *   returns -1 outside ovg_render_points' shape limits (V, H, W <= 0 or V H W >= 2^31). out_rgb [V][H][W][3] u8; out_depth [V][H][W]
+ *   f32 and out_index [V][H][W] int64 are optional.
+ *   OVG_E_ARG: NULL params / cams / ws / out_rgb, NULL vertices with M > 0 or faces with F > 0, M or F negative or >= 2^31, bad V, H, W,
+ *   a near plane that is not positive and finite, unknown shading or cull, flags other than 0, a negative coop_threshold, a misaligned
+ *   or undersized workspace.
+ * ------------------------------------------------------------------ */
+enum { OVG_MESH_SHADE_COLOR = 0, OVG_MESH_SHADE_HEADLIGHT = 1, OVG_MESH_SHADE_NORMAL = 2 };
+enum { OVG_MESH_CULL_NONE = 0, OVG_MESH_CULL_BACK = 1, OVG_MESH_CULL_FRONT = 2 };
+typedef struct {
+  const float* vertices; const int32_t* faces; const float* normals; const uint8_t* colors;
+  int64_t M; int64_t F;
+  const float* cams;
+  int32_t V; int32_t H; int32_t W; int32_t shading;
+  int32_t cull; int32_t coop_threshold;
+  float near;
+  uint8_t background[3]; uint8_t pad0;
+  int32_t flags; int32_t pad1;
+  void* ws; int64_t ws_bytes;
+  uint8_t* out_rgb; float* out_depth; int64_t* out_index;
+} ovg_render_mesh_params;
+int64_t ovg_render_mesh_workspace_bytes(int32_t V, int32_t H, int32_t W);
+int ovg_render_mesh(const ovg_render_mesh_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Multi-view depth consistency (added under ABI 13): for every pixel of S point maps, the number of OTHER views that confirm it, look

@@ -220,6 +220,17 @@ class RenderParams(C.Structure):
                 ("ws", vp), ("ws_bytes", i64), ("out_rgb", vp), ("out_depth", vp), ("out_index", vp)]
 
 
+MESH_SHADE_COLOR, MESH_SHADE_HEADLIGHT, MESH_SHADE_NORMAL = 0, 1, 2
+MESH_CULL_NONE, MESH_CULL_BACK, MESH_CULL_FRONT = 0, 1, 2
+
+
+class RenderMeshParams(C.Structure):
+    _fields_ = [("vertices", vp), ("faces", vp), ("normals", vp), ("colors", vp), ("M", i64), ("F", i64), ("cams", vp),
+                ("V", i32), ("H", i32), ("W", i32), ("shading", i32), ("cull", i32), ("coop_threshold", i32), ("near", f32),
+                ("background", C.c_uint8 * 3), ("pad0", C.c_uint8), ("flags", i32), ("pad1", i32),
+                ("ws", vp), ("ws_bytes", i64), ("out_rgb", vp), ("out_depth", vp), ("out_index", vp)]
+
+
 MVC_MAX_VIEWS = 32767
 MVC_TILE_DEFAULT, MVC_TILE_256x1, MVC_TILE_16x16, MVC_TILE_8x32, MVC_TILE_32x8 = 0, 1, 2, 3, 4
 MVC_ROTATE_TARGETS, MVC_KEEP_MAP = 1, 2
@@ -445,6 +456,8 @@ SYMBOLS = {
     "ovg_tsdf_integrate": (i32, [C.POINTER(TsdfIntegrateParams), vp]),
     "ovg_tsdf_extract": (i32, [C.POINTER(TsdfExtractParams), vp]),
     "ovg_tsdf_extract_workspace_bytes": (i64, [i32, i32, i32]),
+    "ovg_render_mesh": (i32, [C.POINTER(RenderMeshParams), vp]),
+    "ovg_render_mesh_workspace_bytes": (i64, [i32, i32, i32]),
 }
 
 

@@ -726,6 +726,55 @@ def render_points(points, colors, cams, H, W, radius=1, near=1e-3, background=(2
     return rgb, dep, idx
 
 
+def render_mesh_workspace_bytes(V, H, W):
+    for v in (V, H, W):
+        if not -(1 << 31) <= int(v) < (1 << 31):
+            raise L.OvgError("ovg_render_mesh_workspace_bytes: unsupported (V=%d, H=%d, W=%d)" % (V, H, W))
+    b = L.load().ovg_render_mesh_workspace_bytes(int(V), int(H), int(W))
+    if b < 0:
+        raise L.OvgError("ovg_render_mesh_workspace_bytes: unsupported (V=%d, H=%d, W=%d)" % (V, H, W))
+    return int(b)
+
+
+def render_mesh(vertices, faces, cams, H, W, normals=None, colors=None, shading=L.MESH_SHADE_HEADLIGHT, cull=L.MESH_CULL_NONE, near=1e-3,
+                background=(255, 255, 255), depth=True, index=False, coop_threshold=0, ws=None, out=None, flags=0):
+    """ovg_render_mesh on contiguous device tensors: vertices f32 [M, 3], faces int32 [F, 3], optional normals f32 [M, 3] and colors u8
+    [M, 3], cams f32 [V, 16] (as for render_points). -> (rgb u8 [V, H, W, 3], depth f32 [V, H, W] or None, index int64 [V, H, W] or
+    None), allocated here unless out = (rgb, depth or None, index or None) gives them; ws: an optional uint8 device tensor of at
+    least render_mesh_workspace_bytes(V, H, W) bytes. Nothing is read back."""
+    _chk_dev(vertices, faces, cams, normals, colors, ws)
+    if vertices.dtype != torch.float32 or cams.dtype != torch.float32 or faces.dtype != torch.int32 or \
+            not (vertices.is_contiguous() and faces.is_contiguous() and cams.is_contiguous()):
+        raise L.OvgError("render_mesh: vertices / cams must be contiguous f32 tensors, faces a contiguous int32 tensor")
+    M, F, V = vertices.numel() // 3, faces.numel() // 3, cams.numel() // 16
+    if vertices.numel() != 3 * M or faces.numel() != 3 * F or cams.numel() != 16 * V:
+        raise L.OvgError("render_mesh: vertices / faces must hold 3 values per row, cams 16 per view")
+    if normals is not None and (normals.dtype != torch.float32 or not normals.is_contiguous() or normals.numel() != 3 * M):
+        raise L.OvgError("render_mesh: normals must be a contiguous f32 tensor of 3 values per vertex")
+    if colors is not None and (colors.dtype != torch.uint8 or not colors.is_contiguous() or colors.numel() != 3 * M):
+        raise L.OvgError("render_mesh: colors must be a contiguous u8 tensor of 3 values per vertex")
+    need = render_mesh_workspace_bytes(V, H, W)
+    if ws is None or nbytes(ws) < need:
+        ws = torch.empty(need, device=cams.device, dtype=torch.uint8)
+    if out is not None:
+        rgb, dep, idx = out
+    else:
+        rgb = torch.empty(V, H, W, 3, device=cams.device, dtype=torch.uint8)
+        dep = torch.empty(V, H, W, device=cams.device, dtype=torch.float32) if depth else None
+        idx = torch.empty(V, H, W, device=cams.device, dtype=torch.int64) if index else None
+    p = L.RenderMeshParams()
+    p.vertices, p.faces = L.ptr(vertices) if M else None, L.ptr(faces) if F else None
+    p.normals, p.colors = L.ptr(normals) if M else None, L.ptr(colors) if M else None
+    p.M, p.F, p.cams = M, F, L.ptr(cams)
+    p.V, p.H, p.W, p.shading, p.cull, p.coop_threshold = V, int(H), int(W), int(shading), int(cull), int(coop_threshold)
+    p.near, p.flags = float(near), int(flags)
+    for k in range(3):
+        p.background[k] = int(background[k])
+    p.ws, p.ws_bytes, p.out_rgb, p.out_depth, p.out_index = L.ptr(ws), nbytes(ws), L.ptr(rgb), L.ptr(dep), L.ptr(idx)
+    L.call("ovg_render_mesh", p, _stream())
+    return rgb, dep, idx
+
+
 def consistency_workspace_bytes(S, H, W):
     for v in (S, H, W):
         if not -(1 << 31) <= int(v) < (1 << 31):

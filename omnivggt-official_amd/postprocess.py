@@ -1963,6 +1963,91 @@ class Mesh:
         self.extrinsic, self.scene_scale = extrinsic, scene_scale
 
 
+MESH_SHADINGS = {"color": 0, "headlight": 1, "normal": 2}
+MESH_CULLS = {None: 0, "back": 1, "front": 2}
+
+
+def render_mesh(mesh, extrinsic, intrinsic, size, shading="headlight", cull=None, smooth=True, near=1e-3, background=(255, 255, 255),
+                return_depth=True, return_index=False):
+    """Draw a Mesh from V pinhole cameras into 8-bit images on the device (ovg_render_mesh): z-buffered triangles with per-pixel
+    perspective-correct depth, colour and normal. The nearest face of a pixel wins, equal depths go to the earliest face, nothing is
+    blended. The rule is exact (tests/raster_twin.py restates it in numpy) and two calls give identical bytes.
+
+    extrinsic, intrinsic, size, near, background: as for render_point_cloud -- (V,3,4) or one (3,4) world-to-camera in the frame of
+    mesh.vertices (not the aligned frame of mesh.transform), (V,3,3) or one (3,3), (H, W); pixel centres at integer coordinates.
+    shading: "headlight" (the vertex colour times 0.25 + 0.75 |n . optical axis|: a light at the camera, both sides lit), "color"
+    (the vertex colour alone) or "normal" (the world normal as 255 (n / |n| + 1) / 2). A mesh without colours (mesh.colors None) is
+    128 grey. smooth: interpolate mesh.normals; False (or mesh.normals None) shades every face with its own normal. cull: None draws
+    both sides, "back" drops faces whose outward normal looks away from the camera, "front" the others.
+
+    NO CLIPPING: a face is not drawn in a view in which one of its vertices has camera depth <= near, a non-finite camera
+    coordinate or a projection more than 16384 pixels from the origin of the image -- neither cut at the near plane nor at a guard
+    band. A triangle that reaches behind the camera disappears from that view as a whole; subdivide such faces if that matters. A
+    face with a vertex index outside the mesh is skipped. Also not in it: anti-aliasing, textures, transparency, a top-left fill rule
+    (a pixel centre exactly on a shared edge is covered by both faces, and depth, then the lower face index decide).
+
+    -> RenderResult(rgb (V,H,W,3) u8, depth (V,H,W) f32 camera z of the surface at the pixel centre or None, index (V,H,W) int64 face
+    index or None); pixels no face covers take `background`, depth 0 and index -1.
+
+    No device -> host synchronisation: every size is known before the launches. A mesh without faces returns background images.
+    CPU meshes raise OvgError (there is no CPU fallback); a bad size, shading, cull, near or background raises ValueError."""
+    import math
+    import numpy as np
+    L = ops.L
+    if not isinstance(mesh, Mesh):
+        raise ValueError("render_mesh: expected a Mesh")
+    try:
+        H, W = (int(v) for v in size)
+        ok = (H, W) == tuple(size) and H > 0 and W > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("render_mesh: size must be (H, W), two positive integers, got %r" % (size,))
+    if not isinstance(shading, str) or shading not in MESH_SHADINGS:
+        raise ValueError("render_mesh: shading must be one of %r, got %r" % (sorted(MESH_SHADINGS), shading))
+    if not (cull is None or isinstance(cull, str)) or cull not in MESH_CULLS:
+        raise ValueError("render_mesh: cull must be None, \"back\" or \"front\", got %r" % (cull,))
+    try:
+        near32 = float(np.float32(near))
+    except (TypeError, ValueError):
+        near32 = float("nan")
+    if isinstance(near, bool) or not (near32 > 0.0 and math.isfinite(near32)):
+        raise ValueError("render_mesh: near must be positive and finite in float32, got %r" % (near,))
+    try:
+        bg = tuple(int(v) for v in background)
+        ok = len(bg) == 3 and all(0 <= v <= 255 for v in bg) and bg == tuple(background)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("render_mesh: background must be three integers in [0, 255], got %r" % (background,))
+    ext, intr = torch.as_tensor(extrinsic).detach(), torch.as_tensor(intrinsic).detach()
+    if ext.dim() == 2:
+        ext = ext[None]
+    if ext.dim() != 3 or tuple(ext.shape[1:]) != (3, 4) or ext.shape[0] == 0:
+        raise ValueError("render_mesh: extrinsic must be (V, 3, 4), got %r" % (tuple(ext.shape),))
+    V = int(ext.shape[0])
+    if tuple(intr.shape) not in ((3, 3), (V, 3, 3)):
+        raise ValueError("render_mesh: intrinsic must be (3, 3) or (V, 3, 3) = (%d, 3, 3), got %r" % (V, tuple(intr.shape)))
+    if V * H * W >= 1 << 31:
+        raise ValueError("render_mesh: V * H * W = %d pixels is 2^31 or more; render fewer views per call" % (V * H * W))
+    vert, faces = mesh.vertices, mesh.faces
+    for t in (vert, faces, mesh.normals, mesh.colors):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise L.OvgError("render_mesh needs HIP device tensors: there is no CPU fallback")
+    if vert is None or faces is None:
+        raise ValueError("render_mesh: the mesh has no vertices or no faces tensor")
+    M, F = int(vert.shape[0]), int(faces.shape[0])
+    if M >= 1 << 31 or F >= 1 << 31:
+        raise ValueError("render_mesh: the mesh has 2^31 vertices or faces or more")
+    cams = _pack_cams(ext, intr, V, vert.device)
+    normals = mesh.normals.reshape(M, 3).float().contiguous() if smooth and mesh.normals is not None else None
+    colors = mesh.colors.reshape(M, 3).contiguous() if mesh.colors is not None else None
+    rgb, depth, index = ops.render_mesh(vert.reshape(M, 3).float().contiguous(), faces.reshape(F, 3).to(torch.int32).contiguous(), cams, H, W,
+                                        normals=normals, colors=colors, shading=MESH_SHADINGS[shading], cull=MESH_CULLS[cull], near=near32,
+                                        background=bg, depth=return_depth, index=return_index)
+    return RenderResult(rgb, depth, index)
+
+
 def _tsdf_positive(what, name, value):
     import math
     import numpy as np
