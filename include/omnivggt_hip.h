@@ -20,7 +20,8 @@
  *     statistics, softmax statistics, biases, LayerScale gammas, q/k-norm
  *     affine parameters and the RoPE table are always f32.
  *   - thread-safe for distinct streams; the library holds NO mutable state: every tuning choice is either
- *     derived from the call's shapes or passed in the parameter struct (`tile`, `variant`).
+ *     derived from the call's shapes or passed in the parameter struct (`tile`, `variant`). The one thing it remembers is which
+ *     kernels it has already opted in to > 64 KB of dynamic LDS on which device: an idempotent memo, read and written under a lock.
  *   - workspace is caller-provided; ovg_block_workspace_bytes() answers how much a block call needs.
  */
 #ifndef OMNIVGGT_HIP_H

@@ -5,6 +5,7 @@
 // align_corners bilinear resize and the 1x1 + activation output stage. All three dtypes: the 16-bit modes and (r03) the f32 parity mode
 // on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32 through TT<float>::mma, 32-channel k chunks instead of 64).
 #include "ovg_common.h"
+#include <mutex>
 
 namespace {
 
@@ -338,6 +339,18 @@ unsigned grid_1d(int64_t work, int per_block, int cap = 1 << 16) {
   return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
+// > 64 KB of dynamic LDS is a per-device opt-in of the kernel: done once per (kernel, device) and remembered in the caller's bit mask. The
+// mask is the only state; it is read and written under this lock (as allow_big_lds of ovg_gemm.hip), so two host threads on distinct
+// streams never touch it unguarded. Devices from 32 on have no bit and opt in on every call.
+int opt_in_big_lds(unsigned& mask, const void* fn, int bytes, int dev) {
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  if (dev < 32 && ((mask >> dev) & 1u)) return OVG_OK;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return OVG_E_LAUNCH;
+  if (dev < 32) mask |= 1u << dev;
+  return OVG_OK;
+}
+
 }  // namespace
 
 extern "C" int ovg_head_layernorm(const ovg_head_layernorm_params* p, void* stream) {
@@ -388,19 +401,14 @@ extern "C" int ovg_conv(const ovg_conv_params* p, void* stream) {
     const bool wide = gemm_cols % 256 == 0;
     const int nt2 = p->w_rows / (wide ? 256 : 128);
     const dim3 grid2((unsigned)(((M + 255) / 256) * nt2));
-    // > 64 KB of dynamic LDS is a per-device opt-in of the kernel: done once per (kernel, device), remembered in a bit mask (idempotent; a
-    // race between two threads sets it twice)
-    static unsigned opted[4] = {0u, 0u, 0u, 0u};
+    static unsigned opted[4] = {0u, 0u, 0u, 0u};               // one mask per kernel, guarded by opt_in_big_lds
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return OVG_E_LAUNCH;
     const int which = (p->dtype == OVG_BF16 ? 0 : 1) + (wide ? 0 : 2);
     const int lds_b = wide ? c256::Geo<4>::LDS_BYTES : c256::Geo<2>::LDS_BYTES;
-    if (dev >= 32 || !((opted[which] >> dev) & 1u)) {
-      const void* fn = which == 0 ? reinterpret_cast<const void*>(conv256_kernel<bf16_t, 4>) : (which == 1 ? reinterpret_cast<const void*>(conv256_kernel<f16_t, 4>)
-                       : (which == 2 ? reinterpret_cast<const void*>(conv256_kernel<bf16_t, 2>) : reinterpret_cast<const void*>(conv256_kernel<f16_t, 2>)));
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b) != hipSuccess) return OVG_E_LAUNCH;
-      if (dev < 32) opted[which] |= 1u << dev;
-    }
+    const void* fn = which == 0 ? reinterpret_cast<const void*>(conv256_kernel<bf16_t, 4>) : (which == 1 ? reinterpret_cast<const void*>(conv256_kernel<f16_t, 4>)
+                     : (which == 2 ? reinterpret_cast<const void*>(conv256_kernel<bf16_t, 2>) : reinterpret_cast<const void*>(conv256_kernel<f16_t, 2>)));
+    if (opt_in_big_lds(opted[which], fn, lds_b, dev) != OVG_OK) return OVG_E_LAUNCH;
     switch (which) {
       case 0: OVG_LAUNCH((conv256_kernel<bf16_t, 4>), grid2, dim3(512), lds_b, st, *p, OH, OW, M, nt2); break;
       case 1: OVG_LAUNCH((conv256_kernel<f16_t, 4>), grid2, dim3(512), lds_b, st, *p, OH, OW, M, nt2); break;
@@ -466,13 +474,10 @@ extern "C" int ovg_dpt_tail(const ovg_dpt_tail_params* p, void* stream) {
   const float sy = (float)(p->H - 1) / (float)(p->OH - 1), sx = (float)(p->W - 1) / (float)(p->OW - 1);   // as ovg_upsample
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return OVG_E_LAUNCH;
-  static unsigned opted[2] = {0u, 0u};                       // > 64 KB of dynamic LDS: per-device opt-in, once (as in ovg_conv)
+  static unsigned opted[2] = {0u, 0u};                       // > 64 KB of dynamic LDS: per-device opt-in, once, under the lock (as in ovg_conv)
   const int which = p->dtype == OVG_BF16 ? 0 : 1;
-  if (dev >= 32 || !((opted[which] >> dev) & 1u)) {
-    const void* fn = which == 0 ? reinterpret_cast<const void*>(dtail::dpt_tail_kernel<bf16_t>) : reinterpret_cast<const void*>(dtail::dpt_tail_kernel<f16_t>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, dtail::LDS_B) != hipSuccess) return OVG_E_LAUNCH;
-    if (dev < 32) opted[which] |= 1u << dev;
-  }
+  const void* fn = which == 0 ? reinterpret_cast<const void*>(dtail::dpt_tail_kernel<bf16_t>) : reinterpret_cast<const void*>(dtail::dpt_tail_kernel<f16_t>);
+  if (opt_in_big_lds(opted[which], fn, dtail::LDS_B, dev) != OVG_OK) return OVG_E_LAUNCH;
   const int ntiles = (int)nt64;
   const dim3 grid((unsigned)(ntiles < cus ? ntiles : cus)), block(dtail::NT);   // persistent: one workgroup per CU (156 KB of LDS each)
   hipStream_t st = static_cast<hipStream_t>(stream);
