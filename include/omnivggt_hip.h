@@ -71,7 +71,10 @@ extern "C" {
  *       the same way
  *     + volumetric fusion: depth maps into a TSDF volume and a surface-nets mesh of its zero level (ovg_tsdf_integrate,
  *       ovg_tsdf_extract, ovg_tsdf_extract_workspace_bytes): added the same way
- *     + mesh rasterisation: z-buffered, shaded triangles (ovg_render_mesh, ovg_render_mesh_workspace_bytes): added the same way */
+ *     + mesh rasterisation: z-buffered, shaded triangles (ovg_render_mesh, ovg_render_mesh_workspace_bytes): added the same way
+ *     + depth evaluation: masked per-group medians, aligned metric sums and the alignment solve (ovg_deptheval_median,
+ *       ovg_deptheval_sums, ovg_deptheval_solve, ovg_deptheval_median_workspace_bytes, ovg_deptheval_sums_workspace_bytes): added the
+ *       same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -1124,6 +1127,110 @@ typedef struct {
   float* out;
 } ovg_align_apply_params;
 int ovg_align_apply(const ovg_align_apply_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Depth evaluation (added under ABI 13): how good a predicted depth map is against ground truth -- AbsRel, delta < 1.25 and their
+ * kin after a median, scale or scale-and-shift alignment -- as three entries that never read anything back: the masked medians of
+ * every group, the float64 sums of a group (the moments a fit needs, or the metric terms under given coefficients), and the solve
+ * from either to the coefficients. tests/deptheval_twin.py restates all three in numpy; every output is compared byte for byte but
+ * the one sum that holds a logarithm.
+ *
+ * Shared by the three entries. pred, gt: f32 [groups][n], G = groups rows of n contiguous pixels, row g at pred + g stride (stride
+ * in ELEMENTS, the same for pred, gt and valid; stride >= n). valid: u8 [groups][n] or NULL. Pixel i of group g is USED when
+ *   valid is NULL or valid[g][i] != 0,   pred and gt are finite there,   pred > 0,   min_depth < gt <= max_depth
+ * (f32 comparisons; min_depth >= 0 and not NaN, max_depth not NaN, +inf allowed). A used pred or gt is therefore positive and
+ * finite, subnormals included. Limits: 1 <= n, 1 <= groups <= OVG_DEPTHEVAL_MAX_GROUPS, groups n < 2^31, groups stride < 2^40.
+ *
+ * ovg_deptheval_median: out_count int64 [G]: the number N of used pixels of the group; out_median f32 [G][2][2]: for map m (0 pred,
+ *   1 gt) the order statistics of rank (N - 1) / 2 ([m][0], the lower middle) and N / 2 ([m][1], the upper middle; integer division,
+ *   ranks from 0, ascending) of that map's values over the used pixels; the median is the mean of the two. N = 0: count 0 and four
+ *   +0.0. The bit pattern of a positive finite float orders like an unsigned integer, so the statistic is found by a radix select
+ *   over the four bytes of the key, the most significant first: a pass counts, per group and selection, the used keys that agree
+ *   with the bytes found so far into 256 bins (privatised in LDS per workgroup, merged into ws with 32-bit integer atomic adds); a
+ *   one-workgroup-per-group launch then walks the bins to the one that holds the rank, appends its byte and zeroes the bins for the
+ *   next pass. Integer counts only: the result is a function of the multiset of used values and nothing else -- no schedule, grid
+ *   size or arrival order of an atomic can change a byte of it. No sort, no compaction.
+ *   ws: >= ovg_deptheval_median_workspace_bytes(groups, n) bytes, 16-byte aligned: per group four histograms of 256 u32 and eight u32
+ *   of selection state, rounded up to 256; the entry zeroes it itself (a launch of its own). The query returns -1 outside the limits.
+ *   OVG_E_ARG: NULL params / pred / gt / ws / out_count / out_median, sizes outside the limits, stride < n, a NaN or negative
+ *   min_depth, a NaN max_depth, a pointer that is not 4-byte (out_count: 8-byte) aligned, a misaligned or undersized workspace.
+ *
+ * ovg_deptheval_sums: all arithmetic in float64, every operation rounded on its own (no fused multiply-add), p = (double)pred,
+ *   g = (double)gt of a used pixel. The five TERMS of a pixel by mode:
+ *   OVG_DEPTHEVAL_MOMENTS   [0] p   [1] g   [2] p p   [3] p g   [4] g g          (coeff, clip_min, clip_max are not read)
+ *   OVG_DEPTHEVAL_METRICS   coeff f64 [G][2] = (s, t) on the device; q = s p + t; q = q > clip_min ? q : clip_min (a NaN becomes
+ *                           clip_min); q = q < clip_max ? q : clip_max; e = q - g;
+ *                           [0] |e| / g   [1] (e e) / g   [2] e e   [3] |e|   [4] d d with d = log q - log g
+ *                           (clip_min > 0 and finite; clip_max >= clip_min, +inf allowed)
+ *   out_counts int64 [G][4]: [0] the used pixels N; METRICS: [1..3] those with max(q / g, g / q) STRICTLY below 1.25, 1.5625 and
+ *   1.953125 (1.25, 1.25^2, 1.25^3: exact in binary); MOMENTS: 0. out_sums f64 [G][5]: the sums of the terms over the used pixels
+ *   of the group, in the order of ovg_align_moments:
+ *   1. tile k of a group holds its pixels [OVG_DEPTHEVAL_TILE k, OVG_DEPTHEVAL_TILE (k + 1)) -- a tile never straddles two groups;
+ *      thread t of its OVG_DEPTHEVAL_THREADS threads adds the terms of the pixels t, t + THREADS, ... of the tile in that order onto
+ *      +0.0, skipping pixels that are not used or >= n;
+ *   2. inside a wave of 64 lanes v[l] = v[l] + v[l + s] for s = 32, 16, 8, 4, 2, 1;
+ *   3. the four wave sums combine as (w0 + w1) + (w2 + w3): the tile's partial, written to ws;
+ *   4. a second launch, one workgroup per group, folds the group's partials the same way: thread t adds the partials of the tiles
+ *      t, t + THREADS, ... in that order onto +0.0, then steps 2 and 3.
+ *   No float atomics, no workgroup waits for another (stream order between the two launches is the only synchronisation): two calls
+ *   give identical bytes. log is the device library's float64 logarithm: term [4] is the one output held to a bound, not to bytes.
+ *   ws: >= ovg_deptheval_sums_workspace_bytes(groups, n) bytes, 16-byte aligned: OVG_DEPTHEVAL_PARTIAL_BYTES per tile, rounded up
+ *   to 256; the query returns -1 outside the limits.
+ *   OVG_E_ARG: as for the median (out_counts, out_sums, coeff: 8-byte aligned), an unknown mode, and in METRICS a NULL coeff, a NaN
+ *   clip, clip_min that is not positive and finite, clip_max < clip_min.
+ *
+ * ovg_deptheval_solve: one thread per group, float64: (s, t) with gt ~ s pred + t, written to coeff f64 [G][2], status int32 [G].
+ *   N = count[g count_stride] (count_stride in elements: 1 for out_count of the median, 4 for out_counts of the sums), the sums
+ *   (Sp, Sg, Spp, Spg, Sgg) = sums[g][0..4] of OVG_DEPTHEVAL_MOMENTS, the medians out_median[g] of ovg_deptheval_median.
+ *   OVG_DEPTHEVAL_NONE         (1, 0)
+ *   OVG_DEPTHEVAL_MEDIAN       s = mg / mp with m = 0.5 ((double)lower + (double)upper) of each map; t = 0
+ *   OVG_DEPTHEVAL_SCALE        s = Spg / Spp; t = 0                              (least squares through the origin)
+ *   OVG_DEPTHEVAL_SCALE_SHIFT  det = N Spp - Sp Sp; s = (N Spg - Sp Sg) / det; t = (Sg - s Sp) / N      (least squares)
+ *   DEGENERATE, in this order: N < 1, or N < 2 for SCALE_SHIFT (OVG_DEPTHEVAL_FEW); an input the mode reads -- the five sums for
+ *   SCALE and SCALE_SHIFT, the four medians for MEDIAN -- is not finite (OVG_DEPTHEVAL_NOT_FINITE; both bits may be set together);
+ *   then, only while no bit is set, SCALE_SHIFT with det not above OVG_DEPTHEVAL_SPREAD_EPS (2^-40) (N Spp)
+ *   (OVG_DEPTHEVAL_NO_SPREAD: all used pred equal, or so close that the subtraction keeps fewer than 12 bits); then s or t not
+ *   finite, or s <= 0 (OVG_DEPTHEVAL_BAD_FIT). A degenerate group gets (1, 0) and its bits; a NaN is never written.
+ *   OVG_E_ARG: NULL params / count / coeff / status, count_stride < 1, groups outside the limits, an unknown mode, NULL sums for SCALE
+ *   and SCALE_SHIFT, NULL median for MEDIAN, a pointer that is not 8-byte (median, status: 4-byte) aligned.
+ * ------------------------------------------------------------------ */
+enum { OVG_DEPTHEVAL_THREADS = 256, OVG_DEPTHEVAL_TILE = 1024, OVG_DEPTHEVAL_SUMS = 5, OVG_DEPTHEVAL_COUNTS = 4,
+       OVG_DEPTHEVAL_PARTIAL_BYTES = 80, OVG_DEPTHEVAL_MAX_GROUPS = 4096,
+       OVG_DEPTHEVAL_CHUNK = 16384,                /* pixels per workgroup of a histogram pass (speed only) */
+       OVG_DEPTHEVAL_MEDIAN_GROUP_BYTES = 4128 };  /* 4 x 256 u32 bins + 8 u32 of state */
+enum { OVG_DEPTHEVAL_MOMENTS = 0, OVG_DEPTHEVAL_METRICS = 1 };                                                    /* ovg_deptheval_sums_params.mode */
+enum { OVG_DEPTHEVAL_NONE = 0, OVG_DEPTHEVAL_MEDIAN = 1, OVG_DEPTHEVAL_SCALE = 2, OVG_DEPTHEVAL_SCALE_SHIFT = 3 }; /* ovg_deptheval_solve_params.mode */
+enum { OVG_DEPTHEVAL_FEW = 1, OVG_DEPTHEVAL_NOT_FINITE = 2, OVG_DEPTHEVAL_NO_SPREAD = 4, OVG_DEPTHEVAL_BAD_FIT = 8 }; /* status */
+#define OVG_DEPTHEVAL_SPREAD_EPS 9.094947017729282e-13                               /* 2^-40 */
+typedef struct {
+  const float* pred; const float* gt; const uint8_t* valid;
+  int64_t groups; int64_t n; int64_t stride;
+  float min_depth; float max_depth;
+  void* ws; int64_t ws_bytes;
+  int64_t* out_count; float* out_median;
+} ovg_deptheval_median_params;
+int64_t ovg_deptheval_median_workspace_bytes(int64_t groups, int64_t n);
+int ovg_deptheval_median(const ovg_deptheval_median_params*, void* stream);
+
+typedef struct {
+  const float* pred; const float* gt; const uint8_t* valid;
+  int64_t groups; int64_t n; int64_t stride;
+  float min_depth; float max_depth;
+  int32_t mode; int32_t reserved;
+  const double* coeff; double clip_min; double clip_max;
+  void* ws; int64_t ws_bytes;
+  int64_t* out_counts; double* out_sums;
+} ovg_deptheval_sums_params;
+int64_t ovg_deptheval_sums_workspace_bytes(int64_t groups, int64_t n);
+int ovg_deptheval_sums(const ovg_deptheval_sums_params*, void* stream);
+
+typedef struct {
+  const int64_t* count; int64_t count_stride;
+  const double* sums; const float* median;
+  int64_t groups; int32_t mode; int32_t reserved;
+  double* coeff; int32_t* status;
+} ovg_deptheval_solve_params;
+int ovg_deptheval_solve(const ovg_deptheval_solve_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Plane segmentation by RANSAC (added under ABI 13): five entries that never read anything back -- seeded hypotheses, their inlier

@@ -319,7 +319,31 @@ class AlignApplyParams(C.Structure):
     _fields_ = [("points", vp), ("transform", vp), ("n", i64), ("out", vp)]
 
 
-PLANE_HYP_TILE, PLANE_POINT_TILE = 512, 512                  # hypotheses per workgroup, points per LDS tile of ovg_plane_score (tests place shapes around them)
+DEPTHEVAL_THREADS, DEPTHEVAL_TILE, DEPTHEVAL_SUMS, DEPTHEVAL_COUNTS, DEPTHEVAL_PARTIAL_BYTES = 256, 1024, 5, 4, 80   # the order of ovg_deptheval_sums
+DEPTHEVAL_MAX_GROUPS, DEPTHEVAL_CHUNK, DEPTHEVAL_MEDIAN_GROUP_BYTES = 4096, 16384, 4128
+DEPTHEVAL_MOMENTS, DEPTHEVAL_METRICS = 0, 1                  # ovg_deptheval_sums_params.mode
+DEPTHEVAL_NONE, DEPTHEVAL_MEDIAN, DEPTHEVAL_SCALE, DEPTHEVAL_SCALE_SHIFT = 0, 1, 2, 3   # ovg_deptheval_solve_params.mode
+DEPTHEVAL_FEW, DEPTHEVAL_NOT_FINITE, DEPTHEVAL_NO_SPREAD, DEPTHEVAL_BAD_FIT = 1, 2, 4, 8   # status of ovg_deptheval_solve
+DEPTHEVAL_SPREAD_EPS = 2.0 ** -40
+
+
+class DepthEvalMedianParams(C.Structure):
+    _fields_ = [("pred", vp), ("gt", vp), ("valid", vp), ("groups", i64), ("n", i64), ("stride", i64), ("min_depth", f32), ("max_depth", f32),
+                ("ws", vp), ("ws_bytes", i64), ("out_count", vp), ("out_median", vp)]
+
+
+class DepthEvalSumsParams(C.Structure):
+    _fields_ = [("pred", vp), ("gt", vp), ("valid", vp), ("groups", i64), ("n", i64), ("stride", i64), ("min_depth", f32), ("max_depth", f32),
+                ("mode", i32), ("reserved", i32), ("coeff", vp), ("clip_min", C.c_double), ("clip_max", C.c_double), ("ws", vp), ("ws_bytes", i64),
+                ("out_counts", vp), ("out_sums", vp)]
+
+
+class DepthEvalSolveParams(C.Structure):
+    _fields_ = [("count", vp), ("count_stride", i64), ("sums", vp), ("median", vp), ("groups", i64), ("mode", i32), ("reserved", i32),
+                ("coeff", vp), ("status", vp)]
+
+
+PLANE_HYP_TILE, PLANE_POINT_TILE = 512, 512                 # hypotheses per workgroup, points per LDS tile of ovg_plane_score (tests place shapes around them)
 PLANE_NONE, PLANE_FEW, PLANE_NO_SPREAD, PLANE_NOT_FINITE = 1, 2, 4, 8   # status bits of ovg_plane_select (NONE) and ovg_plane_fit
 PLANE_COLLINEAR_EPS, PLANE_SPREAD_EPS = 2.0 ** -20, 2.0 ** -40
 
@@ -458,6 +482,11 @@ SYMBOLS = {
     "ovg_tsdf_extract_workspace_bytes": (i64, [i32, i32, i32]),
     "ovg_render_mesh": (i32, [C.POINTER(RenderMeshParams), vp]),
     "ovg_render_mesh_workspace_bytes": (i64, [i32, i32, i32]),
+    "ovg_deptheval_median": (i32, [C.POINTER(DepthEvalMedianParams), vp]),
+    "ovg_deptheval_median_workspace_bytes": (i64, [i64, i64]),
+    "ovg_deptheval_sums": (i32, [C.POINTER(DepthEvalSumsParams), vp]),
+    "ovg_deptheval_sums_workspace_bytes": (i64, [i64, i64]),
+    "ovg_deptheval_solve": (i32, [C.POINTER(DepthEvalSolveParams), vp]),
 }
 
 

@@ -1198,6 +1198,135 @@ def align_apply(points, transform, out=None):
     return out
 
 
+def _deptheval_ws_bytes(name, groups, n):
+    if not all(-(1 << 63) <= int(v) < (1 << 63) for v in (groups, n)):
+        raise L.OvgError("%s: unsupported (groups=%d, n=%d)" % (name, groups, n))
+    b = getattr(L.load(), name)(int(groups), int(n))
+    if b < 0:
+        raise L.OvgError("%s: unsupported (groups=%d, n=%d)" % (name, groups, n))
+    return int(b)
+
+
+def deptheval_median_workspace_bytes(groups, n):
+    return _deptheval_ws_bytes("ovg_deptheval_median_workspace_bytes", groups, n)
+
+
+def deptheval_sums_workspace_bytes(groups, n):
+    return _deptheval_ws_bytes("ovg_deptheval_sums_workspace_bytes", groups, n)
+
+
+def _deptheval_maps(what, pred, gt, valid, min_depth, max_depth):
+    """-> (G, n, stride) of the f32 [G, n] maps (rows contiguous, one row stride shared by pred, gt and valid)."""
+    for t, name in ((pred, "pred"), (gt, "gt")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1:
+            raise L.OvgError("%s: %s must be an f32 tensor [G, n] with contiguous rows, G >= 1, n >= 1" % (what, name))
+    if valid is not None and (not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or valid.dim() != 2 or valid.stride(1) != 1):
+        raise L.OvgError("%s: valid must be a uint8 tensor [G, n] with contiguous rows" % what)
+    G, n = int(pred.shape[0]), int(pred.shape[1])
+    stride = int(pred.stride(0)) if G > 1 else n
+    for t, name in ((gt, "gt"), (valid, "valid")):
+        if t is not None and (tuple(t.shape) != (G, n) or (G > 1 and int(t.stride(0)) != stride)):
+            raise L.OvgError("%s: %s must be shaped %r with the row stride of pred (%d)" % (what, name, (G, n), stride))
+    if G > L.DEPTHEVAL_MAX_GROUPS or G * n >= (1 << 31) or stride < n:
+        raise L.OvgError("%s: the maps must be at most %d groups, fewer than 2^31 pixels, row stride >= n" % (what, L.DEPTHEVAL_MAX_GROUPS))
+    for v, name in ((min_depth, "min_depth"), (max_depth, "max_depth")):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            raise L.OvgError("%s: %s must be a number, not NaN" % (what, name))
+    if min_depth < 0:
+        raise L.OvgError("%s: min_depth must be >= 0" % what)
+    return G, n, stride
+
+
+def _deptheval_check_ws(what, ws):
+    if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous()):
+        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+
+
+def _deptheval_ws(ws, need, device):
+    return torch.empty(need, device=device, dtype=torch.uint8) if ws is None or nbytes(ws) < need else ws
+
+
+def deptheval_median(pred, gt, valid=None, min_depth=0.0, max_depth=float("inf"), ws=None, count=None, median=None):
+    """ovg_deptheval_median on device tensors: pred, gt f32 [G, n] (rows contiguous, one shared row stride), valid u8 [G, n] or None.
+    -> (count int64 [G], median f32 [G, 2, 2]) (allocated when None): per group the number of used pixels and, for pred ([g, 0]) and
+    gt ([g, 1]), the lower and upper middle order statistics over them -- a function of the multiset of used values alone. ws: an
+    optional uint8 device tensor of at least deptheval_median_workspace_bytes(G, n) bytes (the call zeroes it). Nothing is read back."""
+    what = "deptheval_median"
+    G, n, stride = _deptheval_maps(what, pred, gt, valid, min_depth, max_depth)
+    _align_tensor(what, count, "count", torch.int64, (G,), True)
+    _align_tensor(what, median, "median", torch.float32, (G, 2, 2), True)
+    _deptheval_check_ws(what, ws)
+    _chk_dev(pred, gt, valid, ws, count, median)
+    ws = _deptheval_ws(ws, deptheval_median_workspace_bytes(G, n), pred.device)
+    count = torch.empty(G, device=pred.device, dtype=torch.int64) if count is None else count
+    median = torch.empty(G, 2, 2, device=pred.device, dtype=torch.float32) if median is None else median
+    p = L.DepthEvalMedianParams()
+    p.pred, p.gt, p.valid, p.groups, p.n, p.stride = L.ptr(pred), L.ptr(gt), L.ptr(valid), G, n, stride
+    p.min_depth, p.max_depth = float(min_depth), float(max_depth)
+    p.ws, p.ws_bytes, p.out_count, p.out_median = L.ptr(ws), nbytes(ws), L.ptr(count), L.ptr(median)
+    L.call("ovg_deptheval_median", p, _stream())
+    return count, median
+
+
+def deptheval_sums(pred, gt, valid=None, min_depth=0.0, max_depth=float("inf"), coeff=None, clip_min=1e-3, clip_max=float("inf"), ws=None,
+                   counts=None, sums=None):
+    """ovg_deptheval_sums on device tensors shaped as for deptheval_median. coeff None: the MOMENTS of a fit (sums of p, g, p p, p g,
+    g g); coeff f64 [G, 2] = (s, t): the METRICS terms of q = clip(s p + t) against g (|e| / g, e e / g, e e, |e|, (log q - log g)^2)
+    and the delta counts. -> (counts int64 [G, 4], sums f64 [G, 5]) (allocated when None): counts[:, 0] the used pixels, [:, 1:] those
+    with max(q / g, g / q) < 1.25, 1.25^2, 1.25^3 (0 for the moments); the sums in the fixed order of include/omnivggt_hip.h, so two
+    calls give identical bytes. ws: optional, at least deptheval_sums_workspace_bytes(G, n) bytes. Nothing is read back."""
+    what = "deptheval_sums"
+    G, n, stride = _deptheval_maps(what, pred, gt, valid, min_depth, max_depth)
+    _align_tensor(what, coeff, "coeff", torch.float64, (G, 2), True)
+    _align_tensor(what, counts, "counts", torch.int64, (G, L.DEPTHEVAL_COUNTS), True)
+    _align_tensor(what, sums, "sums", torch.float64, (G, L.DEPTHEVAL_SUMS), True)
+    if coeff is not None:
+        for v, name in ((clip_min, "clip_min"), (clip_max, "clip_max")):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+                raise L.OvgError("%s: %s must be a number, not NaN" % (what, name))
+        if not 0 < clip_min < float("inf") or clip_max < clip_min:
+            raise L.OvgError("%s: clip_min must be positive and finite, clip_max >= clip_min" % what)
+    _deptheval_check_ws(what, ws)
+    _chk_dev(pred, gt, valid, coeff, ws, counts, sums)
+    ws = _deptheval_ws(ws, deptheval_sums_workspace_bytes(G, n), pred.device)
+    counts = torch.empty(G, L.DEPTHEVAL_COUNTS, device=pred.device, dtype=torch.int64) if counts is None else counts
+    sums = torch.empty(G, L.DEPTHEVAL_SUMS, device=pred.device, dtype=torch.float64) if sums is None else sums
+    p = L.DepthEvalSumsParams()
+    p.pred, p.gt, p.valid, p.groups, p.n, p.stride = L.ptr(pred), L.ptr(gt), L.ptr(valid), G, n, stride
+    p.min_depth, p.max_depth = float(min_depth), float(max_depth)
+    p.mode, p.coeff = (L.DEPTHEVAL_MOMENTS, None) if coeff is None else (L.DEPTHEVAL_METRICS, L.ptr(coeff))
+    p.clip_min, p.clip_max = (0.0, 0.0) if coeff is None else (float(clip_min), float(clip_max))
+    p.ws, p.ws_bytes, p.out_counts, p.out_sums = L.ptr(ws), nbytes(ws), L.ptr(counts), L.ptr(sums)
+    L.call("ovg_deptheval_sums", p, _stream())
+    return counts, sums
+
+
+def deptheval_solve(mode, count, sums=None, median=None, coeff=None, status=None):
+    """ovg_deptheval_solve on device tensors: mode L.DEPTHEVAL_NONE / MEDIAN / SCALE / SCALE_SHIFT; count int64 [G] (deptheval_median's)
+    or [G, 4] (deptheval_sums': column 0 is read); sums f64 [G, 5] (the moments: SCALE, SCALE_SHIFT), median f32 [G, 2, 2] (MEDIAN).
+    -> (coeff f64 [G, 2] = (s, t) with gt ~ s pred + t, status int32 [G]) (allocated when None). A degenerate group gets (1, 0) and
+    L.DEPTHEVAL_FEW / NOT_FINITE / NO_SPREAD / BAD_FIT in its status. Nothing is read back."""
+    what = "deptheval_solve"
+    if isinstance(mode, bool) or mode not in (L.DEPTHEVAL_NONE, L.DEPTHEVAL_MEDIAN, L.DEPTHEVAL_SCALE, L.DEPTHEVAL_SCALE_SHIFT):
+        raise L.OvgError("%s: mode must be one of L.DEPTHEVAL_NONE / MEDIAN / SCALE / SCALE_SHIFT, got %r" % (what, mode))
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int64 or not count.is_contiguous() or count.dim() not in (1, 2) or \
+            count.shape[0] < 1 or count.shape[0] > L.DEPTHEVAL_MAX_GROUPS or (count.dim() == 2 and count.shape[1] != L.DEPTHEVAL_COUNTS):
+        raise L.OvgError("%s: count must be a contiguous int64 tensor [G] or [G, %d], 1 <= G <= %d" % (what, L.DEPTHEVAL_COUNTS, L.DEPTHEVAL_MAX_GROUPS))
+    G = int(count.shape[0])
+    _align_tensor(what, sums, "sums", torch.float64, (G, L.DEPTHEVAL_SUMS), mode not in (L.DEPTHEVAL_SCALE, L.DEPTHEVAL_SCALE_SHIFT))
+    _align_tensor(what, median, "median", torch.float32, (G, 2, 2), mode != L.DEPTHEVAL_MEDIAN)
+    _align_tensor(what, coeff, "coeff", torch.float64, (G, 2), True)
+    _align_tensor(what, status, "status", torch.int32, (G,), True)
+    _chk_dev(count, sums, median, coeff, status)
+    coeff = torch.empty(G, 2, device=count.device, dtype=torch.float64) if coeff is None else coeff
+    status = torch.empty(G, device=count.device, dtype=torch.int32) if status is None else status
+    p = L.DepthEvalSolveParams()
+    p.count, p.count_stride, p.sums, p.median = L.ptr(count), 1 if count.dim() == 1 else L.DEPTHEVAL_COUNTS, L.ptr(sums), L.ptr(median)
+    p.groups, p.mode, p.coeff, p.status = G, int(mode), L.ptr(coeff), L.ptr(status)
+    L.call("ovg_deptheval_solve", p, _stream())
+    return coeff, status
+
+
 def _plane_points(what, points):
     if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or \
             points.shape[1] != 3 or not 1 <= points.shape[0] < 1 << 31:

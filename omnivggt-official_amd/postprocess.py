@@ -1241,6 +1241,236 @@ def trajectory_ate(pred_extrinsic, gt_extrinsic, with_scale=True):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# Depth and pose evaluation: aligned depth metrics (ovg_deptheval_*), relative pose accuracy and AUC
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+DEPTH_ALIGNMENTS = {"none": ops.L.DEPTHEVAL_NONE, "median": ops.L.DEPTHEVAL_MEDIAN, "scale": ops.L.DEPTHEVAL_SCALE,
+                    "scale_shift": ops.L.DEPTHEVAL_SCALE_SHIFT}
+DEPTH_FEW, DEPTH_NOT_FINITE, DEPTH_NO_SPREAD, DEPTH_BAD_FIT = (ops.L.DEPTHEVAL_FEW, ops.L.DEPTHEVAL_NOT_FINITE, ops.L.DEPTHEVAL_NO_SPREAD,
+                                                               ops.L.DEPTHEVAL_BAD_FIT)
+DEPTH_FIGURES = ("abs_rel", "sq_rel", "rmse", "mae", "rmse_log", "delta1", "delta2", "delta3")
+
+
+class DepthMetrics:
+    """Result of depth_metrics. Per group (one per view with scope="view", one in all with scope="sequence") float64 device tensors
+    [G]: abs_rel (mean |q - g| / g), sq_rel (mean (q - g)^2 / g), rmse, mae, rmse_log (root mean square of log q - log g), delta1 /
+    delta2 / delta3 (share of pixels with max(q / g, g / q) < 1.25, 1.25^2, 1.25^3), q the aligned and clipped prediction; n int64 [G]
+    (used pixels), scale / shift float64 [G] (the alignment q = scale pred + shift), status int32 [G] (DEPTH_* bits, 0 for a regular
+    fit; a degenerate group is scored unaligned). A group with n = 0 reports nan. Python floats: `mean` (dict by figure: the mean over
+    the groups with n > 0, the per-image protocol), `pooled` (dict: all used pixels as one set), `n_total` (int)."""
+    __slots__ = DEPTH_FIGURES + ("n", "scale", "shift", "status", "mean", "pooled", "n_total", "align", "scope")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def __repr__(self):
+        return "DepthMetrics(align=%r, scope=%r, n_total=%r, mean=%r, pooled=%r)" % (self.align, self.scope, self.n_total, self.mean, self.pooled)
+
+
+def _depth_number(what, name, v, lo=None, lo_open=False):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+        raise ValueError("%s: %s must be a number, not NaN, got %r" % (what, name, v))
+    if lo is not None and (v <= lo if lo_open else v < lo):
+        raise ValueError("%s: %s must be %s %r, got %r" % (what, name, ">" if lo_open else ">=", lo, v))
+    return float(v)
+
+
+def _depth_args(what, pred, gt, valid, align, scope, min_depth, max_depth):
+    """-> (pred [G, n], gt [G, n], valid u8 [G, n] or None, solve mode): the checked arguments as the entries take them."""
+    if align not in DEPTH_ALIGNMENTS:
+        raise ValueError("%s: align must be one of %s, got %r" % (what, " | ".join(DEPTH_ALIGNMENTS), align))
+    if scope not in ("view", "sequence"):
+        raise ValueError("%s: scope must be view | sequence, got %r" % (what, scope))
+    maps = []
+    for t, name in ((pred, "pred"), (gt, "gt")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[-1] != 1):
+            raise ValueError("%s: %s must be a float32 tensor (S, H, W) or (S, H, W, 1)" % (what, name))
+        maps.append(t.reshape(t.shape[:3]))
+    S, H, W = maps[0].shape
+    if maps[1].shape != maps[0].shape or S < 1 or H * W < 1:
+        raise ValueError("%s: pred and gt must hold the same S >= 1 maps of H x W >= 1 pixels, got %r and %r" % (what, tuple(pred.shape), tuple(gt.shape)))
+    if S * H * W >= 1 << 31 or (scope == "view" and S > ops.L.DEPTHEVAL_MAX_GROUPS):
+        raise ValueError("%s: fewer than 2^31 pixels and at most %d views per call" % (what, ops.L.DEPTHEVAL_MAX_GROUPS))
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or valid.dim() not in (3, 4) or \
+                tuple(valid.shape[:3]) != (S, H, W) or (valid.dim() == 4 and valid.shape[-1] != 1):
+            raise ValueError("%s: valid must be a bool / uint8 tensor shaped like the maps" % what)
+    _depth_number(what, "min_depth", min_depth, 0.0)
+    _depth_number(what, "max_depth", max_depth)
+    if not all(t is None or t.is_cuda for t in (pred, gt, valid)):
+        raise ops.L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
+    shape = (S, H * W) if scope == "view" else (1, S * H * W)
+    p, g = (m.contiguous().reshape(shape) for m in maps)
+    v = None if valid is None else valid.reshape(S, H, W).contiguous().view(torch.uint8).reshape(shape)
+    return p, g, v, DEPTH_ALIGNMENTS[align]
+
+
+def _depth_coeff(p, g, v, mode, min_depth, max_depth):
+    """The alignment of every group -> (coeff f64 [G, 2], status int32 [G]); one pass over the maps, four for the median."""
+    L = ops.L
+    if mode == L.DEPTHEVAL_MEDIAN:
+        count, med = ops.deptheval_median(p, g, v, min_depth, max_depth)
+        return ops.deptheval_solve(mode, count, median=med)
+    counts, sums = ops.deptheval_sums(p, g, v, min_depth, max_depth)
+    return ops.deptheval_solve(mode, counts, sums=sums)
+
+
+def align_depth(pred, gt, valid=None, align="median", scope="view", min_depth=0.0, max_depth=float("inf")):
+    """The alignment a depth benchmark makes before it scores: gt ~ scale pred + shift over the USED pixels of a group -- valid (or
+    all), pred and gt finite, pred > 0, min_depth < gt <= max_depth. align: "none" (1, 0), "median" (ratio of the medians, the
+    protocol of scale-ambiguous predictions), "scale" (least squares through the origin), "scale_shift" (least squares, the protocol
+    of affine-invariant depth). scope: "view" fits every map on its own, "sequence" all S maps with one pair of coefficients.
+    pred, gt: float32 device tensors (S, H, W) or (S, H, W, 1); valid: bool / uint8 like them. The medians are exact order statistics
+    (a radix select per group: no sort, no compaction), the sums float64 in a fixed order: two calls give identical bytes.
+    -> (scale, shift, status): float64 / float64 / int32 device tensors [S] or [1]; a degenerate group (no used pixel, no spread, a
+    fit that is not positive and finite) gets (1, 0) and its DEPTH_* status bits. `scale` is what get_world_points_from_depth(gt_scale=)
+    and fuse_predictions take. Nothing is read back."""
+    p, g, v, mode = _depth_args("align_depth", pred, gt, valid, align, scope, min_depth, max_depth)
+    coeff, status = _depth_coeff(p, g, v, mode, min_depth, max_depth)
+    return coeff[:, 0], coeff[:, 1], status
+
+
+def depth_metrics(pred, gt, valid=None, align="median", scope="view", min_depth=0.0, max_depth=float("inf"), clip_min=1e-3, clip_max=None):
+    """AbsRel, SqRel, RMSE, MAE, RMSE-log and delta < 1.25 / 1.25^2 / 1.25^3 of predicted depth against ground truth after the
+    alignment of align_depth (same arguments), on the device: q = scale pred + shift, clipped to [clip_min, clip_max] (clip_min > 0
+    keeps the logarithm defined where a shift drives q below zero; clip_max None: no upper clip), scored against gt over the used
+    pixels. The term sums are float64 in the fixed order of include/omnivggt_hip.h, the ratios and roots float64 torch operations on
+    them. -> DepthMetrics (one device -> host read at the end, for its summary floats)."""
+    what = "depth_metrics"
+    cmin = _depth_number(what, "clip_min", clip_min, 0.0, lo_open=True)
+    cmax = float("inf") if clip_max is None else _depth_number(what, "clip_max", clip_max)
+    if cmin == float("inf") or cmax < cmin:
+        raise ValueError("%s: clip_min must be finite and clip_max >= clip_min, got %r, %r" % (what, clip_min, clip_max))
+    p, g, v, mode = _depth_args(what, pred, gt, valid, align, scope, min_depth, max_depth)
+    coeff, status = _depth_coeff(p, g, v, mode, min_depth, max_depth)
+    counts, sums = ops.deptheval_sums(p, g, v, min_depth, max_depth, coeff=coeff, clip_min=cmin, clip_max=cmax)
+    n = counts[:, 0]
+    nd = n.double()
+    mean = sums / nd[:, None]                                                 # 0 / 0 = nan for a group without a used pixel
+    per = torch.stack([mean[:, 0], mean[:, 1], mean[:, 2].sqrt(), mean[:, 3], mean[:, 4].sqrt(),
+                       counts[:, 1].double() / nd, counts[:, 2].double() / nd, counts[:, 3].double() / nd])            # [8, G]
+    has = n > 0
+    over_groups = torch.where(has, per, torch.zeros_like(per)).sum(1) / has.sum().double()
+    tn = nd.sum()
+    tm = sums.sum(0) / tn
+    pooled = torch.stack([tm[0], tm[1], tm[2].sqrt(), tm[3], tm[4].sqrt(), counts[:, 1].sum().double() / tn, counts[:, 2].sum().double() / tn,
+                          counts[:, 3].sum().double() / tn])
+    host = torch.cat([over_groups, pooled, tn[None]]).tolist()               # the one device -> host read
+    out = {k: per[i] for i, k in enumerate(DEPTH_FIGURES)}
+    out.update(n=n, scale=coeff[:, 0], shift=coeff[:, 1], status=status, align=align, scope=scope, n_total=int(host[16]),
+               mean=dict(zip(DEPTH_FIGURES, host[0:8])), pooled=dict(zip(DEPTH_FIGURES, host[8:16])))
+    return DepthMetrics(**out)
+
+
+def _pose_matrices(what, pred_extrinsic, gt_extrinsic, min_cameras):
+    es = []
+    for e, name in ((pred_extrinsic, "pred_extrinsic"), (gt_extrinsic, "gt_extrinsic")):
+        if not isinstance(e, torch.Tensor) or e.dim() != 3 or tuple(e.shape[1:]) not in ((3, 4), (4, 4)) or e.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s must be a float32 / float64 tensor (S, 3, 4) or (S, 4, 4)" % name)
+        es.append(e)
+    if es[0].shape[0] != es[1].shape[0] or es[0].shape[0] < min_cameras:
+        raise ValueError("%s pairs camera i with camera i and needs at least %d: %d predicted, %d ground-truth cameras"
+                         % (what, min_cameras, es[0].shape[0], es[1].shape[0]))
+    if not (es[0].is_cuda and es[1].is_cuda):
+        raise ops.L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
+    return es
+
+
+def _relative_poses(e):
+    """World-to-camera [A | t] (S, 3+, 4) -> (A_j A_i^-1, t_j - A_j A_i^-1 t_i) for all pairs i < j (i major), float64. The 3 x 3 inverse
+    is the adjugate over the determinant (cross products of the columns' partners): elementwise, no solver."""
+    A, t = e[:, :3, :3].double(), e[:, :3, 3].double()
+    S = A.shape[0]
+    i, j = torch.triu_indices(S, S, 1, device=e.device)
+    r0, r1, r2 = A[:, 0], A[:, 1], A[:, 2]
+    c0, c1, c2 = torch.linalg.cross(r1, r2), torch.linalg.cross(r2, r0), torch.linalg.cross(r0, r1)
+    det = (r0 * c0).sum(1)
+    inv = torch.stack([c0, c1, c2], 2) / det[:, None, None]
+    rel = A[j] @ inv[i]
+    return rel, t[j] - (rel @ t[i][:, :, None]).squeeze(-1)
+
+
+def relative_pose_errors(pred_extrinsic, gt_extrinsic):
+    """Relative pose errors over all pairs i < j of S >= 2 cameras, the figures RRA / RTA / AUC are made of: rel_ij = E_j E_i^-1 of the
+    world-to-camera matrices in float64 on the device -- unchanged by any similarity of the world frame, so no alignment is needed.
+    Rotation error: the angle of dR = R_pred R_gt^T as atan2(|vee(dR - dR^T)| / 2, (tr dR - 1) / 2) (accurate at 0 and at 180 degrees
+    alike); translation error: the angle between the two relative translations as atan2(|a x b|, a . b), folded to min(theta, 180 -
+    theta) (the sign of a direction is not observable), 0 when either is shorter than 1e-12.
+    pred_extrinsic, gt_extrinsic: float32 / float64 device tensors (S, 3, 4) or (S, 4, 4). -> (rot_err, trans_err) in degrees,
+    float64 device tensors [S (S - 1) / 2], pair (i, j) at i-major position. Nothing is read back."""
+    ep, eg = _pose_matrices("relative_pose_errors", pred_extrinsic, gt_extrinsic, 2)
+    (rp, a), (rg, b) = _relative_poses(ep), _relative_poses(eg)
+    dR = rp @ rg.transpose(1, 2)
+    w = torch.stack([dR[:, 2, 1] - dR[:, 1, 2], dR[:, 0, 2] - dR[:, 2, 0], dR[:, 1, 0] - dR[:, 0, 1]], 1)
+    rot = torch.rad2deg(torch.atan2(0.5 * torch.linalg.vector_norm(w, dim=1), (dR[:, 0, 0] + dR[:, 1, 1] + dR[:, 2, 2] - 1.0) / 2.0))
+    theta = torch.rad2deg(torch.atan2(torch.linalg.vector_norm(torch.linalg.cross(a, b), dim=1), (a * b).sum(1)))
+    trans = torch.minimum(theta, 180.0 - theta)
+    short = (torch.linalg.vector_norm(a, dim=1) < 1e-12) | (torch.linalg.vector_norm(b, dim=1) < 1e-12)
+    return rot, torch.where(short, torch.zeros_like(trans), trans)
+
+
+def pose_auc(rot_err, trans_err, thresholds=(5, 15, 30)):
+    """Relative pose accuracy from the errors of relative_pose_errors (degrees, device tensors of one length >= 1), for every integer
+    threshold t >= 1: "RRA@t" / "RTA@t" the share of pairs with rotation / translation error below t, "Acc@t" with both below it,
+    "AUC@t" the mean over the integer degrees d = 1 .. t of the share of pairs whose larger error lies below d. Counted in integers
+    on the device. -> dict of Python floats (one device -> host read)."""
+    for e, name in ((rot_err, "rot_err"), (trans_err, "trans_err")):
+        if not isinstance(e, torch.Tensor) or e.dim() != 1 or not e.dtype.is_floating_point or e.numel() < 1:
+            raise ValueError("pose_auc: %s must be a 1-D floating-point tensor with at least one pair" % name)
+    if rot_err.shape != trans_err.shape:
+        raise ValueError("pose_auc: %d rotation and %d translation errors" % (rot_err.numel(), trans_err.numel()))
+    ts = list(thresholds) if isinstance(thresholds, (tuple, list)) else None
+    if not ts or any(isinstance(t, bool) or not isinstance(t, int) or t < 1 or t > 180 for t in ts):
+        raise ValueError("pose_auc: thresholds must be a sequence of integer degrees in [1, 180], got %r" % (thresholds,))
+    if not (rot_err.is_cuda and trans_err.is_cuda):
+        raise ops.L.OvgError("pose_auc needs HIP device tensors: there is no CPU fallback")
+    r, t = rot_err.double(), trans_err.double()
+    worst = torch.maximum(r, t)
+    thr = torch.tensor(ts, device=r.device, dtype=torch.float64)
+    degrees = torch.arange(1, max(ts) + 1, device=r.device, dtype=torch.float64)
+    below = torch.cumsum((worst[:, None] < degrees[None, :]).sum(0), 0)       # [max t]: pairs-below-d summed over d = 1 .. t
+    counts = torch.cat([(r[:, None] < thr).sum(0), (t[:, None] < thr).sum(0), ((r[:, None] < thr) & (t[:, None] < thr)).sum(0),
+                        below[torch.tensor([x - 1 for x in ts], device=r.device)]]).tolist()
+    P, k, out = r.numel(), len(ts), {}
+    for i, x in enumerate(ts):
+        out["RRA@%d" % x], out["RTA@%d" % x], out["Acc@%d" % x] = counts[i] / P, counts[k + i] / P, counts[2 * k + i] / P
+        out["AUC@%d" % x] = counts[3 * k + i] / (P * x)
+    return out
+
+
+def evaluate_predictions(predictions, gt_depth=None, gt_valid=None, gt_extrinsic=None, batch_index=0, **kw):
+    """Scores batch element `batch_index` of the dict OmniVGGT.forward returns against whatever ground truth is given: with gt_depth
+    (S, H, W[, 1]) (and gt_valid) depth_metrics of predictions["depth"] (keywords: align, scope, min_depth, max_depth, clip_min,
+    clip_max); with gt_extrinsic (S, 3 | 4, 4) relative_pose_errors and pose_auc (keyword: thresholds) of the cameras decoded from
+    predictions["pose_enc"] (or predictions["extrinsic"] when present). -> a plain dict: "depth" (DepthMetrics), "rot_err",
+    "trans_err" (device tensors), "pose" (the pose_auc dict) -- each only when its ground truth was given."""
+    if not isinstance(predictions, dict):
+        raise ValueError("evaluate_predictions: predictions must be the dict OmniVGGT.forward returns")
+    if gt_depth is None and gt_extrinsic is None:
+        raise ValueError("evaluate_predictions: give gt_depth, gt_extrinsic or both")
+    thresholds = kw.pop("thresholds", (5, 15, 30))
+    unknown = set(kw) - {"align", "scope", "min_depth", "max_depth", "clip_min", "clip_max"}
+    if unknown:
+        raise ValueError("evaluate_predictions: unknown keywords %s" % sorted(unknown))
+    b, out = batch_index, {}
+    if gt_depth is not None:
+        if "depth" not in predictions:
+            raise ValueError("evaluate_predictions: predictions carry no `depth`")
+        out["depth"] = depth_metrics(predictions["depth"][b], gt_depth, gt_valid, **kw)
+    if gt_extrinsic is not None:
+        if "extrinsic" in predictions:
+            ext = predictions["extrinsic"][b]
+        elif "pose_enc" in predictions:
+            ext = pose_encoding_to_extri_intri(predictions["pose_enc"][b:b + 1], build_intrinsics=False)[0][0]
+        else:
+            raise ValueError("evaluate_predictions: predictions carry neither `extrinsic` nor `pose_enc`: the cameras are needed")
+        out["rot_err"], out["trans_err"] = relative_pose_errors(ext if ext.dtype in (torch.float32, torch.float64) else ext.float(), gt_extrinsic)
+        out["pose"] = pose_auc(out["rot_err"], out["trans_err"], thresholds)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # Plane segmentation: RANSAC over seeded hypotheses, least-squares refit, floor alignment (ovg_plane_*)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
