@@ -74,7 +74,9 @@ extern "C" {
  *     + mesh rasterisation: z-buffered, shaded triangles (ovg_render_mesh, ovg_render_mesh_workspace_bytes): added the same way
  *     + depth evaluation: masked per-group medians, aligned metric sums and the alignment solve (ovg_deptheval_median,
  *       ovg_deptheval_sums, ovg_deptheval_solve, ovg_deptheval_median_workspace_bytes, ovg_deptheval_sums_workspace_bytes): added the
- *       same way */
+ *       same way
+ *     + image-space map geometry: usable depth, normals, edge flags and the grid mesh of the prediction maps (ovg_map_depth,
+ *       ovg_map_normals, ovg_map_edges, ovg_map_triangulate, ovg_map_triangulate_workspace_bytes): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -1440,6 +1442,112 @@ typedef struct {
 } ovg_tsdf_extract_params;
 int64_t ovg_tsdf_extract_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int ovg_tsdf_extract(const ovg_tsdf_extract_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Image-space map geometry (added under ABI 13): what follows from the prediction being IMAGES -- depth / world_points are [S][H][W]
+ * maps in which a pixel's neighbours are known for free. Four entries, all stencils over the maps plus one ordered compaction, by
+ * exact rules that tests/mapgeom_twin.py restates in numpy; the device returns the twin's bytes. Every f32 step is one operation
+ * rounded on its own (no fused multiply-add), divisions and square roots are correctly rounded, comparisons with NaN fail.
+ * Pixel (s, y, x) has the flat index g = (s H + y) W + x. A stencil never leaves its view: neither the previous row's last pixel nor
+ * the neighbouring view's rows are ever neighbours. Nothing is allocated, nothing is read back, all work goes to the caller's stream,
+ * there are no atomics, two calls give identical bytes. Every entry answers OVG_E_ARG before its first HIP call (nothing is written)
+ * to NULL params, S, H, W <= 0 or S H W >= 2^31, a pointer that is not aligned to its element, and to what its paragraph lists.
+ *
+ * ovg_map_depth: the usable-depth map z [S][H][W] f32, which the three other entries read and nothing else to decide usability.
+ *   Exactly one of two inputs: points [S][H][W][3] with cams [S][16] (packed as for ovg_render_points), then z = camera_depth() of
+ *   csrc/ovg_project.h = ((c6 x + c7 y) + c8 z) + c11, rule 1 of ovg_multiview_consistency; or depth [S][H][W], then z = depth.
+ *   valid [S][H][W] u8 is optional. A pixel is USABLE when valid != 0 (if given), z is finite and z > near; z[g] is that value for a
+ *   usable pixel and the quiet NaN 0x7FC00000 otherwise. One thread per pixel, blockIdx.y = view (the camera row is wave-uniform).
+ *   OVG_E_ARG also: both or neither of points / depth, points without cams, NULL z, near not positive and finite.
+ *
+ * ovg_map_normals: normals [S][H][W][3] f32 from the point map P = points and z.
+ *   A neighbour q of p (same view, one step along a row or a column) is USABLE FOR p when z[q] is not NaN, the three coordinates
+ *   of P[q] are finite and |z[q] - z[p]| <= rel_tol * z[p]: one subtraction, one multiplication, inclusive; rel_tol = +inf switches
+ *   the test off (the product is +inf).
+ *   Horizontal difference dh (three f32 subtractions): P[x+1] - P[x-1] when both sides are usable for p, else P[x+1] - P[x] when the
+ *   right one is, else P[x] - P[x-1] when the left one is, else none. Vertical difference dv likewise along y (y+1 is "right").
+ *   p has NO NORMAL -- (0, 0, 0) is written -- when z[p] is NaN, a coordinate of P[p] is not finite, or either difference is missing.
+ *   Otherwise dh, dv are widened to float64 and n = dv x dh: nx = dv.y dh.z - dv.z dh.y, ny = dv.z dh.x - dv.x dh.z, nz = dv.x dh.y -
+ *   dv.y dh.x, every product and difference one float64 operation. With x to the right, y down and the camera looking along +z this
+ *   points back towards the camera: the "inside to outside" convention of the meshes. No camera is needed (a world point map differs
+ *   from camera coordinates by a proper rotation). l = sqrt((nx nx + ny ny) + nz nz) in float64; the output is n / l (float64
+ *   division) rounded to f32 when l is finite and > 0, else (0, 0, 0). One thread per pixel, no LDS: five point reads per pixel.
+ *   OVG_E_ARG also: NULL points / z / normals, rel_tol negative or NaN.
+ *
+ * ovg_map_edges: flags [S][H][W] u8, bits OVG_MAP_UNUSABLE, OVG_MAP_DEPTH_EDGE, OVG_MAP_NORMAL_EDGE, OVG_MAP_NO_NORMAL.
+ *   The WINDOW of p is the (2 radius + 1)^2 block around it clipped to the view, radius in {1, 2, 3}; only its usable pixels (z not
+ *   NaN) count, p included. A pixel whose z is NaN carries OVG_MAP_UNUSABLE alone. Otherwise:
+ *   - DEPTH_EDGE when zmax - zmin > rel_tol * z[p], zmax / zmin over the window: one subtraction, one multiplication, strict, no
+ *     division; rel_tol = +inf never flags;
+ *   - with normals [S][H][W][3] (optional): NO_NORMAL when all three components of n[p] equal 0; otherwise NORMAL_EDGE when any usable
+ *     q of the window whose normal is not (0, 0, 0) has (n[p].x n[q].x + n[p].y n[q].y) + n[p].z n[q].z < min_cos (f32). The caller
+ *     converts an angle to min_cos (in float64, rounded once to f32); min_cos = -inf never flags.
+ *   tile: OVG_MAP_TILE_256x1 is the plain form, 256 consecutive pixels of a view per workgroup and every window read from global
+ *   memory; the others stage the workgroup's width x height tile plus its halo of z (and the normals) in LDS once and read the up
+ *   to 49 window pixels from there. OVG_MAP_TILE_DEFAULT is the one DESIGN.md 12n names. The tile changes speed only, never a byte.
+ *   OVG_E_ARG also: NULL z / flags, radius outside {1, 2, 3}, rel_tol negative or NaN, with normals a NaN min_cos, an unknown tile.
+ *
+ * ovg_map_triangulate: the grid mesh of the S views -- two triangles per pixel quad, the faces that are not wanted dropped, the
+ * vertices compacted -- in two stages in the shape of ovg_tsdf_extract.
+ *   A pixel is a CORNER when z is not NaN, the three coordinates of points are finite and keep != 0 (keep [S][H][W] u8, optional).
+ *   The quad of (y, x), x < W - 1, y < H - 1, has a = (y, x), b = (y, x+1), c = (y+1, x), d = (y+1, x+1) and offers the faces
+ *   0: (a, c, b) and 1: (b, c, d): the diagonal is fixed at b-c, as in the reference's pts3d_to_trimesh, and the winding is such
+ *   that the triangle normal faces the camera (the direction of ovg_map_normals). A face is EMITTED when its three pixels are corners
+ *   and it is not TORN: (max z - min z of the three) > rel_tol * (min z of the three), one subtraction, one multiplication, strict;
+ *   rel_tol = +inf never tears. Faces leave in ascending (view, y, x, which of the two); a quad never spans two rows' ends or two
+ *   views. VERTICES are the pixels that an emitted face names, in ascending flat index; a pixel decides that from the at most six
+ *   faces around it (0 of its own quad, 0 and 1 of the quad to its left, 0 and 1 of the quad above, 1 of the quad above left).
+ *   stage OVG_MAP_COUNT: the face bits of every quad, the referenced pixels, per-workgroup counts (OVG_MAP_BLOCK pixels each) and
+ *   their scans into ws; out_count[0] = M vertices, out_count[1] = F faces (two int64, device). stage OVG_MAP_SCATTER reads what
+ *   COUNT left in ws and writes per vertex out_vertices [M][3] f32 (the point as it is), out_normals [M][3] f32 (the pixel of normals
+ *   [S][H][W][3] f32 as it is; (0, 0, 0) without), out_colors [M][3] u8 (the pixel of colors [S][H][W][3] u8; OVG_TSDF_GREY
+ *   without) and out_pixel_index [M] int64 (g), and out_faces [F][3] int32 indices into the vertices. Vertices at positions >=
+ *   vertex_capacity and faces at positions >= face_capacity are dropped (a face may then name a dropped vertex). Both stages in one
+ *   call need the capacities known in advance; the usual form is COUNT, read the counts, allocate, SCATTER with the same ws. Maps
+ *   without a face (H or W of 1, nothing usable) give M = F = 0 and OVG_OK.
+ *   ws: >= ovg_map_triangulate_workspace_bytes(S, H, W) bytes (an int32 vertex index and one byte per pixel and two int64 per
+ *   OVG_MAP_BLOCK pixels, each part rounded up to 256), 16-byte aligned; the query returns -1 for S, H, W <= 0 or S H W >= 2^31.
+ *   OVG_E_ARG also: NULL z / points / ws / out_count, rel_tol negative or NaN, an unknown stage, in SCATTER a negative capacity or a
+ *   NULL out_vertices / out_normals / out_colors / out_pixel_index (vertex_capacity > 0) or out_faces (face_capacity > 0), a
+ *   misaligned or undersized workspace.
+ *   Not in it: the reference's second, backward copy of every face (ovg_render_mesh draws both sides), per-face colours, smoothing.
+ * ------------------------------------------------------------------ */
+enum { OVG_MAP_UNUSABLE = 1, OVG_MAP_DEPTH_EDGE = 2, OVG_MAP_NORMAL_EDGE = 4, OVG_MAP_NO_NORMAL = 8 };
+enum { OVG_MAP_TILE_DEFAULT = 0, OVG_MAP_TILE_256x1 = 1, OVG_MAP_TILE_16x16 = 2, OVG_MAP_TILE_32x8 = 3, OVG_MAP_TILE_64x4 = 4 };
+enum { OVG_MAP_COUNT = 1, OVG_MAP_SCATTER = 2 };
+enum { OVG_MAP_BLOCK = 256, OVG_MAP_MAX_RADIUS = 3 };
+typedef struct {
+  const float* points; const float* cams; const float* depth; const uint8_t* valid;
+  int32_t S; int32_t H; int32_t W; float near;
+  float* z;
+} ovg_map_depth_params;
+int ovg_map_depth(const ovg_map_depth_params*, void* stream);
+
+typedef struct {
+  const float* points; const float* z;
+  int32_t S; int32_t H; int32_t W; float rel_tol;
+  float* normals;
+} ovg_map_normals_params;
+int ovg_map_normals(const ovg_map_normals_params*, void* stream);
+
+typedef struct {
+  const float* z; const float* normals;
+  int32_t S; int32_t H; int32_t W; int32_t radius;
+  float rel_tol; float min_cos; int32_t tile; int32_t pad;
+  uint8_t* flags;
+} ovg_map_edges_params;
+int ovg_map_edges(const ovg_map_edges_params*, void* stream);
+
+typedef struct {
+  const float* z; const float* points; const uint8_t* keep; const float* normals; const uint8_t* colors;
+  int32_t S; int32_t H; int32_t W; float rel_tol;
+  int32_t stage; int32_t pad;
+  int64_t vertex_capacity; int64_t face_capacity;
+  float* out_vertices; float* out_normals; uint8_t* out_colors; int64_t* out_pixel_index; int32_t* out_faces; int64_t* out_count;
+  void* ws; int64_t ws_bytes;
+} ovg_map_triangulate_params;
+int64_t ovg_map_triangulate_workspace_bytes(int32_t S, int32_t H, int32_t W);
+int ovg_map_triangulate(const ovg_map_triangulate_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

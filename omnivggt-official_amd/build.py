@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libomnivggt_hip.so")
 SOURCES = ["ovg_gemm.hip", "ovg_attn.hip", "ovg_elem.hip", "ovg_block.hip", "ovg_head.hip", "ovg_camhead.hip", "ovg_camtab.hip", "ovg_pointcloud.hip",
            "ovg_preprocess.hip", "ovg_render.hip", "ovg_consistency.hip", "ovg_nn.hip", "ovg_fps.hip", "ovg_radius.hip", "ovg_normals.hip",
-           "ovg_align.hip", "ovg_plane.hip", "ovg_tsdf.hip", "ovg_raster.hip", "ovg_deptheval.hip"]
+           "ovg_align.hip", "ovg_plane.hip", "ovg_tsdf.hip", "ovg_raster.hip", "ovg_deptheval.hip", "ovg_mapgeom.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # attention: no NaN can occur on valid inputs (masked scores are -inf, never inf-inf), and without
 # this hipcc inserts a canonicalising v_max before every fmaxf on an MFMA output (64 VALU / tile)
@@ -43,7 +43,9 @@ EXTRA_FLAGS = {"ovg_attn.hip": ["-fno-honor-nans"],
                # mesh rasterisation: the projection of csrc/ovg_project.h and the float64 depth and shading of tests/raster_twin.py
                "ovg_raster.hip": ["-ffp-contract=off"],
                # depth evaluation: the float64 moment and metric sums in the fixed order of tests/deptheval_twin.py, one rounding per operation
-               "ovg_deptheval.hip": ["-ffp-contract=off"]}
+               "ovg_deptheval.hip": ["-ffp-contract=off"],
+               # map geometry: the projection of csrc/ovg_project.h, the f32 differences and the float64 cross product of tests/mapgeom_twin.py
+               "ovg_mapgeom.hip": ["-ffp-contract=off"]}
 
 
 # attn16_kernel<bf16, QB, WAVES, MODE 0, RING, X3 0>: the three launches of the bf16 plan (mangled-name fragment -> QB)

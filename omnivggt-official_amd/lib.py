@@ -388,6 +388,32 @@ class TsdfExtractParams(C.Structure):
                 ("normals", vp), ("colors", vp), ("faces", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
+MAP_UNUSABLE, MAP_DEPTH_EDGE, MAP_NORMAL_EDGE, MAP_NO_NORMAL = 1, 2, 4, 8                       # bits of ovg_map_edges' flags
+MAP_TILE_DEFAULT, MAP_TILE_256x1, MAP_TILE_16x16, MAP_TILE_32x8, MAP_TILE_64x4 = 0, 1, 2, 3, 4  # ovg_map_edges_params.tile
+MAP_COUNT, MAP_SCATTER = 1, 2                                # ovg_map_triangulate_params.stage
+MAP_BLOCK, MAP_MAX_RADIUS = 256, 3                           # pixels per triangulation workgroup; largest window radius of ovg_map_edges
+
+
+class MapDepthParams(C.Structure):
+    _fields_ = [("points", vp), ("cams", vp), ("depth", vp), ("valid", vp), ("S", i32), ("H", i32), ("W", i32), ("near", f32), ("z", vp)]
+
+
+class MapNormalsParams(C.Structure):
+    _fields_ = [("points", vp), ("z", vp), ("S", i32), ("H", i32), ("W", i32), ("rel_tol", f32), ("normals", vp)]
+
+
+class MapEdgesParams(C.Structure):
+    _fields_ = [("z", vp), ("normals", vp), ("S", i32), ("H", i32), ("W", i32), ("radius", i32), ("rel_tol", f32), ("min_cos", f32),
+                ("tile", i32), ("pad", i32), ("flags", vp)]
+
+
+class MapTriangulateParams(C.Structure):
+    _fields_ = [("z", vp), ("points", vp), ("keep", vp), ("normals", vp), ("colors", vp), ("S", i32), ("H", i32), ("W", i32),
+                ("rel_tol", f32), ("stage", i32), ("pad", i32), ("vertex_capacity", i64), ("face_capacity", i64), ("out_vertices", vp),
+                ("out_normals", vp), ("out_colors", vp), ("out_pixel_index", vp), ("out_faces", vp), ("out_count", vp), ("ws", vp),
+                ("ws_bytes", i64)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -487,6 +513,11 @@ SYMBOLS = {
     "ovg_deptheval_sums": (i32, [C.POINTER(DepthEvalSumsParams), vp]),
     "ovg_deptheval_sums_workspace_bytes": (i64, [i64, i64]),
     "ovg_deptheval_solve": (i32, [C.POINTER(DepthEvalSolveParams), vp]),
+    "ovg_map_depth": (i32, [C.POINTER(MapDepthParams), vp]),
+    "ovg_map_normals": (i32, [C.POINTER(MapNormalsParams), vp]),
+    "ovg_map_edges": (i32, [C.POINTER(MapEdgesParams), vp]),
+    "ovg_map_triangulate": (i32, [C.POINTER(MapTriangulateParams), vp]),
+    "ovg_map_triangulate_workspace_bytes": (i64, [i32, i32, i32]),
 }
 
 

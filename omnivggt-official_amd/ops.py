@@ -1582,3 +1582,151 @@ def tsdf_extract(stage, tsdf, weight, origin, voxel, ws, min_weight=1.0, color=N
     p.vertices, p.normals, p.colors, p.faces, p.out_count = L.ptr(vertices), L.ptr(normals), L.ptr(colors), L.ptr(faces), L.ptr(out_count)
     p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
     L.call("ovg_tsdf_extract", p, _stream())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# image-space map geometry (ovg_map_depth, ovg_map_normals, ovg_map_edges, ovg_map_triangulate)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _map_tensor(what, t, name, dtype, shape, optional=False):
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise L.OvgError("%s: %s must be a contiguous %s tensor %r" % (what, name, str(dtype).replace("torch.", ""), list(shape)))
+
+
+def _map_shape(what, t, name, trailing=()):
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 + len(trailing) or tuple(t.shape[3:]) != tuple(trailing) or 0 in t.shape or \
+            t.numel() // max(1, int(torch.Size(trailing).numel())) >= 1 << 31:
+        raise L.OvgError("%s: %s must be a tensor [S, H, W%s], 1 <= S H W < 2^31" % (what, name, "".join(", %d" % v for v in trailing)))
+    return tuple(int(v) for v in t.shape[:3])
+
+
+def _map_tol(what, name, value, allow_inf=True):
+    import math
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not value >= 0 or (not allow_inf and math.isinf(value)):
+        raise L.OvgError("%s: %s must be a non-negative number%s, got %r" % (what, name, " (+inf switches the test off)" if allow_inf else "", value))
+    return float(value)
+
+
+def _map_out(what, t, name, dtype, shape, device):
+    if t is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    _map_tensor(what, t, name, dtype, shape)
+    return t
+
+
+def map_depth(points=None, cams=None, depth=None, valid=None, near=1e-3, out=None):
+    """ovg_map_depth on contiguous device tensors: exactly one of points f32 [S, H, W, 3] with cams f32 [S, 16] (packed as for
+    render_points) or depth f32 [S, H, W]; valid u8 [S, H, W] or None. -> z f32 [S, H, W] (`out`, or allocated here): the camera depth
+    of a usable pixel (valid, finite, > near), NaN otherwise. Nothing is read back."""
+    what = "map_depth"
+    if (points is None) == (depth is None):
+        raise L.OvgError("%s: exactly one of points / depth" % what)
+    if points is not None:
+        S, H, W = _map_shape(what, points, "points", (3,))
+        _map_tensor(what, points, "points", torch.float32, (S, H, W, 3))
+        _map_tensor(what, cams, "cams", torch.float32, (S, 16))
+    else:
+        S, H, W = _map_shape(what, depth, "depth")
+        _map_tensor(what, depth, "depth", torch.float32, (S, H, W))
+    _map_tensor(what, valid, "valid", torch.uint8, (S, H, W), True)
+    near = _tsdf_scalar(what, "near", near)
+    src = points if points is not None else depth
+    out = _map_out(what, out, "out", torch.float32, (S, H, W), src.device)
+    _chk_dev(points, cams, depth, valid, out)
+    p = L.MapDepthParams()
+    p.points, p.cams, p.depth, p.valid = L.ptr(points), L.ptr(cams) if points is not None else None, L.ptr(depth), L.ptr(valid)
+    p.S, p.H, p.W, p.near, p.z = S, H, W, near, L.ptr(out)
+    L.call("ovg_map_depth", p, _stream())
+    return out
+
+
+def map_normals(points, z, rel_tol=0.03, out=None):
+    """ovg_map_normals on contiguous device tensors: points f32 [S, H, W, 3], z f32 [S, H, W] (map_depth's). -> normals f32
+    [S, H, W, 3] (`out`, or allocated here), unit vectors towards the camera, (0, 0, 0) where the rule gives none."""
+    what = "map_normals"
+    S, H, W = _map_shape(what, points, "points", (3,))
+    _map_tensor(what, points, "points", torch.float32, (S, H, W, 3))
+    _map_tensor(what, z, "z", torch.float32, (S, H, W))
+    rel_tol = _map_tol(what, "rel_tol", rel_tol)
+    out = _map_out(what, out, "out", torch.float32, (S, H, W, 3), points.device)
+    _chk_dev(points, z, out)
+    p = L.MapNormalsParams()
+    p.points, p.z, p.S, p.H, p.W, p.rel_tol, p.normals = L.ptr(points), L.ptr(z), S, H, W, rel_tol, L.ptr(out)
+    L.call("ovg_map_normals", p, _stream())
+    return out
+
+
+def map_edges(z, normals=None, radius=1, rel_tol=0.03, min_cos=float("-inf"), tile=L.MAP_TILE_DEFAULT, out=None):
+    """ovg_map_edges on contiguous device tensors: z f32 [S, H, W], normals f32 [S, H, W, 3] or None; radius 1, 2 or 3; min_cos a
+    float32 value (not NaN). -> flags u8 [S, H, W] (`out`, or allocated here), bits L.MAP_UNUSABLE / MAP_DEPTH_EDGE /
+    MAP_NORMAL_EDGE / MAP_NO_NORMAL. tile: L.MAP_TILE_*, speed only."""
+    what = "map_edges"
+    S, H, W = _map_shape(what, z, "z")
+    _map_tensor(what, z, "z", torch.float32, (S, H, W))
+    _map_tensor(what, normals, "normals", torch.float32, (S, H, W, 3), True)
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= L.MAP_MAX_RADIUS:
+        raise L.OvgError("%s: radius must be 1 .. %d, got %r" % (what, L.MAP_MAX_RADIUS, radius))
+    rel_tol = _map_tol(what, "rel_tol", rel_tol)
+    if isinstance(min_cos, bool) or not isinstance(min_cos, (int, float)) or min_cos != min_cos:
+        raise L.OvgError("%s: min_cos must be a number, got %r" % (what, min_cos))
+    if isinstance(tile, bool) or not isinstance(tile, int) or not L.MAP_TILE_DEFAULT <= tile <= L.MAP_TILE_64x4:
+        raise L.OvgError("%s: unknown tile %r" % (what, tile))
+    out = _map_out(what, out, "out", torch.uint8, (S, H, W), z.device)
+    _chk_dev(z, normals, out)
+    p = L.MapEdgesParams()
+    p.z, p.normals, p.S, p.H, p.W, p.radius = L.ptr(z), L.ptr(normals), S, H, W, radius
+    p.rel_tol, p.min_cos, p.tile, p.pad, p.flags = rel_tol, float(min_cos), tile, 0, L.ptr(out)
+    L.call("ovg_map_edges", p, _stream())
+    return out
+
+
+def map_triangulate_workspace_bytes(S, H, W):
+    for v in (S, H, W):
+        if not -(1 << 31) <= int(v) < (1 << 31):
+            raise L.OvgError("ovg_map_triangulate_workspace_bytes: unsupported (S=%d, H=%d, W=%d)" % (S, H, W))
+    b = L.load().ovg_map_triangulate_workspace_bytes(int(S), int(H), int(W))
+    if b < 0:
+        raise L.OvgError("ovg_map_triangulate_workspace_bytes: unsupported (S=%d, H=%d, W=%d)" % (S, H, W))
+    return int(b)
+
+
+def map_triangulate(stage, z, points, ws, rel_tol=0.03, keep=None, normals=None, colors=None, out_count=None, vertex_capacity=0,
+                    face_capacity=0, vertices=None, out_normals=None, out_colors=None, pixel_index=None, faces=None):
+    """ovg_map_triangulate on contiguous device tensors: z f32 [S, H, W], points f32 [S, H, W, 3], keep u8 [S, H, W], normals f32
+    [S, H, W, 3] and colors u8 [S, H, W, 3] or None; ws a uint8 tensor of at least map_triangulate_workspace_bytes(S, H, W) bytes.
+    stage L.MAP_COUNT writes (vertices M, faces F) to the two int64 of out_count; L.MAP_SCATTER writes the first vertex_capacity
+    vertices to vertices / out_normals f32 [., 3], out_colors u8 [., 3] and pixel_index int64 [.] and the first face_capacity faces to
+    faces int32 [., 3] from what the COUNT stage left in ws."""
+    what = "map_triangulate"
+    S, H, W = _map_shape(what, z, "z")
+    _map_tensor(what, z, "z", torch.float32, (S, H, W))
+    _map_tensor(what, points, "points", torch.float32, (S, H, W, 3))
+    _map_tensor(what, keep, "keep", torch.uint8, (S, H, W), True)
+    _map_tensor(what, normals, "normals", torch.float32, (S, H, W, 3), True)
+    _map_tensor(what, colors, "colors", torch.uint8, (S, H, W, 3), True)
+    rel_tol = _map_tol(what, "rel_tol", rel_tol)
+    if stage not in (L.MAP_COUNT, L.MAP_SCATTER, L.MAP_COUNT | L.MAP_SCATTER):
+        raise L.OvgError("%s: unknown stage %r" % (what, stage))
+    for name, v in (("vertex_capacity", vertex_capacity), ("face_capacity", face_capacity)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 62:
+            raise L.OvgError("%s: %s must be a non-negative integer, got %r" % (what, name, v))
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    if stage & L.MAP_SCATTER:
+        outs = ((vertices, torch.float32, 3 * vertex_capacity), (out_normals, torch.float32, 3 * vertex_capacity),
+                (out_colors, torch.uint8, 3 * vertex_capacity), (pixel_index, torch.int64, vertex_capacity), (faces, torch.int32, 3 * face_capacity))
+        for t, dt, need in outs:
+            if need and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < need):
+                raise L.OvgError("%s: output buffers must be contiguous and hold the capacities" % what)
+    if not isinstance(out_count, torch.Tensor) or out_count.dtype != torch.int64 or out_count.numel() < 2 or not out_count.is_contiguous():
+        raise L.OvgError("%s: out_count must be a contiguous int64 device tensor of two elements" % what)
+    _chk_dev(z, points, keep, normals, colors, ws, out_count, vertices, out_normals, out_colors, pixel_index, faces)
+    p = L.MapTriangulateParams()
+    p.z, p.points, p.keep, p.normals, p.colors = L.ptr(z), L.ptr(points), L.ptr(keep), L.ptr(normals), L.ptr(colors)
+    p.S, p.H, p.W, p.rel_tol, p.stage, p.pad = S, H, W, rel_tol, int(stage), 0
+    p.vertex_capacity, p.face_capacity = vertex_capacity, face_capacity
+    p.out_vertices, p.out_normals, p.out_colors = L.ptr(vertices), L.ptr(out_normals), L.ptr(out_colors)
+    p.out_pixel_index, p.out_faces, p.out_count = L.ptr(pixel_index), L.ptr(faces), L.ptr(out_count)
+    p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
+    L.call("ovg_map_triangulate", p, _stream())

@@ -2635,3 +2635,323 @@ def write_mesh_glb(path, mesh, cameras=False, camera_scale=0.05):
             raise ValueError("write_mesh_glb: cameras=True needs a mesh with extrinsic and scene_scale")
         binary = _glb_add_cameras(gltf, node, binary, mesh.extrinsic, float(camera_scale) * float(mesh.scene_scale))
     _glb_write(path, gltf, binary)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Image-space map geometry: normals, edge masks and per-view meshes straight from the (S, H, W) maps (ovg_map_depth,
+# ovg_map_normals, ovg_map_edges, ovg_map_triangulate)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class MapEdges:
+    """Result of map_edges: flags (S,H,W) u8 with the bits ops.L.MAP_UNUSABLE / MAP_DEPTH_EDGE / MAP_NORMAL_EDGE / MAP_NO_NORMAL, and
+    the (S,H,W) bool views of it depth_edge, normal_edge and usable. Device tensors."""
+    __slots__ = ("flags", "depth_edge", "normal_edge", "usable")
+
+    def __init__(self, flags):
+        L = ops.L
+        self.flags = flags
+        self.depth_edge, self.normal_edge = (flags & L.MAP_DEPTH_EDGE) != 0, (flags & L.MAP_NORMAL_EDGE) != 0
+        self.usable = (flags & L.MAP_UNUSABLE) == 0
+
+
+class MapMesh(Mesh):
+    """A Mesh from triangulate_maps / predictions_to_mesh: additionally pixel_index (M,) int64, the flat index of every vertex into the
+    S x H x W maps it was built from, and conf_threshold (0-d f32 device tensor: predictions_to_mesh's percentile; else None)."""
+    __slots__ = ("pixel_index", "conf_threshold")
+
+    def __init__(self, vertices, faces, normals, colors, transform, extrinsic=None, scene_scale=None, pixel_index=None, conf_threshold=None):
+        Mesh.__init__(self, vertices, faces, normals, colors, transform, extrinsic, scene_scale)
+        self.pixel_index, self.conf_threshold = pixel_index, conf_threshold
+
+
+def _map_f32(what, name, value, positive=False, allow_inf=False):
+    """A host number as the float32 value the kernels see; None with allow_inf is +inf (the test switched off)."""
+    import math
+    import numpy as np
+    if value is None and allow_inf:
+        return float("inf")
+    try:
+        with np.errstate(over="ignore"):
+            v = float(np.float32(value))
+    except (TypeError, ValueError):
+        v = float("nan")
+    ok = not isinstance(value, bool) and (v > 0.0 if positive else v >= 0.0) and (allow_inf or math.isfinite(v))
+    if not ok:
+        raise ValueError("%s: %s must be %s in float32, got %r" % (what, name, "positive and finite" if positive else
+                                                                    "non-negative" + ("" if allow_inf else " and finite"), value))
+    return v
+
+
+def _map_points(what, points):
+    if not isinstance(points, torch.Tensor) or points.dim() != 4 or points.shape[3] != 3 or 0 in points.shape or not points.is_floating_point():
+        raise ValueError("%s: points must be a (S, H, W, 3) float tensor" % what)
+    S, H, W = (int(v) for v in points.shape[:3])
+    if S * H * W >= 1 << 31:
+        raise ValueError("%s: S = %d views of %d x %d exceed S * H * W < 2^31" % (what, S, H, W))
+    return S, H, W
+
+
+def _map_like(what, t, name, shape, dtypes):
+    if t is None:
+        return
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or not (t.dtype in dtypes if dtypes else t.is_floating_point()):
+        raise ValueError("%s: %s must be a %s tensor %r" % (what, name, "bool / uint8" if dtypes else "float", tuple(shape)))
+
+
+def _map_u8(t):
+    return None if t is None else (t.to(torch.uint8) if t.dtype == torch.bool else t).contiguous()
+
+
+def _map_need_device(what, *ts):
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise ops.L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
+
+
+def camera_depth_maps(points=None, extrinsic=None, depth=None, valid=None, near=1e-3):
+    """The usable-depth map z (S,H,W) f32 that map_normals, map_edges and triangulate_maps read (ovg_map_depth): a pixel's camera
+    depth where it is usable -- valid (if given), finite and > near -- and NaN elsewhere. Exactly one of two inputs: points
+    (S,H,W,3), world points in the frame of extrinsic (S,3,4) world-to-camera (device tensor, numpy array or list, rounded to f32),
+    whose depth is the third row of the camera transform; or depth (S,H,W) / (S,H,W,1), taken as it is. valid: optional (S,H,W)
+    bool / u8. No device -> host synchronisation; CPU tensors raise OvgError, bad shapes or near ValueError."""
+    what = "camera_depth_maps"
+    if (points is None) == (depth is None):
+        raise ValueError("%s: exactly one of points / depth" % what)
+    near32 = _map_f32(what, "near", near, positive=True)
+    if points is not None:
+        S, H, W = _map_points(what, points)
+        if extrinsic is None:
+            raise ValueError("%s: points need the extrinsic (S, 3, 4) of their views" % what)
+        ext = torch.as_tensor(extrinsic).detach()
+        if tuple(ext.shape) != (S, 3, 4):
+            raise ValueError("%s: extrinsic must be (S, 3, 4) = (%d, 3, 4), got %r" % (what, S, tuple(ext.shape)))
+        _map_like(what, valid, "valid", (S, H, W), (torch.bool, torch.uint8))
+        _map_need_device(what, points, valid)
+        cams = _pack_cams(ext, torch.eye(3), S, points.device)              # the intrinsics are not read
+        return ops.map_depth(points=points.float().contiguous(), cams=cams, valid=_map_u8(valid), near=near32)
+    if isinstance(depth, torch.Tensor) and depth.dim() == 4 and depth.shape[-1] == 1:
+        depth = depth[..., 0]
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or 0 in depth.shape or not depth.is_floating_point() or depth.numel() >= 1 << 31:
+        raise ValueError("%s: depth must be a (S, H, W) or (S, H, W, 1) float tensor, S * H * W < 2^31" % what)
+    _map_like(what, valid, "valid", tuple(depth.shape), (torch.bool, torch.uint8))
+    _map_need_device(what, depth, valid)
+    return ops.map_depth(depth=depth.float().contiguous(), valid=_map_u8(valid), near=near32)
+
+
+def map_normals(points, z, rel_tol=0.03):
+    """Normals (S,H,W,3) f32 of a point map from its own pixel grid (ovg_map_normals): the normalised cross product of the vertical
+    and the horizontal finite difference, central where both neighbours are usable, one-sided at the frame, next to unusable pixels
+    and across depth steps (a neighbour counts when |z_q - z_p| <= rel_tol * z_p; rel_tol None switches that off). They point back
+    towards the camera -- the outside of the surface, as Mesh normals do -- without needing the camera; pixels without both
+    differences carry (0, 0, 0). points (S,H,W,3), z = camera_depth_maps(...). The rule is exact (tests/mapgeom_twin.py restates it);
+    no search, no eigen-solve, no synchronisation. write_ply(normals=...) takes normals[flat indices of the cloud]."""
+    what = "map_normals"
+    S, H, W = _map_points(what, points)
+    _map_like(what, z, "z", (S, H, W), None)
+    tol32 = _map_f32(what, "rel_tol", rel_tol, allow_inf=True)
+    _map_need_device(what, points, z)
+    return ops.map_normals(points.float().contiguous(), z.float().contiguous(), rel_tol=tol32)
+
+
+def map_edges(z, normals=None, radius=1, rel_tol=0.03, max_angle_deg=None):
+    """Edge flags of the maps over a (2 radius + 1)^2 pixel window, radius 1, 2 or 3 (ovg_map_edges): a usable pixel is a DEPTH
+    EDGE when the usable depths of its window spread by more than rel_tol * its own depth -- the relative depth-edge test that removes
+    the flying pixels of a depth head at discontinuities, per view, without a search -- and, with normals (map_normals') and
+    max_angle_deg, a NORMAL EDGE when a window pixel's normal makes a larger angle with its own (cos < cos(max_angle_deg), the
+    float64 cosine rounded once to f32); pixels without a normal are flagged NO_NORMAL instead. z = camera_depth_maps(...).
+    -> MapEdges(flags, depth_edge, normal_edge, usable); edge_mask(result) is the keep mask. No synchronisation."""
+    import math
+    import numpy as np
+    what = "map_edges"
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or 0 in z.shape or not z.is_floating_point() or z.numel() >= 1 << 31:
+        raise ValueError("%s: z must be a (S, H, W) float tensor, S * H * W < 2^31" % what)
+    _map_like(what, normals, "normals", tuple(z.shape) + (3,), None)
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= ops.L.MAP_MAX_RADIUS:
+        raise ValueError("%s: radius must be 1, 2 or 3, got %r" % (what, radius))
+    tol32 = _map_f32(what, "rel_tol", rel_tol, allow_inf=True)
+    min_cos = float("-inf")
+    if max_angle_deg is not None:
+        if isinstance(max_angle_deg, bool) or not isinstance(max_angle_deg, (int, float)) or not 0.0 <= max_angle_deg <= 180.0:
+            raise ValueError("%s: max_angle_deg must be an angle in [0, 180], got %r" % (what, max_angle_deg))
+        if normals is None:
+            raise ValueError("%s: max_angle_deg needs normals" % what)
+        min_cos = float(np.float32(math.cos(math.radians(float(max_angle_deg)))))
+    _map_need_device(what, z, normals)
+    flags = ops.map_edges(z.float().contiguous(), None if normals is None else normals.float().contiguous(), radius=int(radius),
+                          rel_tol=tol32, min_cos=min_cos)
+    return MapEdges(flags)
+
+
+def edge_mask(result, depth=True, normal=False):
+    """(S,H,W) bool keep mask of a MapEdges: usable pixels that are no depth edge (depth=True) and no normal edge (normal=True);
+    pixels flagged NO_NORMAL stay. It is the keep_mask of predictions_to_point_cloud / fuse_predictions / predictions_to_mesh and the
+    valid of multiview_consistency / tsdf_integrate."""
+    if not isinstance(result, MapEdges):
+        raise ValueError("edge_mask: expected a MapEdges")
+    keep = result.usable
+    if depth:
+        keep = keep & ~result.depth_edge
+    if normal:
+        keep = keep & ~result.normal_edge
+    return keep
+
+
+def _prediction_maps(what, predictions, prediction_mode, batch_index, near, valid):
+    """-> (points (S,H,W,3) f32, z, confidence WITH its batch dimension or None, extrinsic, images with the batch dimension)."""
+    if not isinstance(predictions, dict):
+        raise ValueError("predictions must be a dictionary")
+    images = predictions["images"]
+    if images.dim() == 4:
+        images = images.unsqueeze(0)
+    B = images.shape[0]
+    if not isinstance(batch_index, int) or not 0 <= batch_index < B:
+        raise ValueError("batch_index %r out of range for a batch of %d" % (batch_index, B))
+    if not images.is_cuda:
+        raise ops.L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
+    S, H, W = images.shape[1], images.shape[-2], images.shape[-1]
+    pts, conf, extrinsic, _ = _prediction_geometry(predictions, prediction_mode, batch_index, images)
+    pts = pts.reshape(S, H, W, 3).float().contiguous()
+    z = camera_depth_maps(points=pts, extrinsic=extrinsic, valid=valid, near=near)
+    return pts, z, conf, extrinsic, images
+
+
+def prediction_normals(predictions, prediction_mode="Predicted Pointmap", batch_index=0, rel_tol=0.03, near=1e-3, valid=None):
+    """map_normals of the dict OmniVGGT.forward returns: the points by the choices predictions_to_point_cloud makes for
+    `prediction_mode`, their depth in the dict's cameras (`extrinsic`, else decoded from pose_enc). -> (normals (S,H,W,3), z (S,H,W))."""
+    pts, z, _, _, _ = _prediction_maps("prediction_normals", predictions, prediction_mode, batch_index, near, valid)
+    return map_normals(pts, z, rel_tol=rel_tol), z
+
+
+def prediction_edges(predictions, prediction_mode="Predicted Pointmap", batch_index=0, radius=1, rel_tol=0.03, max_angle_deg=None,
+                     near=1e-3, valid=None):
+    """map_edges of the dict OmniVGGT.forward returns, on the same maps as prediction_normals (the normals are computed only for
+    max_angle_deg). -> MapEdges; edge_mask(result) is the keep_mask of predictions_to_point_cloud."""
+    pts, z, _, _, _ = _prediction_maps("prediction_edges", predictions, prediction_mode, batch_index, near, valid)
+    normals = None if max_angle_deg is None else map_normals(pts, z, rel_tol=rel_tol)
+    return map_edges(z, normals, radius=radius, rel_tol=rel_tol, max_angle_deg=max_angle_deg)
+
+
+def _triangulate(what, pts, z, keep, colors, normals, tol32, extrinsic, conf_threshold=None):
+    """COUNT, the one read-back (the two counts with the first camera), SCATTER. -> MapMesh."""
+    import numpy as np
+    L = ops.L
+    S, H, W = (int(v) for v in z.shape)
+    dev = z.device
+    ws = torch.empty(ops.map_triangulate_workspace_bytes(S, H, W), device=dev, dtype=torch.uint8)
+    count = torch.empty(2, device=dev, dtype=torch.int64)
+    args = dict(z=z, points=pts, ws=ws, rel_tol=tol32, keep=keep, normals=normals, colors=colors, out_count=count)
+    ops.map_triangulate(L.MAP_COUNT, **args)
+    # the one synchronisation: both counts and the first camera in one copy (int64 counts are exact in float64 below 2^53)
+    first = extrinsic[0].reshape(-1).to(device=dev, dtype=torch.float64) if extrinsic is not None else torch.zeros(0, device=dev, dtype=torch.float64)
+    host = torch.cat([count.double(), first]).cpu().numpy()
+    M, F = int(host[0]), int(host[1])
+    transform = scene_alignment(host[2:14].reshape(3, 4)) if extrinsic is not None else np.eye(4)
+    vertices = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    out_normals = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    out_colors = torch.empty(M, 3, device=dev, dtype=torch.uint8)
+    index = torch.empty(M, device=dev, dtype=torch.int64)
+    faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    if M:
+        ops.map_triangulate(L.MAP_SCATTER, vertex_capacity=M, face_capacity=F, vertices=vertices, out_normals=out_normals, out_colors=out_colors,
+                            pixel_index=index, faces=faces, **args)
+        scale = ops.percentile(vertices, M, 3, 1, 3, [5.0, 95.0], norm=True)[1]
+    else:
+        scale = torch.ones((), device=dev, dtype=torch.float32)
+    return MapMesh(vertices, faces, out_normals, out_colors, transform, extrinsic, scale, index, conf_threshold)
+
+
+def triangulate_maps(points, z, keep=None, images=None, normals=None, rel_tol=0.03, extrinsic=None):
+    """The grid mesh of S point maps on the device (ovg_map_triangulate), what the reference's viz.pts3d_to_trimesh builds: two
+    triangles per 2 x 2 pixel quad, (a, c, b) and (b, c, d) with the diagonal b-c, wound so that they face the camera. A face is
+    emitted when its three pixels are usable in z (camera_depth_maps), finite and kept, and it is not torn: the spread of its three
+    depths is at most rel_tol times the smallest (None switches that off). Vertices are the pixels a face names, in pixel order, at
+    native resolution; faces in ascending (view, y, x). Deterministic and exact (tests/mapgeom_twin.py restates the rule).
+
+    points (S,H,W,3), z (S,H,W) device tensors; keep: optional (S,H,W) bool / u8 (edge_mask(...), a confidence test, ...); images:
+    (S,3,H,W) floats in [0, 1] or (S,H,W,3) u8 vertex colours (128 grey without); normals: optional (S,H,W,3) (map_normals') copied to
+    the vertices ((0, 0, 0) without). extrinsic (S,3,4): the views' cameras, for the alignment inv(E0) @ diag(1,-1,-1,1) @ R_y(180)
+    of the first one that the writers apply and for write_mesh_glb(cameras=True); without it the transform is the identity.
+    -> MapMesh (a Mesh with pixel_index), scene_scale = ||P95 - P5|| of its vertices: write_mesh_ply, write_mesh_glb, render_mesh and
+    mesh_to_point_cloud take it as it is. Exactly one device -> host synchronisation: the two counts, read with the first camera.
+    CPU tensors raise OvgError (there is no CPU fallback), bad shapes and values ValueError."""
+    what = "triangulate_maps"
+    S, H, W = _map_points(what, points)
+    _map_like(what, z, "z", (S, H, W), None)
+    _map_like(what, keep, "keep", (S, H, W), (torch.bool, torch.uint8))
+    _map_like(what, normals, "normals", (S, H, W, 3), None)
+    tol32 = _map_f32(what, "rel_tol", rel_tol, allow_inf=True)
+    colors = None
+    if images is not None:
+        try:
+            colors = _tsdf_colors(images, S, H, W)
+        except ValueError:
+            raise ValueError("%s: images must be (S, 3, H, W) = (%d, 3, %d, %d) floats in [0, 1] or (S, H, W, 3) uint8" % (what, S, H, W)) from None
+    ext = None
+    if extrinsic is not None:
+        ext = torch.as_tensor(extrinsic).detach()
+        if tuple(ext.shape) != (S, 3, 4):
+            raise ValueError("%s: extrinsic must be (S, 3, 4) = (%d, 3, 4), got %r" % (what, S, tuple(ext.shape)))
+    _map_need_device(what, points, z, keep, normals, colors)
+    return _triangulate(what, points.float().contiguous(), z.float().contiguous(), _map_u8(keep), colors,
+                        None if normals is None else normals.float().contiguous(), tol32, ext)
+
+
+def predictions_to_mesh(predictions, conf_thres=50.0, filter_by_frames="all", prediction_mode="Predicted Pointmap", keep_mask=None,
+                        rel_tol=0.03, edge_radius=1, with_normals=True, batch_index=0, min_conf=1e-5, near=1e-3):
+    """The per-view grid mesh of the dict OmniVGGT.forward returns, at native resolution: the quick look at a prediction that needs no
+    volume (fuse_predictions is the fused surface). The maps, the frame filter, the confidence rule and the alignment are
+    predictions_to_point_cloud's: points and confidence by `prediction_mode`, filter_by_frames "k: ..." keeps frame k, the threshold
+    is numpy's linear percentile of the selected frames' confidences (conf_thres None means 10, 0 skips it), a pixel is kept when
+    conf >= threshold and conf > min_conf, and, with keep_mask ((S,H,W) bool device tensor), where that is True. On top of that the
+    depth edges of map_edges(radius=edge_radius, rel_tol) are dropped (edge_radius 0 skips the test) -- the flying pixels between
+    a foreground and its background -- and triangulate_maps(rel_tol) drops torn faces. Colours come from `images`; with_normals fills
+    the vertex normals with map_normals(rel_tol), else they are (0, 0, 0) and render_mesh shades by face.
+    -> MapMesh with transform = inv(E0) @ diag(1,-1,-1,1) @ R_y(180) of the first selected camera, extrinsic, scene_scale, pixel_index
+    (flat indices into the selected frames' maps) and conf_threshold, so write_mesh_ply, write_mesh_glb(cameras=True), render_mesh
+    and mesh_to_point_cloud work on it unchanged. Exactly one device -> host synchronisation (the counts, read with the first
+    camera). CPU tensors raise OvgError: there is no CPU fallback."""
+    import numpy as np
+    what = "predictions_to_mesh"
+    if conf_thres is None:
+        conf_thres = 10.0
+    if isinstance(conf_thres, bool) or not isinstance(conf_thres, (int, float)) or not 0.0 <= conf_thres <= 100.0:
+        raise ValueError("%s: conf_thres must be a percentile in [0, 100], got %r" % (what, conf_thres))
+    if isinstance(edge_radius, bool) or not isinstance(edge_radius, (int, np.integer)) or not 0 <= edge_radius <= ops.L.MAP_MAX_RADIUS:
+        raise ValueError("%s: edge_radius must be 0 (no edge test), 1, 2 or 3, got %r" % (what, edge_radius))
+    tol32 = _map_f32(what, "rel_tol", rel_tol, allow_inf=True)
+    if isinstance(predictions, dict) and keep_mask is not None:
+        im = predictions["images"]
+        shape = (im.shape[-4], im.shape[-2], im.shape[-1])
+        if not isinstance(keep_mask, torch.Tensor) or keep_mask.dtype != torch.bool or tuple(keep_mask.shape) != shape:
+            raise ValueError("keep_mask must be a bool tensor (S, H, W) = %r at the map size" % (shape,))
+        _map_need_device(what, keep_mask)
+    pts, z, conf, extrinsic, images = _prediction_maps(what, predictions, prediction_mode, batch_index, near, None)
+    b = batch_index
+    S, H, W = (int(v) for v in z.shape)
+    conf = torch.ones(S, H, W, device=z.device, dtype=torch.float32) if conf is None else conf[b].reshape(S, H, W).float().contiguous()
+    img = images[b].reshape(S, 3, H, W)
+    _map_need_device(what, conf, extrinsic)
+    frame = _parse_frame(filter_by_frames)
+    if frame is not None:
+        if not -S <= frame < S:
+            raise ValueError("filter_by_frames selects frame %d of %d" % (frame, S))
+        frame %= S
+        sl = slice(frame, frame + 1)
+        pts, z, conf, img, extrinsic = pts[sl].contiguous(), z[sl].contiguous(), conf[sl].contiguous(), img[sl], extrinsic[sl]
+        keep_mask = None if keep_mask is None else keep_mask[sl]
+        S = 1
+    cf = conf.reshape(-1)
+    keep = cf > float(min_conf)
+    if conf_thres == 0.0:
+        conf_threshold = torch.zeros((), device=z.device, dtype=torch.float32)
+    else:
+        conf_threshold = ops.percentile(cf, cf.numel(), 1, 0, 1, [float(conf_thres)]).reshape(())
+        keep = keep & (cf >= conf_threshold)
+    keep = keep.reshape(S, H, W)
+    if keep_mask is not None:
+        keep = keep & keep_mask
+    if edge_radius:
+        flags = ops.map_edges(z, radius=int(edge_radius), rel_tol=tol32)
+        keep = keep & ((flags & ops.L.MAP_DEPTH_EDGE) == 0)
+    normals = ops.map_normals(pts, z, rel_tol=tol32) if with_normals else None
+    return _triangulate(what, pts, z, keep.to(torch.uint8), _tsdf_colors(img.float(), S, H, W), normals, tol32, extrinsic, conf_threshold)
