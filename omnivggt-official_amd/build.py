@@ -17,35 +17,13 @@ SOURCES = ["ovg_gemm.hip", "ovg_attn.hip", "ovg_elem.hip", "ovg_block.hip", "ovg
            "ovg_preprocess.hip", "ovg_render.hip", "ovg_consistency.hip", "ovg_nn.hip", "ovg_fps.hip", "ovg_radius.hip", "ovg_normals.hip",
            "ovg_align.hip", "ovg_plane.hip", "ovg_tsdf.hip", "ovg_raster.hip", "ovg_deptheval.hip", "ovg_mapgeom.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
+# every exact-arithmetic unit restates a numpy twin (tests/*_twin.py) operation for operation, one rounding each: no FMA contraction
+# anywhere in it, the inlined HIP header helpers and the shared primitives of csrc/ovg_geom.h and csrc/ovg_project.h included
+EXACT_UNITS = ("ovg_pointcloud.hip", "ovg_render.hip", "ovg_consistency.hip", "ovg_nn.hip", "ovg_fps.hip", "ovg_radius.hip", "ovg_normals.hip",
+               "ovg_align.hip", "ovg_plane.hip", "ovg_tsdf.hip", "ovg_raster.hip", "ovg_deptheval.hip", "ovg_mapgeom.hip")
 # attention: no NaN can occur on valid inputs (masked scores are -inf, never inf-inf), and without
 # this hipcc inserts a canonicalising v_max before every fmaxf on an MFMA output (64 VALU / tile)
-EXTRA_FLAGS = {"ovg_attn.hip": ["-fno-honor-nans"],
-               # point clouds: numpy's percentile lerp and norm, operation for operation (no FMA contraction, also in inlined HIP helpers)
-               "ovg_pointcloud.hip": ["-ffp-contract=off"],
-               # rendering: the projection of tests/render_twin.py in numpy float32, one rounding per operation
-               "ovg_render.hip": ["-ffp-contract=off"],
-               # multi-view consistency: the same projection (csrc/ovg_project.h) and tests/consistency_twin.py's band test
-               "ovg_consistency.hip": ["-ffp-contract=off"],
-               # nearest neighbours: tests/nn_twin.py's squared distance in numpy float32, one rounding per operation
-               "ovg_nn.hip": ["-ffp-contract=off"],
-               # farthest-point sampling: the same squared distance, restated by tests/fps_twin.py
-               "ovg_fps.hip": ["-ffp-contract=off"],
-               # radius search: the same squared distance and the cell function of tests/radius_twin.py, one rounding per operation
-               "ovg_radius.hip": ["-ffp-contract=off"],
-               # PCA normals: the float64 mean and covariance of tests/knn_twin.py, one rounding per operation
-               "ovg_normals.hip": ["-ffp-contract=off"],
-               # registration: the float64 moments in the fixed order of tests/align_twin.py and its apply, one rounding per operation
-               "ovg_align.hip": ["-ffp-contract=off"],
-               # plane segmentation: the float32 residual and the float64 hypotheses of tests/plane_twin.py, one rounding per operation
-               "ovg_plane.hip": ["-ffp-contract=off"],
-               # volumetric fusion: the projection of csrc/ovg_project.h, the running means and the surface nets of tests/tsdf_twin.py
-               "ovg_tsdf.hip": ["-ffp-contract=off"],
-               # mesh rasterisation: the projection of csrc/ovg_project.h and the float64 depth and shading of tests/raster_twin.py
-               "ovg_raster.hip": ["-ffp-contract=off"],
-               # depth evaluation: the float64 moment and metric sums in the fixed order of tests/deptheval_twin.py, one rounding per operation
-               "ovg_deptheval.hip": ["-ffp-contract=off"],
-               # map geometry: the projection of csrc/ovg_project.h, the f32 differences and the float64 cross product of tests/mapgeom_twin.py
-               "ovg_mapgeom.hip": ["-ffp-contract=off"]}
+EXTRA_FLAGS = {"ovg_attn.hip": ["-fno-honor-nans"], **{unit: ["-ffp-contract=off"] for unit in EXACT_UNITS}}
 
 
 # attn16_kernel<bf16, QB, WAVES, MODE 0, RING, X3 0>: the three launches of the bf16 plan (mangled-name fragment -> QB)

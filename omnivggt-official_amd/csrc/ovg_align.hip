@@ -3,8 +3,7 @@
 // similarity transform from them by Horn's quaternion method (a 4 x 4 cyclic Jacobi solve in one thread), and the transform applied.
 // The moments are a streaming reduction -- 24 bytes of points, up to 10 of index, masks and gate per pair, and a gather -- bound by
 // memory; the order is fixed by giving every thread its pairs, every wave its tree and every tile its slot: no atomics, no spinning.
-#include <math.h>
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 // the twin is one numpy float64 operation per rounding: no fused multiply-adds in this unit (build.py: -ffp-contract=off)
 #pragma clang fp contract(off)
@@ -15,38 +14,8 @@ constexpr int kThreads = OVG_ALIGN_THREADS;
 constexpr int kTile = OVG_ALIGN_TILE;
 constexpr int kRounds = kTile / kThreads;
 constexpr int kSums = OVG_ALIGN_SUMS;
-constexpr int kWaves = kThreads / 64;
 constexpr int kSlots = OVG_ALIGN_PARTIAL_BYTES / 8;       // a tile's partial: the int64 count, the 18 sums, one slot of padding
-static_assert(kWaves == 4 && kRounds >= 1 && kSlots >= kSums + 1, "the combine below is (w0 + w1) + (w2 + w3)");
-
-OVG_DEV bool finite_f(float v) { return fabsf(v) <= 3.4028234663852886e38f; }      // false for NaN
-OVG_DEV bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
-// steps 2 and 3 of the rule: v[l] += v[l + s] inside every wave, then (w0 + w1) + (w2 + w3); thread k < 18 of the workgroup leaves
-// with sum k, thread 18 with the count. All 256 threads call it.
-OVG_DEV void fold_block(double (&v)[kSums], long long cnt, int64_t* out_count, double* out_sums) {
-  __shared__ double part[kWaves][kSums];
-  __shared__ long long part_n[kWaves];
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) v[k] = v[k] + __shfl_down(v[k], s, 64);        // lanes >= 64 - s add their own value: never read below
-    cnt += __shfl_down(cnt, s, 64);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) part[wave][k] = v[k];
-    part_n[wave] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    const int k = threadIdx.x;
-    out_sums[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
-  } else if (threadIdx.x == kSums) {
-    *out_count = (int64_t)((part_n[0] + part_n[1]) + (part_n[2] + part_n[3]));
-  }
-}
+static_assert(kRounds >= 1 && kSlots >= kSums + 1, "a tile has pairs and its partial has room");
 
 __global__ __launch_bounds__(kThreads) void align_tiles(ovg_align_moments_params p) {
   const int64_t base = (int64_t)blockIdx.x * kTile + threadIdx.x;
@@ -59,7 +28,7 @@ __global__ __launch_bounds__(kThreads) void align_tiles(ovg_align_moments_params
   double v[kSums];
 #pragma unroll
   for (int k = 0; k < kSums; ++k) v[k] = 0.0;
-  long long cnt = 0;
+  long long cnt[1] = {0};
 #pragma unroll
   for (int r = 0; r < kRounds; ++r) {
     const int64_t i = base + (int64_t)r * kThreads;
@@ -73,7 +42,7 @@ __global__ __launch_bounds__(kThreads) void align_tiles(ovg_align_moments_params
     const float* ps = p.source + 3 * i;
     const float* qs = p.target + 3 * j;
     const float p0 = ps[0], p1 = ps[1], p2 = ps[2], q0 = qs[0], q1 = qs[1], q2 = qs[2];
-    if (!(finite_f(p0) && finite_f(p1) && finite_f(p2) && finite_f(q0) && finite_f(q1) && finite_f(q2))) continue;
+    if (!(finite_f32(p0) && finite_f32(p1) && finite_f32(p2) && finite_f32(q0) && finite_f32(q1) && finite_f32(q2))) continue;
     const double a[3] = {(double)p0 - c[0], (double)p1 - c[1], (double)p2 - c[2]};
     const double b[3] = {(double)q0 - c[3], (double)q1 - c[4], (double)q2 - c[5]};
     const double d0 = (double)q0 - (double)p0, d1 = (double)q1 - (double)p1, d2 = (double)q2 - (double)p2;
@@ -87,10 +56,10 @@ __global__ __launch_bounds__(kThreads) void align_tiles(ovg_align_moments_params
     v[15] = v[15] + ((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
     v[16] = v[16] + ((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
     v[17] = v[17] + ((d0 * d0 + d1 * d1) + d2 * d2);
-    ++cnt;
+    ++cnt[0];
   }
   double* slot = static_cast<double*>(p.ws) + (int64_t)blockIdx.x * kSlots;
-  fold_block(v, cnt, reinterpret_cast<int64_t*>(slot), slot + 1);
+  fold_block<kThreads>(v, cnt, reinterpret_cast<int64_t*>(slot), slot + 1);
 }
 
 // step 4: one workgroup over the tile partials, thread t the tiles t, t + 256, ... in that order
@@ -98,14 +67,14 @@ __global__ __launch_bounds__(kThreads) void align_fold(const double* ws, int64_t
   double v[kSums];
 #pragma unroll
   for (int k = 0; k < kSums; ++k) v[k] = 0.0;
-  long long cnt = 0;
+  long long cnt[1] = {0};
   for (int64_t g = threadIdx.x; g < tiles; g += kThreads) {
     const double* slot = ws + g * kSlots;
-    cnt += *reinterpret_cast<const long long*>(slot);
+    cnt[0] += *reinterpret_cast<const long long*>(slot);
 #pragma unroll
     for (int k = 0; k < kSums; ++k) v[k] = v[k] + slot[1 + k];
   }
-  fold_block(v, cnt, out_count, out_sums);
+  fold_block<kThreads>(v, cnt, out_count, out_sums);
 }
 
 // one Jacobi rotation in the (P, Q) plane of the symmetric 4 x 4 matrix A, accumulated into the columns P, Q of V (ovg_knn_normals'
@@ -133,9 +102,9 @@ __global__ __launch_bounds__(64) void align_solve(ovg_align_solve_params p) {
   const int64_t n = *p.count;
   double m[kSums], cen[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   bool finite = true;
-  for (int k = 0; k < kSums; ++k) m[k] = p.sums[k], finite = finite && finite_d(m[k]);
+  for (int k = 0; k < kSums; ++k) m[k] = p.sums[k], finite = finite && finite_f64(m[k]);
   if (p.centre) {
-    for (int k = 0; k < 6; ++k) cen[k] = p.centre[k], finite = finite && finite_d(cen[k]);
+    for (int k = 0; k < 6; ++k) cen[k] = p.centre[k], finite = finite && finite_f64(cen[k]);
   }
   int32_t status = 0;
   if (n < 3) status |= OVG_ALIGN_FEW_PAIRS;
@@ -180,11 +149,11 @@ __global__ __launch_bounds__(64) void align_solve(ovg_align_solve_params p) {
       }
       const double ma[3] = {m[0] / dn + cen[0], m[1] / dn + cen[1], m[2] / dn + cen[2]};
       const double mb[3] = {m[3] / dn + cen[3], m[4] / dn + cen[4], m[5] / dn + cen[5]};
-      bool ok = finite_d(scale);
+      bool ok = finite_f64(scale);
       for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) step[r][c] = scale * R[r][c], ok = ok && finite_d(step[r][c]);
+        for (int c = 0; c < 3; ++c) step[r][c] = scale * R[r][c], ok = ok && finite_f64(step[r][c]);
         step[r][3] = mb[r] - ((step[r][0] * ma[0] + step[r][1] * ma[1]) + step[r][2] * ma[2]);
-        ok = ok && finite_d(step[r][3]);
+        ok = ok && finite_f64(step[r][3]);
       }
       if (!ok) status |= OVG_ALIGN_NOT_FINITE;
     }
@@ -211,7 +180,7 @@ __global__ __launch_bounds__(64) void align_solve(ovg_align_solve_params p) {
     T[12] = 0.0, T[13] = 0.0, T[14] = 0.0, T[15] = 1.0;
   }
   if (p.out_scale) *p.out_scale = scale;
-  if (p.out_rms) *p.out_rms = (n >= 1 && finite_d(m[17])) ? sqrt(m[17] / dn) : 0.0;
+  if (p.out_rms) *p.out_rms = (n >= 1 && finite_f64(m[17])) ? sqrt(m[17] / dn) : 0.0;
   if (p.out_count) *p.out_count = n;
   if (p.out_status) *p.out_status = status;
 }
@@ -231,15 +200,13 @@ __global__ __launch_bounds__(kThreads) void align_apply(ovg_align_apply_params p
   d[0] = o[0], d[1] = o[1], d[2] = o[2];
 }
 
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
-bool size_ok(int64_t n) { return n >= 1 && n < (1ll << 31); }
 int64_t tiles_of(int64_t n) { return (n + kTile - 1) / kTile; }
 
 }  // namespace
 
 extern "C" int64_t ovg_align_workspace_bytes(int64_t n) {
   if (!size_ok(n)) return -1;
-  return (tiles_of(n) * OVG_ALIGN_PARTIAL_BYTES + 255) / 256 * 256;
+  return round256(tiles_of(n) * OVG_ALIGN_PARTIAL_BYTES);
 }
 
 extern "C" int ovg_align_moments(const ovg_align_moments_params* p, void* stream) {

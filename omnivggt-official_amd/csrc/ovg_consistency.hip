@@ -2,6 +2,7 @@
 // confirm it (support), look through it (violations) or cannot see it (occluded). Two launches: the own-depth maps z[S][H][W] into the
 // caller's workspace (unusable pixels as NaN, so that the pair kernel needs one read per pair), then one thread per source pixel with
 // the target views in a loop. No atomics and no communication between workgroups; the cost is the S (S - 1) H W gathered reads.
+#include "ovg_geom.h"
 #include "ovg_project.h"
 
 // tests/consistency_twin.py restates the rule in numpy float32, one rounding per operation: no fused multiply-adds in this unit
@@ -89,8 +90,6 @@ int mvc_launch(const ovg_consistency_params* p, hipStream_t st) {
   OVG_CHECK_LAUNCH();
   return OVG_OK;
 }
-
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 }  // namespace
 

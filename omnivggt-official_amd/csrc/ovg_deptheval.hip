@@ -3,8 +3,7 @@
 // float64 moment / metric sums of a group in the FIXED order of ovg_align_moments, and the alignment coefficients from either.
 // include/omnivggt_hip.h states the rule, tests/deptheval_twin.py restates it in numpy. Both hot kernels stream 8 (+ 1 mask) bytes per
 // pixel and are bound by memory; a select costs four such passes.
-#include <math.h>
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 // the twin is one numpy float64 operation per rounding: no fused multiply-adds in this unit (build.py: -ffp-contract=off)
 #pragma clang fp contract(off)
@@ -16,18 +15,14 @@ constexpr int kTile = OVG_DEPTHEVAL_TILE;
 constexpr int kRounds = kTile / kThreads;
 constexpr int kSums = OVG_DEPTHEVAL_SUMS;
 constexpr int kCounts = OVG_DEPTHEVAL_COUNTS;
-constexpr int kWaves = kThreads / 64;
 constexpr int kSlots = OVG_DEPTHEVAL_PARTIAL_BYTES / 8;   // a tile's partial: the 4 int64 counts, the 5 sums, one slot of padding
 constexpr int kChunk = OVG_DEPTHEVAL_CHUNK;
 constexpr int kChunkRounds = kChunk / kThreads;
 constexpr int kSel = 4;                                   // selections of a group: 2 m + r, map m (0 pred, 1 gt), rank r (0 lower, 1 upper middle)
 constexpr int kBins = 256;
 constexpr int kGroupWords = OVG_DEPTHEVAL_MEDIAN_GROUP_BYTES / 4;
-static_assert(kWaves == 4 && kRounds >= 1 && kSlots >= kSums + kCounts, "the combine below is (w0 + w1) + (w2 + w3)");
+static_assert(kRounds >= 1 && kSlots >= kSums + kCounts, "a tile has pixels and its partial has room");
 static_assert(kGroupWords == kSel * kBins + 2 * kSel && kChunk % kThreads == 0 && kThreads == kBins, "one thread per bin in the scan");
-
-OVG_DEV bool finite_f(float v) { return fabsf(v) <= 3.4028234663852886e38f; }      // false for NaN
-OVG_DEV bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
 // THE predicate of all three entries: is pixel i (an element offset into pred / gt / valid) used? Positive and finite is tested on
 // the bit pattern, so a subnormal pred counts whatever the denormal mode of the comparison would make of it.
@@ -35,7 +30,7 @@ OVG_DEV bool used_pixel(const float* pred, const float* gt, const uint8_t* valid
   if (valid && valid[i] == 0) return false;
   p = pred[i], g = gt[i];
   const uint32_t pb = __builtin_bit_cast(uint32_t, p);
-  return pb - 1u < 0x7f7fffffu && finite_f(g) && g > min_depth && g <= max_depth;
+  return pb - 1u < 0x7f7fffffu && finite_f32(g) && g > min_depth && g <= max_depth;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -141,35 +136,6 @@ __global__ __launch_bounds__(kThreads) void median_scan(ovg_deptheval_median_par
 // ---------------------------------------------------------------------------------------------------------------------------------
 // sums
 // ---------------------------------------------------------------------------------------------------------------------------------
-// steps 2 and 3 of the rule: v[l] += v[l + s] inside every wave, then (w0 + w1) + (w2 + w3); thread k < 5 of the workgroup leaves
-// with sum k, thread 5 + k with count k. All 256 threads call it.
-OVG_DEV void fold_block(double (&v)[kSums], long long (&cnt)[kCounts], int64_t* out_counts, double* out_sums) {
-  __shared__ double part[kWaves][kSums];
-  __shared__ long long part_n[kWaves][kCounts];
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) v[k] = v[k] + __shfl_down(v[k], s, 64);        // lanes >= 64 - s add their own value: never read below
-#pragma unroll
-    for (int k = 0; k < kCounts; ++k) cnt[k] += __shfl_down(cnt[k], s, 64);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) part[wave][k] = v[k];
-#pragma unroll
-    for (int k = 0; k < kCounts; ++k) part_n[wave][k] = cnt[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    const int k = threadIdx.x;
-    out_sums[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
-  } else if (threadIdx.x < kSums + kCounts) {
-    const int k = threadIdx.x - kSums;
-    out_counts[k] = (int64_t)((part_n[0][k] + part_n[1][k]) + (part_n[2][k] + part_n[3][k]));
-  }
-}
-
 template <int MODE> __global__ __launch_bounds__(kThreads) void sums_tiles(ovg_deptheval_sums_params p, int64_t tiles) {
   const int64_t grp = blockIdx.y;
   const int64_t row = grp * p.stride;
@@ -203,7 +169,7 @@ template <int MODE> __global__ __launch_bounds__(kThreads) void sums_tiles(ovg_d
     ++cnt[0];
   }
   double* slot = static_cast<double*>(p.ws) + (grp * tiles + blockIdx.x) * kSlots;
-  fold_block(v, cnt, reinterpret_cast<int64_t*>(slot), slot + kCounts);
+  fold_block<kThreads>(v, cnt, reinterpret_cast<int64_t*>(slot), slot + kCounts);
 }
 
 // step 4: one workgroup per group over its tile partials, thread t the tiles t, t + 256, ... in that order
@@ -220,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void sums_fold(const double* ws, int64_t 
 #pragma unroll
     for (int c = 0; c < kSums; ++c) v[c] = v[c] + slot[kCounts + c];
   }
-  fold_block(v, cnt, out_counts + grp * kCounts, out_sums + grp * kSums);
+  fold_block<kThreads>(v, cnt, out_counts + grp * kCounts, out_sums + grp * kSums);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -236,9 +202,9 @@ __global__ __launch_bounds__(64) void deptheval_solve(ovg_deptheval_solve_params
   double m[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0}, med[4] = {0.0, 0.0, 0.0, 0.0};
   bool finite = true;
   if (mode == OVG_DEPTHEVAL_SCALE || mode == OVG_DEPTHEVAL_SCALE_SHIFT) {
-    for (int k = 0; k < kSums; ++k) m[k] = p.sums[grp * kSums + k], finite = finite && finite_d(m[k]);
+    for (int k = 0; k < kSums; ++k) m[k] = p.sums[grp * kSums + k], finite = finite && finite_f64(m[k]);
   } else if (mode == OVG_DEPTHEVAL_MEDIAN) {
-    for (int k = 0; k < 4; ++k) med[k] = (double)p.median[grp * 4 + k], finite = finite && finite_d(med[k]);
+    for (int k = 0; k < 4; ++k) med[k] = (double)p.median[grp * 4 + k], finite = finite && finite_f64(med[k]);
   }
   if (!finite) status |= OVG_DEPTHEVAL_NOT_FINITE;
   double s = 1.0, t = 0.0;
@@ -259,14 +225,13 @@ __global__ __launch_bounds__(64) void deptheval_solve(ovg_deptheval_solve_params
         t = (m[1] - s * m[0]) / dn;
       }
     }
-    if (status == 0 && !(finite_d(s) && finite_d(t) && s > 0.0)) status |= OVG_DEPTHEVAL_BAD_FIT;
+    if (status == 0 && !(finite_f64(s) && finite_f64(t) && s > 0.0)) status |= OVG_DEPTHEVAL_BAD_FIT;
   }
   if (status != 0) s = 1.0, t = 0.0;
   p.coeff[2 * grp] = s, p.coeff[2 * grp + 1] = t;
   p.status[grp] = status;
 }
 
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 bool sizes_ok(int64_t groups, int64_t n) {
   return groups >= 1 && groups <= OVG_DEPTHEVAL_MAX_GROUPS && n >= 1 && n < (1ll << 31) && groups * n < (1ll << 31);
 }
@@ -280,12 +245,12 @@ int64_t tiles_of(int64_t n) { return (n + kTile - 1) / kTile; }
 
 extern "C" int64_t ovg_deptheval_median_workspace_bytes(int64_t groups, int64_t n) {
   if (!sizes_ok(groups, n)) return -1;
-  return (groups * OVG_DEPTHEVAL_MEDIAN_GROUP_BYTES + 255) / 256 * 256;
+  return round256(groups * OVG_DEPTHEVAL_MEDIAN_GROUP_BYTES);
 }
 
 extern "C" int64_t ovg_deptheval_sums_workspace_bytes(int64_t groups, int64_t n) {
   if (!sizes_ok(groups, n)) return -1;
-  return (groups * tiles_of(n) * OVG_DEPTHEVAL_PARTIAL_BYTES + 255) / 256 * 256;
+  return round256(groups * tiles_of(n) * OVG_DEPTHEVAL_PARTIAL_BYTES);
 }
 
 extern "C" int ovg_deptheval_median(const ovg_deptheval_median_params* p, void* stream) {

@@ -14,7 +14,7 @@
 // the workspace, the winner merged into the next step's key slot with a 64-bit unsigned atomic max (the mirror of ovg_nn.hip's atomic
 // min); the next launch reads it. Stream order is the only synchronisation between workgroups: nothing here ever waits for another
 // workgroup, every loop bound is an argument.
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 // tests/fps_twin.py restates the rule in numpy float32, one rounding per operation: no fused multiply-adds in this unit (build.py
 // compiles it with -ffp-contract=off as well)
@@ -42,10 +42,6 @@ bool fps_shape_ok(int64_t batch, int64_t n, int64_t npoint) {
 }
 // per cloud: npoint + 1 key slots (u64), then n mind (f32)
 int64_t fps_ws_per_cloud(int64_t n, int64_t npoint) { return (4 * n + 8 * (npoint + 1) + 15) / 16 * 16; }
-
-OVG_DEV bool finite3(float x, float y, float z) {
-  return (__float_as_uint(x) & kInfBits) != kInfBits && (__float_as_uint(y) & kInfBits) != kInfBits && (__float_as_uint(z) & kInfBits) != kInfBits;
-}
 
 // mind of a usable point is +0 .. 1e10: its bits order like its value. +inf marks an unusable point (never a candidate): key 0 = none,
 // below every real key, whose low word 0xFFFFFFFF - j is non-zero since j < 2^31. The larger key is the larger mind, then the LOWER j.
@@ -248,8 +244,6 @@ __global__ __launch_bounds__(256) void fps_distance(const void* __restrict__ ws,
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < (uint32_t)n) distance[(int64_t)blockIdx.y * n + i] = w.mind[i];
 }
-
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 }  // namespace
 

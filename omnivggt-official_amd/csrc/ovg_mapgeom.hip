@@ -2,6 +2,7 @@
 // being [S][H][W] maps in which a pixel's neighbours are known for free -- the usable-depth map, normals as a cross product of two
 // finite differences, depth / normal edge flags over a small window, and the grid mesh of the views by one ordered compaction.
 // All stencils stay inside their view; no atomics, no communication between workgroups except through the two scans of the mesh.
+#include "ovg_geom.h"
 #include "ovg_project.h"
 
 // tests/mapgeom_twin.py restates the rules in numpy, one rounding per operation: no fused multiply-adds in this unit
@@ -18,12 +19,10 @@ bool map_shape_ok(int32_t S, int32_t H, int32_t W) {
   return S > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && (int64_t)S * ((int64_t)H * W) < (1ll << 31);
 }
 int32_t per_view_blocks(int32_t hw) { return (int32_t)(((int64_t)hw + kThreads - 1) / kThreads); }   // S * this <= S H W < 2^31
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 bool pos_finite(float v) { return v > 0.0f && v <= 3.402823466e38f; }
 bool tol_ok(float v) { return v >= 0.0f; }                                // +inf switches a test off; negative and NaN are refused
 
 OVG_DEV float quiet_nan() { return __uint_as_float(0x7FC00000u); }
-OVG_DEV bool finite3(const float* __restrict__ p) { return finite_f32(p[0]) && finite_f32(p[1]) && finite_f32(p[2]); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // ovg_map_depth. One-dimensional grids throughout this unit (gridDim.y would cap S at 65535): workgroup b of view s is
@@ -218,18 +217,17 @@ int edges_launch(const ovg_map_edges_params* p, hipStream_t st) {
 // ovg_map_triangulate: face bits per quad, referenced pixels, two scans of per-workgroup counts, two scatters (the shape of
 // ovg_tsdf_extract)
 // ---------------------------------------------------------------------------------------------------------------------------------
-int64_t r256(int64_t b) { return (b + 255) / 256 * 256; }
 int64_t tri_blocks(int64_t n) { return (n + kThreads - 1) / kThreads; }
-int64_t tri_ws_bytes(int64_t n) { return r256(4 * n) + r256(n) + 2 * r256(8 * tri_blocks(n)); }
+int64_t tri_ws_bytes(int64_t n) { return round256(4 * n) + round256(n) + 2 * round256(8 * tri_blocks(n)); }
 
 struct TriWs { int32_t* vidx; uint8_t* fmask; int64_t* voff; int64_t* foff; };
 TriWs tri_ws(void* ws, int64_t n) {
   char* b = static_cast<char*>(ws);
   TriWs w;
   w.vidx = reinterpret_cast<int32_t*>(b);
-  w.fmask = reinterpret_cast<uint8_t*>(b + r256(4 * n));
-  w.voff = reinterpret_cast<int64_t*>(b + r256(4 * n) + r256(n));
-  w.foff = reinterpret_cast<int64_t*>(b + r256(4 * n) + r256(n) + r256(8 * tri_blocks(n)));
+  w.fmask = reinterpret_cast<uint8_t*>(b + round256(4 * n));
+  w.voff = reinterpret_cast<int64_t*>(b + round256(4 * n) + round256(n));
+  w.foff = reinterpret_cast<int64_t*>(b + round256(4 * n) + round256(n) + round256(8 * tri_blocks(n)));
   return w;
 }
 
@@ -243,32 +241,6 @@ OVG_DEV Pixel pixel_of(const ovg_map_triangulate_params& p, int64_t n) {
   l.x = (int32_t)(g - row * p.W);
   l.y = (int32_t)(row % p.H);
   return l;
-}
-
-OVG_DEV uint32_t wave_incl_scan_u32(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// exclusive rank of this thread's `c` items among the workgroup's, in thread order; total: the workgroup's sum. Every thread calls it.
-OVG_DEV uint32_t block_excl_scan(uint32_t c, uint32_t* wsum, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t incl = wave_incl_scan_u32(c);
-  __syncthreads();
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-  for (int w = 0; w < kThreads / 64; ++w) {
-    if (w < wave) before += wsum[w];
-    total += wsum[w];
-  }
-  return before + incl - c;
 }
 
 OVG_DEV bool torn(float z0, float z1, float z2, float rel_tol) {
@@ -297,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void tri_mark_faces(ovg_map_triangulate_p
   }
   if (l.in) ws.fmask[l.g] = (uint8_t)mask;
   uint32_t total;
-  block_excl_scan(__popc(mask), wsum, total);
+  block_excl_scan<kThreads>(__popc(mask), wsum, total);
   if (threadIdx.x == 0) ws.foff[blockIdx.x] = total;
 }
 
@@ -314,44 +286,17 @@ __global__ __launch_bounds__(kThreads) void tri_mark_vertices(ovg_map_triangulat
     ws.vidx[l.g] = ref ? 0 : -1;
   }
   uint32_t total;
-  block_excl_scan(ref, wsum, total);
+  block_excl_scan<kThreads>(ref, wsum, total);
   if (threadIdx.x == 0) ws.voff[blockIdx.x] = total;
-}
-
-OVG_DEV uint64_t wave_incl_scan_u64(uint64_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
 }
 
 // exclusive scans of the two per-workgroup count arrays in place, one workgroup of 1024 threads; the totals are the mesh sizes
 __global__ __launch_bounds__(1024) void tri_scan(TriWs ws, int64_t nblk, int64_t* out_count) {
-  __shared__ uint64_t wsum[16];
-  __shared__ uint64_t carry;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int which = 0; which < 2; ++which) {
     int64_t* counts = which ? ws.foff : ws.voff;
-    __syncthreads();
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < nblk; b0 += 1024) {
-      const int64_t b = b0 + threadIdx.x;
-      const uint64_t v = b < nblk ? (uint64_t)counts[b] : 0;
-      const uint64_t incl = wave_incl_scan_u64(v);
-      if (lane == 63) wsum[wave] = incl;
-      __syncthreads();
-      uint64_t excl = carry + incl - v;
-      for (int w = 0; w < wave; ++w) excl += wsum[w];
-      if (b < nblk) counts[b] = (int64_t)excl;
-      __syncthreads();
-      if (threadIdx.x == 1023) carry = excl + v;
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out_count[which] = (int64_t)carry;
+    __syncthreads();                                                      // the two scans share their LDS
+    const int64_t total = count_scan(counts, counts, nblk);
+    if (threadIdx.x == 0) out_count[which] = total;
   }
 }
 
@@ -361,7 +306,7 @@ __global__ __launch_bounds__(kThreads) void tri_vertices(ovg_map_triangulate_par
   const Pixel l = pixel_of(p, n);
   const bool active = l.in && ws.vidx[l.g] >= 0;
   uint32_t total;
-  const uint32_t rank = block_excl_scan(active, wsum, total);
+  const uint32_t rank = block_excl_scan<kThreads>(active, wsum, total);
   if (!active) return;
   const int64_t pos = ws.voff[blockIdx.x] + rank;                         // <= the number of pixels < 2^31
   ws.vidx[l.g] = (int32_t)pos;
@@ -386,7 +331,7 @@ __global__ __launch_bounds__(kThreads) void tri_faces(ovg_map_triangulate_params
   // tri_mark_faces' position test again: a workspace that COUNT did not fill must not send a read out of bounds
   const uint32_t mask = l.in && l.x < p.W - 1 && l.y < p.H - 1 ? ws.fmask[l.g] & 3u : 0u;
   uint32_t total;
-  const uint32_t rank = block_excl_scan(__popc(mask), wsum, total);
+  const uint32_t rank = block_excl_scan<kThreads>(__popc(mask), wsum, total);
   if (!mask) return;
   int64_t pos = ws.foff[blockIdx.x] + rank;
   if (pos < 0) return;

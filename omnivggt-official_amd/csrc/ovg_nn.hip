@@ -4,7 +4,7 @@
 // (groups of four points as x[4] y[4] z[4], so that a group is three 16-byte reads of an address all lanes share: a broadcast, no
 // bank conflicts) and walks it in ascending index with a strict "smaller than". One split stores its result; several merge the packed
 // (bits(d) << 32) | j with a 64-bit unsigned atomic min (as ovg_render.hip's z-buffer does) and a last launch decodes the keys.
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 // tests/nn_twin.py restates the rule in numpy float32, one rounding per operation: no fused multiply-adds in this unit (build.py
 // compiles it with -ffp-contract=off as well)
@@ -26,12 +26,8 @@ constexpr uint64_t kEmptyKey = ((uint64_t)kInfBits << 32) | 0xFFFFFFFFull;
 
 static_assert(kQueriesPerThread * kThreads == OVG_NN_QUERY_TILE && kRefTile % kThreads == 0 && kRefTile % 4 == 0, "tile shapes");
 
-bool nn_shape_ok(int64_t nq, int64_t nr) { return nq > 0 && nr > 0 && nq < (1ll << 31) && nr < (1ll << 31); }
+bool nn_shape_ok(int64_t nq, int64_t nr) { return size_ok(nq) && size_ok(nr); }
 int64_t nn_ws_bytes(int64_t nq) { return (nq * 8 + 15) / 16 * 16; }
-
-OVG_DEV bool finite3(float x, float y, float z) {
-  return (__float_as_uint(x) & kInfBits) != kInfBits && (__float_as_uint(y) & kInfBits) != kInfBits && (__float_as_uint(z) & kInfBits) != kInfBits;
-}
 
 __global__ __launch_bounds__(256) void nn_fill(uint64_t* __restrict__ keys, int32_t nq) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;                       // nq < 2^31: no wrap in unsigned arithmetic
@@ -147,8 +143,6 @@ __global__ __launch_bounds__(kThreads) void nn_search(const float* __restrict__ 
     }
   }
 }
-
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 }  // namespace
 

@@ -2,8 +2,7 @@
 // of `index` names, in float64 over the ranks in ascending order, and the unit eigenvector of the smallest eigenvalue by cyclic
 // Jacobi rotations (include/omnivggt_hip.h states the rule, tests/knn_twin.py restates the covariance operation for operation).
 // One query per thread: 2 k gathered points, six running sums and a 3 x 3 solve, bound by the gather of the index rows and points.
-#include <math.h>
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 // the twin's covariance is one numpy float64 operation per rounding: no fused multiply-adds in this unit (build.py: -ffp-contract=off)
 #pragma clang fp contract(off)
@@ -12,25 +11,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kSweeps = OVG_KNN_NORMALS_SWEEPS;
-
-// one Jacobi rotation in the (p, q) plane of a symmetric 3 x 3 matrix: app, aqq, apq its entries there, arp / arq the third row's;
-// vp, vq the matching columns of the accumulated rotations. theta^2 may overflow to +inf: t becomes 0, the rotation the identity
-OVG_DEV void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double (&vp)[3], double (&vq)[3]) {
-  if (apq == 0.0) return;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  app = app - t * apq, aqq = aqq + t * apq, apq = 0.0;
-  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-  arp = rp, arq = rq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double a = c * vp[k] - s * vq[k], b = s * vp[k] + c * vq[k];
-    vp[k] = a, vq[k] = b;
-  }
-}
-
-OVG_DEV bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN
 
 __global__ __launch_bounds__(kThreads) void knn_normals(ovg_knn_normals_params p) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -62,20 +42,12 @@ __global__ __launch_bounds__(kThreads) void knn_normals(ovg_knn_normals_params p
     c[0] = xx, c[1] = xy, c[2] = xz, c[3] = yy, c[4] = yz, c[5] = zz;
   }
   float n[3] = {0.0f, 0.0f, 0.0f}, curv = 0.0f;
-  if (m >= 3 && finite_d(xx) && finite_d(xy) && finite_d(xz) && finite_d(yy) && finite_d(yz) && finite_d(zz)) {
-    double v0[3] = {1.0, 0.0, 0.0}, v1[3] = {0.0, 1.0, 0.0}, v2[3] = {0.0, 0.0, 1.0};
+  if (m >= 3 && finite_f64(xx) && finite_f64(xy) && finite_f64(xz) && finite_f64(yy) && finite_f64(yz) && finite_f64(zz)) {
+    double v0[3], v1[3], v2[3], e[3];
     const double trace = (xx + yy) + zz;
-    for (int s = 0; s < kSweeps; ++s) {
-      jacobi_rotate(xx, yy, xy, xz, yz, v0, v1);       // (0, 1): the third index is 2
-      jacobi_rotate(xx, zz, xz, xy, yz, v0, v2);       // (0, 2): the third index is 1
-      jacobi_rotate(yy, zz, yz, xy, xz, v1, v2);       // (1, 2): the third index is 0
-    }
-    // the smallest diagonal entry, the lowest column on ties
-    double lam = xx, e[3] = {v0[0], v0[1], v0[2]};
-    if (yy < lam) lam = yy, e[0] = v1[0], e[1] = v1[1], e[2] = v1[2];
-    if (zz < lam) lam = zz, e[0] = v2[0], e[1] = v2[1], e[2] = v2[2];
-    const double len = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-    e[0] = e[0] / len, e[1] = e[1] / len, e[2] = e[2] / len;
+    jacobi_sweeps3(xx, xy, xz, yy, yz, zz, v0, v1, v2, kSweeps);
+    int kmin;
+    const double lam = jacobi_smallest(xx, yy, zz, v0, v1, v2, kmin, e);
     bool flip;
     if (p.viewpoint) {
       const float* v = p.viewpoint + (int64_t)p.viewpoint_stride * i;
@@ -97,13 +69,11 @@ __global__ __launch_bounds__(kThreads) void knn_normals(ovg_knn_normals_params p
   if (p.curvature) p.curvature[i] = curv;
 }
 
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int ovg_knn_normals(const ovg_knn_normals_params* p, void* stream) {
   if (!p || !p->query || !p->reference || !p->index || !p->normal) return OVG_E_ARG;
-  if (p->nq <= 0 || p->nr <= 0 || p->nq >= (1ll << 31) || p->nr >= (1ll << 31) || p->k < 1) return OVG_E_ARG;
+  if (!size_ok(p->nq) || !size_ok(p->nr) || p->k < 1) return OVG_E_ARG;
   if (p->viewpoint ? (p->viewpoint_stride != 0 && p->viewpoint_stride != 3) : p->viewpoint_stride != 0) return OVG_E_ARG;
   if (!al(p->query, 4) || !al(p->reference, 4) || !al(p->index, 4) || !al(p->viewpoint, 4) || !al(p->normal, 4) || !al(p->curvature, 4) ||
       !al(p->covariance, 8) || !al(p->used, 4))

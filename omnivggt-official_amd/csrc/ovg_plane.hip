@@ -5,8 +5,7 @@
 // one point tile after the other in LDS (groups of four points as x[4] y[4] z[4]: three 16-byte reads of an address all lanes share,
 // a broadcast without bank conflicts) and walks it with no cross-lane traffic; a split adds its counters with one integer atomic
 // per hypothesis. Integer sums do not depend on the order of arrival: identical bytes run to run and for every split count.
-#include <math.h>
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 // tests/plane_twin.py restates the residual in numpy float32 and the hypotheses in float64, one rounding per operation: no fused
 // multiply-adds in this unit (build.py compiles it with -ffp-contract=off as well)
@@ -21,14 +20,9 @@ constexpr int kTargetWorkgroups = 2048;              // auto splits: 256 CUs x 4
 constexpr int kMaxSplits = 65535;                    // gridDim.y
 constexpr int kFlat = 256;                           // threads of the one-item-per-thread launches
 constexpr int kMaskPerThread = 4;                    // points per thread of plane_mask: one atomic per 1024 points
-constexpr uint32_t kInfBits = 0x7F800000u;
 constexpr uint32_t kNanBits = 0x7FC00000u;
 
 static_assert(kPlanesPerThread * kThreads == OVG_PLANE_HYP_TILE && kPointTile % kThreads == 0 && kPointTile % 4 == 0, "tile shapes");
-
-OVG_DEV bool finite_bits(float v) { return (__float_as_uint(v) & kInfBits) != kInfBits; }
-OVG_DEV bool finite3(float x, float y, float z) { return finite_bits(x) && finite_bits(y) && finite_bits(z); }
-OVG_DEV bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN
 
 OVG_DEV uint64_t mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
@@ -192,7 +186,7 @@ __global__ __launch_bounds__(kFlat) void plane_select(ovg_plane_select_params p)
   bool found = c >= p.min_inliers;
   if (found) {
     const float* s = p.planes + 4 * (int64_t)h;
-    found = finite_bits(s[0]) && finite_bits(s[1]) && finite_bits(s[2]) && finite_bits(s[3]);
+    found = finite_f32(s[0]) && finite_f32(s[1]) && finite_f32(s[2]) && finite_f32(s[3]);
     if (found) q[0] = s[0], q[1] = s[1], q[2] = s[2], q[3] = s[3];
   }
   *p.best = found ? h : -1;
@@ -222,32 +216,8 @@ __global__ __launch_bounds__(kFlat) void plane_mask(ovg_plane_mask_params p) {
     if (p.distance) p.distance[i] = e;
     cnt += in ? 1 : 0;
   }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) cnt += __shfl_down(cnt, s, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t total = 0;
-#pragma unroll
-    for (int k = 0; k < kFlat / 64; ++k) total += part[k];
-    if (total != 0) atomicAdd(reinterpret_cast<unsigned long long*>(p.out_count), (unsigned long long)total);
-  }
-}
-
-// ovg_knn_normals' rotation (csrc/ovg_normals.hip): theta^2 may overflow to +inf, t becomes 0 and the rotation the identity
-OVG_DEV void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double (&vp)[3], double (&vq)[3]) {
-  if (apq == 0.0) return;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  app = app - t * apq, aqq = aqq + t * apq, apq = 0.0;
-  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-  arp = rp, arq = rq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double a = c * vp[k] - s * vq[k], b = s * vp[k] + c * vq[k];
-    vp[k] = a, vq[k] = b;
-  }
+  const int32_t total = block_reduce<kFlat>(cnt, part, IntSum());
+  if (threadIdx.x == 0 && total != 0) atomicAdd(reinterpret_cast<unsigned long long*>(p.out_count), (unsigned long long)total);
 }
 
 __global__ __launch_bounds__(64) void plane_fit(ovg_plane_fit_params p) {
@@ -255,9 +225,9 @@ __global__ __launch_bounds__(64) void plane_fit(ovg_plane_fit_params p) {
   const int64_t n = *p.count;
   double m[OVG_ALIGN_SUMS], cen[3] = {0.0, 0.0, 0.0};
   bool finite = true;
-  for (int k = 0; k < OVG_ALIGN_SUMS; ++k) m[k] = p.sums[k], finite = finite && finite_d(m[k]);
+  for (int k = 0; k < OVG_ALIGN_SUMS; ++k) m[k] = p.sums[k], finite = finite && finite_f64(m[k]);
   if (p.centre) {
-    for (int k = 0; k < 6; ++k) finite = finite && finite_d(p.centre[k]);
+    for (int k = 0; k < 6; ++k) finite = finite && finite_f64(p.centre[k]);
     for (int k = 0; k < 3; ++k) cen[k] = p.centre[k];
   }
   int32_t status = 0;
@@ -269,38 +239,27 @@ __global__ __launch_bounds__(64) void plane_fit(ovg_plane_fit_params p) {
     double xx = m[6] - (m[0] * m[0]) / dn, xy = m[7] - (m[0] * m[1]) / dn, xz = m[8] - (m[0] * m[2]) / dn;
     double yy = m[10] - (m[1] * m[1]) / dn, yz = m[11] - (m[1] * m[2]) / dn, zz = m[14] - (m[2] * m[2]) / dn;
     const double g[3] = {m[0] / dn + cen[0], m[1] / dn + cen[1], m[2] / dn + cen[2]};
-    double v0[3] = {1.0, 0.0, 0.0}, v1[3] = {0.0, 1.0, 0.0}, v2[3] = {0.0, 0.0, 1.0};
-    for (int s = 0; s < OVG_KNN_NORMALS_SWEEPS; ++s) {
-      jacobi_rotate(xx, yy, xy, xz, yz, v0, v1);       // (0, 1): the third index is 2
-      jacobi_rotate(xx, zz, xz, xy, yz, v0, v2);       // (0, 2): the third index is 1
-      jacobi_rotate(yy, zz, yz, xy, xz, v1, v2);       // (1, 2): the third index is 0
-    }
-    // the smallest diagonal entry, the lowest column on ties; of the two others the larger and the smaller
+    double v0[3], v1[3], v2[3], e[3];
+    jacobi_sweeps3(xx, xy, xz, yy, yz, zz, v0, v1, v2, OVG_KNN_NORMALS_SWEEPS);
+    // the smallest eigenvalue and its unit eigenvector (ovg_knn_normals' rule); of the two others the larger and the smaller
     const double lam[3] = {xx, yy, zz};
-    int kmin = 0;
-    if (yy < lam[kmin]) kmin = 1;
-    if (zz < lam[kmin]) kmin = 2;
+    int kmin;
+    const double low = jacobi_smallest(xx, yy, zz, v0, v1, v2, kmin, e);
     const int ka = kmin == 0 ? 1 : 0, kb = kmin == 2 ? 1 : 2;
     const double mid = lam[ka] < lam[kb] ? lam[ka] : lam[kb], top = lam[ka] < lam[kb] ? lam[kb] : lam[ka];
     if (!(mid > OVG_PLANE_SPREAD_EPS * top)) {
       status |= OVG_PLANE_NO_SPREAD;
     } else {
-      double e[3];
-      if (kmin == 0) e[0] = v0[0], e[1] = v0[1], e[2] = v0[2];
-      else if (kmin == 1) e[0] = v1[0], e[1] = v1[1], e[2] = v1[2];
-      else e[0] = v2[0], e[1] = v2[1], e[2] = v2[2];
-      const double len = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-      e[0] = e[0] / len, e[1] = e[1] / len, e[2] = e[2] / len;
       double d = 0.0;
       if (p.axis) d = (e[0] * (double)p.axis[0] + e[1] * (double)p.axis[1]) + e[2] * (double)p.axis[2];
       if (flip_normal(e, p.axis != nullptr, d)) e[0] = -e[0], e[1] = -e[1], e[2] = -e[2];
       const double w = -((e[0] * g[0] + e[1] * g[1]) + e[2] * g[2]);
       const float q[4] = {(float)e[0], (float)e[1], (float)e[2], (float)w};
-      if (finite_bits(q[0]) && finite_bits(q[1]) && finite_bits(q[2]) && finite_bits(q[3]) && finite_d(lam[kmin]) && finite_d(top)) {
+      if (finite_f32(q[0]) && finite_f32(q[1]) && finite_f32(q[2]) && finite_f32(q[3]) && finite_f64(low) && finite_f64(top)) {
         p.plane[0] = q[0], p.plane[1] = q[1], p.plane[2] = q[2], p.plane[3] = q[3];
         // a scatter matrix is positive semi-definite: a negative smallest eigenvalue is rounding, reported as 0
-        rms = sqrt((lam[kmin] > 0.0 ? lam[kmin] : 0.0) / dn);
-        eig[0] = lam[kmin], eig[1] = mid, eig[2] = top;
+        rms = sqrt((low > 0.0 ? low : 0.0) / dn);
+        eig[0] = low, eig[1] = mid, eig[2] = top;
       } else {
         status |= OVG_PLANE_NOT_FINITE;
       }
@@ -311,8 +270,6 @@ __global__ __launch_bounds__(64) void plane_fit(ovg_plane_fit_params p) {
   if (p.status) *p.status = status;
 }
 
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
-bool size_ok(int64_t n) { return n >= 1 && n < (1ll << 31); }
 bool threshold_ok(float t) { return t >= 0.0f && t <= 3.4028234663852886e38f; }     // false for NaN and +inf
 
 }  // namespace

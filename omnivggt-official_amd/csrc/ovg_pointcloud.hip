@@ -3,7 +3,7 @@
 // Every kernel is HBM bound: the selection reads each key three times and the filter reads conf / image twice; no launch waits on the host.
 // Voxel-grid decimation of a selected cloud (ovg_voxel_downsample) shares the filter's count / scan / scatter; its hash stage is bound
 // by random 64-bit atomics, not by bandwidth.
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 // the percentile's lerp and the scene-scale norm restate numpy's f32 / f64 operation sequence: no fused multiply-adds anywhere in this
 // unit. The pragma covers the code below; build.py also compiles the unit with -ffp-contract=off, which reaches the inlined HIP header
@@ -111,16 +111,6 @@ __global__ __launch_bounds__(kThreads) void pct_hist(ovg_percentile_params p, ui
   uint64_t* g = hist + (int64_t)c * kHistWords + (PASS == 1 ? 0 : (PASS == 2 ? kBins1 : kBins1 + kSlots * kBins2));
   for (int i = threadIdx.x; i < nslot * BINS; i += kThreads)
     if (h[i]) __hip_atomic_fetch_add(&g[i], (uint64_t)h[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-OVG_DEV uint64_t wave_incl_scan(uint64_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
 }
 
 OVG_DEV float lerp_numpy(float a, float b, float t) {
@@ -238,21 +228,11 @@ struct PfWs {
 };
 
 int64_t pf_blocks(int64_t n) { return (n + kTile - 1) / kTile; }
-int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
 int64_t pf_ws_bytes(int64_t n) { return round256(n) + 2 * round256(pf_blocks(n) * 8); }
 PfWs pf_ws(const ovg_point_filter_params* p) {
   uint8_t* b = static_cast<uint8_t*>(p->ws);
   const int64_t nb = pf_blocks(p->n);
   return {b, reinterpret_cast<int64_t*>(b + round256(p->n)), reinterpret_cast<int64_t*>(b + round256(p->n) + round256(nb * 8))};
-}
-
-OVG_DEV int64_t block_sum(int64_t v, int64_t* red) {
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int64_t t = 0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-  return t;
 }
 
 __global__ __launch_bounds__(kThreads) void pf_mask(ovg_point_filter_params p, PfWs ws) {
@@ -269,31 +249,14 @@ __global__ __launch_bounds__(kThreads) void pf_mask(ovg_point_filter_params p, P
       cnt += k;
     }
   }
-  const int64_t t = block_sum(cnt, red);
+  const int64_t t = block_reduce<kThreads>(cnt, red, IntSum());
   if (threadIdx.x == 0) ws.counts[blockIdx.x] = t;
 }
 
 // exclusive scan of the per-workgroup counts in one workgroup of 1024 threads; the total is the cloud size
 __global__ __launch_bounds__(1024) void pf_scan(PfWs ws, int64_t nblk, int64_t* out_count) {
-  __shared__ uint64_t wsum[16];
-  __shared__ uint64_t carry;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t b0 = 0; b0 < nblk; b0 += 1024) {
-    const int64_t b = b0 + threadIdx.x;
-    const uint64_t v = b < nblk ? (uint64_t)ws.counts[b] : 0;
-    const uint64_t incl = wave_incl_scan(v);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t excl = carry + incl - v;
-    for (int w = 0; w < wave; ++w) excl += wsum[w];
-    if (b < nblk) ws.offsets[b] = (int64_t)excl;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = excl + v;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out_count = (int64_t)carry;
+  const int64_t total = count_scan(ws.counts, ws.offsets, nblk);
+  if (threadIdx.x == 0) *out_count = total;
 }
 
 // order-preserving scatter: entry i of the tile lands at offset[block] + (kept entries before it in the tile); the order inside a
@@ -375,8 +338,6 @@ VgWs vg_ws(const ovg_voxel_downsample_params* p) {
           {k, reinterpret_cast<int64_t*>(k + round256(p->n)), reinterpret_cast<int64_t*>(k + round256(p->n) + round256(nb * 8))}};
 }
 
-OVG_DEV bool finite_f32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
-
 __global__ __launch_bounds__(kThreads) void vg_init(VgWs ws, int64_t n) {
   const int64_t t0 = (int64_t)blockIdx.x * kThreads + threadIdx.x, step = (int64_t)gridDim.x * kThreads;
   u32x4* tab = reinterpret_cast<u32x4*>(ws.table);
@@ -393,7 +354,7 @@ __global__ __launch_bounds__(kThreads) void vg_origin(ovg_voxel_downsample_param
   uint32_t m[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * kThreads) {
     const float x = p.points[3 * i], y = p.points[3 * i + 1], z = p.points[3 * i + 2];
-    if (finite_f32(x) && finite_f32(y) && finite_f32(z)) {
+    if (finite3(x, y, z)) {
       m[0] = min(m[0], order_key(x));
       m[1] = min(m[1], order_key(y));
       m[2] = min(m[2], order_key(z));
@@ -401,7 +362,7 @@ __global__ __launch_bounds__(kThreads) void vg_origin(ovg_voxel_downsample_param
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    for (int d = 32; d > 0; d >>= 1) m[k] = min(m[k], (uint32_t)__shfl_down(m[k], d, 64));
+    m[k] = wave_reduce(m[k], IntMin());
     if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = m[k];
   }
   __syncthreads();
@@ -410,11 +371,6 @@ __global__ __launch_bounds__(kThreads) void vg_origin(ovg_voxel_downsample_param
     for (int w = 1; w < kThreads / 64; ++w) v = min(v, red[threadIdx.x][w]);
     if (v != 0xFFFFFFFFu) __hip_atomic_fetch_min(&ws.head->origin[threadIdx.x], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-}
-
-OVG_DEV uint64_t vg_mix(uint64_t h) {                // murmur3's 64-bit finaliser
-  h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
-  return h;
 }
 
 __global__ __launch_bounds__(kThreads) void vg_insert(ovg_voxel_downsample_params p, VgWs ws) {
@@ -426,7 +382,7 @@ __global__ __launch_bounds__(kThreads) void vg_insert(ovg_voxel_downsample_param
     return;
   }
   const float x = p.points[3 * i], y = p.points[3 * i + 1], z = p.points[3 * i + 2];
-  if (!(finite_f32(x) && finite_f32(y) && finite_f32(z))) return;
+  if (!finite3(x, y, z)) return;
   // np.floor((p - origin) / v) in float32: one subtraction, one correctly rounded division, a floor (p >= origin, so c >= 0)
   const float cx = floorf(__fdiv_rn(__fsub_rn(x, key_value(ws.head->origin[0])), v));
   const float cy = floorf(__fdiv_rn(__fsub_rn(y, key_value(ws.head->origin[1])), v));
@@ -444,7 +400,7 @@ __global__ __launch_bounds__(kThreads) void vg_insert(ovg_voxel_downsample_param
     if (c == c) ck = order_key(c + 0.0f);
   }
   const uint64_t word = ((uint64_t)ck << 32) | (uint32_t)~(uint32_t)i;                  // larger conf first, then the smaller index
-  int64_t s = (int64_t)__umul64hi(vg_mix(key), (uint64_t)ws.nslots);
+  int64_t s = (int64_t)__umul64hi(mix_murmur64(key), (uint64_t)ws.nslots);
   for (int64_t t = 0; t < ws.nslots; ++t) {          // at most n of the >= 2n slots are ever claimed: the walk ends at a free one
     VgSlot* slot = ws.table + s;
     uint64_t k = __hip_atomic_load(&slot->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -482,7 +438,7 @@ __global__ __launch_bounds__(kThreads) void vg_count(VgWs ws, int64_t n, int64_t
     const int64_t i = base + (int64_t)j * kThreads + threadIdx.x;
     if (i < n) cnt += ws.pf.keep[i];
   }
-  const int64_t t = block_sum(cnt, red);
+  const int64_t t = block_reduce<kThreads>(cnt, red, IntSum());
   if (threadIdx.x == 0) {
     ws.pf.counts[blockIdx.x] = t;
     if (blockIdx.x == 0) out_count[1] = (int64_t)ws.head->flags;
@@ -506,8 +462,6 @@ __global__ __launch_bounds__(kThreads) void vg_scatter(ovg_voxel_downsample_para
     if (p.out_index) p.out_index[pos] = i;
   });
 }
-
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 unsigned grid_for(int64_t work, int64_t per_block, int64_t cap) {
   const int64_t b = (work + per_block - 1) / per_block;

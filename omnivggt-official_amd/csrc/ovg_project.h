@@ -2,11 +2,9 @@
 // rules 1-3 of tests/render_twin.py, operation for operation in float32 with one rounding each. Units that include this are compiled
 // with -ffp-contract=off (build.py); the pragma below covers the functions of this header as well.
 #pragma once
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 #pragma clang fp contract(off)
-
-OVG_DEV bool finite_f32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
 
 // third row of the world-to-camera transform alone: zc = ((R20 x + R21 y) + R22 z) + tz
 OVG_DEV float camera_depth(const float* __restrict__ c, float x, float y, float z) { return ((c[6] * x + c[7] * y) + c[8] * z) + c[11]; }

@@ -7,7 +7,7 @@
 // the grid changes the cost and never a byte. The table is bound by random 64-bit atomics, the search by its gather of records.
 // ovg_knn_search and ovg_cluster (connected components / DBSCAN: a lock-free union-find over the neighbour pairs) walk the same grid.
 #include <math.h>
-#include "ovg_common.h"
+#include "ovg_geom.h"
 
 // tests/radius_twin.py restates the rule and the cell function in numpy float32, one rounding per operation: no fused multiply-adds
 // in this unit (build.py compiles it with -ffp-contract=off as well)
@@ -31,8 +31,7 @@ struct RsWs { RsHead* head; RsSlot* table; int64_t nslots; u32x4* rec; uint32_t*
 
 static_assert(sizeof(RsSlot) == 16 && sizeof(RsHead) <= 256, "workspace layout");
 
-bool rs_shape_ok(int64_t nq, int64_t nr) { return nq > 0 && nr > 0 && nq < (1ll << 31) && nr < (1ll << 31); }
-int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
+bool rs_shape_ok(int64_t nq, int64_t nr) { return size_ok(nq) && size_ok(nr); }
 int64_t rs_slots(int64_t nr) { return 2 * nr < OVG_RS_MIN_SLOTS ? OVG_RS_MIN_SLOTS : 2 * nr; }   // load factor <= 1/2
 int64_t rs_tiles(int64_t nr) { return (rs_slots(nr) + kScanTile - 1) / kScanTile; }
 int64_t rs_ws_bytes(int64_t nr) { return 256 + round256(rs_slots(nr) * 16) + round256(nr * 16) + round256(rs_tiles(nr) * 4); }
@@ -51,12 +50,9 @@ float rs_reach(float radius_sq) {
   return (double)r > v ? r : nextafterf(r, INFINITY);
 }
 
-OVG_DEV bool finite1(float f) { return (__float_as_uint(f) & kInfBits) != kInfBits; }
-OVG_DEV bool finite3(float x, float y, float z) { return finite1(x) && finite1(y) && finite1(z); }
-
 OVG_DEV float rs_origin(const float* origin, int k) {
   const float o = origin ? origin[k] : 0.0f;
-  return finite1(o) ? o : 0.0f;
+  return finite_f32(o) ? o : 0.0f;
 }
 
 // C(x) of the header, shifted to [0, 2^21): monotone in x. With a finite origin and cell no NaN arises (x is finite or +-inf)
@@ -68,12 +64,7 @@ OVG_DEV uint32_t rs_cell(float x, float o, float cell) {
 
 OVG_DEV uint64_t rs_key(uint32_t cx, uint32_t cy, uint32_t cz) { return ((uint64_t)cx << 42) | ((uint64_t)cy << 21) | (uint64_t)cz; }
 
-OVG_DEV uint64_t rs_mix(uint64_t h) {                  // murmur3's 64-bit finaliser
-  h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
-  return h;
-}
-
-OVG_DEV int64_t rs_home(const RsWs& ws, uint64_t key) { return (int64_t)__umul64hi(rs_mix(key), (uint64_t)ws.nslots); }
+OVG_DEV int64_t rs_home(const RsWs& ws, uint64_t key) { return (int64_t)__umul64hi(mix_murmur64(key), (uint64_t)ws.nslots); }
 
 // the slot of a cell in a table that no launch is writing keys to: -1 when the cell holds no reference
 OVG_DEV int64_t rs_find(const RsWs& ws, uint64_t key, uint32_t& count, uint32_t& end) {
@@ -107,16 +98,6 @@ OVG_DEV bool rs_point(const float* pts, const uint8_t* valid, uint32_t i, float 
   const float* p = pts + 3 * (int64_t)i;
   v[0] = p[0], v[1] = p[1], v[2] = p[2];
   return finite3(v[0], v[1], v[2]) && (!valid || valid[i] != 0);
-}
-
-OVG_DEV uint32_t wave_incl_scan_u32(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
 }
 
 __global__ __launch_bounds__(kThreads) void rs_clear(RsWs ws) {
@@ -163,10 +144,7 @@ __global__ __launch_bounds__(kThreads) void rs_tile_sums(RsWs ws) {
     const uint32_t c = s < ws.nslots ? ws.table[s].count : 0u;
     sum += c, occ += c != 0, mx = max(mx, c);
   }
-  for (int d = 32; d > 0; d >>= 1) {
-    sum += __shfl_down(sum, d, 64), occ += __shfl_down(occ, d, 64);
-    mx = max(mx, (uint32_t)__shfl_down(mx, d, 64));
-  }
+  sum = wave_reduce(sum, IntSum()), occ = wave_reduce(occ, IntSum()), mx = wave_reduce(mx, IntMax());
   if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = sum, red[1][threadIdx.x >> 6] = occ, red[2][threadIdx.x >> 6] = mx;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -181,24 +159,7 @@ __global__ __launch_bounds__(kThreads) void rs_tile_sums(RsWs ws) {
 
 // exclusive scan of the tile sums in place, one workgroup of 1024 threads (the total is below 2^31)
 __global__ __launch_bounds__(1024) void rs_scan_tiles(RsWs ws) {
-  __shared__ uint32_t wsum[16];
-  __shared__ uint32_t carry;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t b0 = 0; b0 < ws.ntiles; b0 += 1024) {
-    const int64_t b = b0 + threadIdx.x;
-    const uint32_t v = b < ws.ntiles ? ws.tile[b] : 0u;
-    const uint32_t incl = wave_incl_scan_u32(v);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t excl = carry + incl - v;
-    for (int w = 0; w < wave; ++w) excl += wsum[w];
-    if (b < ws.ntiles) ws.tile[b] = excl;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = excl + v;
-    __syncthreads();
-  }
+  count_scan(ws.tile, ws.tile, ws.ntiles);
 }
 
 __global__ __launch_bounds__(kThreads) void rs_starts(RsWs ws) {
@@ -212,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void rs_starts(RsWs ws) {
     c[k] = s < ws.nslots ? ws.table[s].count : 0u;
     sum += c[k];
   }
-  const uint32_t incl = wave_incl_scan_u32(sum);
+  const uint32_t incl = wave_incl_scan(sum);
   if (lane == 63) wsum[wave] = incl;
   __syncthreads();
   uint32_t run = ws.tile[blockIdx.x] + incl - sum;
@@ -255,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void rs_cost(ovg_radius_params p, RsWs ws
           if (rs_find(ws, rs_key(cx, cy, cz), count, end) >= 0) sum += count;
         }
   }
-  for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+  sum = wave_reduce(sum, IntSum());
   if ((threadIdx.x & 63) == 0 && sum) __hip_atomic_fetch_add(&ws.head->pairs, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -539,8 +500,6 @@ __global__ void cl_done(ovg_radius_params p, RsWs ws) {
   p.out_stats[2] = no == OVG_RS_NOT_BUILT ? 0 : (int64_t)h.max_cell;
   p.out_stats[3] = no == OVG_RS_NOT_BUILT ? 0 : (int64_t)h.pairs;
 }
-
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 unsigned grid_for(int64_t work, int64_t per_block, int64_t cap) {
   const int64_t b = (work + per_block - 1) / per_block;

@@ -3,6 +3,7 @@
 // atomic min per covered pixel), resolve (the winning face again through the same functions, then colour / normal / shade).
 // tests/raster_twin.py restates every step in numpy; no fused multiply-adds in this unit (the pragma below and -ffp-contract=off in
 // build.py). The point renderer (ovg_render.hip) is not touched: the fill kernel is repeated here.
+#include "ovg_geom.h"
 #include "ovg_project.h"
 
 #pragma clang fp contract(off)
@@ -149,7 +150,6 @@ __global__ __launch_bounds__(kThreads) void rs_draw(const float* __restrict__ ve
 }
 
 OVG_DEV uint8_t rs_u8(double x) { return !(x >= 0.0) ? 0 : x > 255.0 ? 255 : (uint8_t)x; }
-OVG_DEV bool finite_f64(double d) { return (__double_as_longlong(d) & 0x7FF0000000000000ll) != 0x7FF0000000000000ll; }
 
 // rule 6: one thread per pixel
 __global__ __launch_bounds__(kThreads) void rs_resolve(const uint64_t* __restrict__ zbuf, const float* __restrict__ vertices,
@@ -211,8 +211,6 @@ __global__ __launch_bounds__(kThreads) void rs_resolve(const uint64_t* __restric
   if (depth) depth[q] = hit ? __uint_as_float((uint32_t)(key >> 32)) : 0.0f;
   if (index) index[q] = hit ? (int64_t)f : -1;
 }
-
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 }  // namespace
 

@@ -1,6 +1,7 @@
 // Point-cloud rendering (ovg_render_points): z-buffered square splats of a coloured cloud into V pinhole views, the headless stand-in
 // for the reference's interactive viewer (inference.py: viser_wrapper). Three launches: fill the u64 z-buffer with ~0, splat (one
 // 64-bit unsigned atomic min per covered pixel), resolve to rgb / depth / index. The splat is bound by its atomics, not by arithmetic.
+#include "ovg_geom.h"
 #include "ovg_project.h"
 
 // the projection (ovg_project.h, shared with ovg_consistency.hip) restates tests/render_twin.py's numpy float32 expression operation
@@ -72,8 +73,6 @@ __global__ __launch_bounds__(kThreads) void rd_resolve(const uint64_t* __restric
   if (depth) depth[q] = hit ? __uint_as_float((uint32_t)(key >> 32)) : 0.0f;
   if (index) index[q] = hit ? (int64_t)i : -1;
 }
-
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 
 }  // namespace
 

@@ -3,6 +3,7 @@
 // lattice point, the views in a loop, the shared projection of ovg_project.h and one gathered 4-byte depth read per (point, view);
 // the state of a point lives in registers across the loop. No atomics anywhere: fixed view order per point, counts and scans for the
 // mesh, so two runs give identical bytes.
+#include "ovg_geom.h"
 #include "ovg_project.h"
 
 // tests/tsdf_twin.py restates both rules in numpy float32, one rounding per operation: no fused multiply-adds in this unit
@@ -17,7 +18,6 @@ static_assert(kThreads == OVG_TSDF_EXTRACT_BLOCK, "one lattice point per thread 
 OVG_DEV float min_lt(float a, float b) { return a < b ? a : b; }          // the twin's fmin: NaN in a gives b, NaN in b gives b
 bool pos_finite(float v) { return v > 0.0f && v <= 3.402823466e38f; }
 bool finite_host(float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }
-bool al(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; }
 bool dims_ok(int32_t nx, int32_t ny, int32_t nz) {
   // each factor < 2^31: the first product is below 2^62, and it is below 2^31 before the second one is formed
   return nx > 0 && ny > 0 && nz > 0 && (int64_t)nx * ny < (1ll << 31) && (int64_t)nx * ny * nz < (1ll << 31);
@@ -102,7 +102,6 @@ struct ExWs {
   int64_t* qoff;        // [blocks]: quads per workgroup, then their exclusive scan
 };
 
-int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
 int64_t ex_blocks(int64_t n) { return (n + kThreads - 1) / kThreads; }
 int64_t ex_ws_bytes(int64_t n) { return round256(4 * n) + round256(n) + 2 * round256(8 * ex_blocks(n)); }
 ExWs ex_ws(void* ws, int64_t n) {
@@ -129,32 +128,6 @@ OVG_DEV Lattice lattice_of(const ovg_tsdf_extract_params& p, int64_t n) {
   return l;
 }
 
-OVG_DEV uint32_t wave_incl_scan_u32(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// exclusive rank of this thread's `c` items among the workgroup's, in thread order; total: the workgroup's sum. Every thread calls it.
-OVG_DEV uint32_t block_excl_scan(uint32_t c, uint32_t* wsum, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t incl = wave_incl_scan_u32(c);
-  __syncthreads();                                                        // wsum may still be read from an earlier call
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-  for (int w = 0; w < kThreads / 64; ++w) {
-    if (w < wave) before += wsum[w];
-    total += wsum[w];
-  }
-  return before + incl - c;
-}
-
 // the active cells: vidx = 0 / -1 per lattice point, vertices per workgroup
 __global__ __launch_bounds__(kThreads) void ex_cells(ovg_tsdf_extract_params p, ExWs ws, int64_t n) {
   __shared__ uint32_t wsum[kThreads / 64];
@@ -174,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void ex_cells(ovg_tsdf_extract_params p, 
   }
   if (l.in) ws.vidx[l.g] = active ? 0 : -1;
   uint32_t total;
-  block_excl_scan(active, wsum, total);
+  block_excl_scan<kThreads>(active, wsum, total);
   if (threadIdx.x == 0) ws.voff[blockIdx.x] = total;
 }
 
@@ -200,44 +173,17 @@ __global__ __launch_bounds__(kThreads) void ex_quads(ovg_tsdf_extract_params p, 
     ws.qmask[l.g] = (uint8_t)mask;
   }
   uint32_t total;
-  block_excl_scan(__popc(mask), wsum, total);
+  block_excl_scan<kThreads>(__popc(mask), wsum, total);
   if (threadIdx.x == 0) ws.qoff[blockIdx.x] = total;
-}
-
-OVG_DEV uint64_t wave_incl_scan_u64(uint64_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
 }
 
 // exclusive scans of the two per-workgroup count arrays in place, one workgroup of 1024 threads; the totals are the mesh sizes
 __global__ __launch_bounds__(1024) void ex_scan(ExWs ws, int64_t nblk, int64_t* out_count) {
-  __shared__ uint64_t wsum[16];
-  __shared__ uint64_t carry;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int which = 0; which < 2; ++which) {
     int64_t* counts = which ? ws.qoff : ws.voff;
-    __syncthreads();
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < nblk; b0 += 1024) {
-      const int64_t b = b0 + threadIdx.x;
-      const uint64_t v = b < nblk ? (uint64_t)counts[b] : 0;
-      const uint64_t incl = wave_incl_scan_u64(v);
-      if (lane == 63) wsum[wave] = incl;
-      __syncthreads();
-      uint64_t excl = carry + incl - v;
-      for (int w = 0; w < wave; ++w) excl += wsum[w];
-      if (b < nblk) counts[b] = (int64_t)excl;
-      __syncthreads();
-      if (threadIdx.x == 1023) carry = excl + v;
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out_count[which] = (int64_t)carry;
+    __syncthreads();                                                      // the two scans share their LDS
+    const int64_t total = count_scan(counts, counts, nblk);
+    if (threadIdx.x == 0) out_count[which] = total;
   }
 }
 
@@ -248,7 +194,7 @@ __global__ __launch_bounds__(kThreads) void ex_vertices(ovg_tsdf_extract_params 
   // the position tests repeat ex_cells': a workspace that COUNT did not fill must not send a read or a write out of bounds
   const bool active = l.in && l.i < p.nx - 1 && l.j < p.ny - 1 && l.k < p.nz - 1 && ws.vidx[l.g] >= 0;
   uint32_t total;
-  const uint32_t rank = block_excl_scan(active, wsum, total);
+  const uint32_t rank = block_excl_scan<kThreads>(active, wsum, total);
   if (!active) return;
   const int64_t pos = ws.voff[blockIdx.x] + rank;                         // <= the number of cells < 2^31
   ws.vidx[l.g] = (int32_t)pos;
@@ -317,7 +263,7 @@ __global__ __launch_bounds__(kThreads) void ex_faces(ovg_tsdf_extract_params p, 
     if (!(at[a] <= dims[a] - 2 && at[b] >= 1 && at[b] <= dims[b] - 2 && at[c] >= 1 && at[c] <= dims[c] - 2)) mask &= ~(1u << a);
   }
   uint32_t total;
-  const uint32_t rank = block_excl_scan(__popc(mask), wsum, total);
+  const uint32_t rank = block_excl_scan<kThreads>(__popc(mask), wsum, total);
   if (!mask) return;
   int64_t pos = ws.qoff[blockIdx.x] + rank;
   if (pos < 0) return;

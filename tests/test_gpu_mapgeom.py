@@ -216,6 +216,26 @@ def test_scan_second_level_empty_maps_and_capacities():
     assert bool((flags == L.MAP_UNUSABLE).all())
 
 
+def test_scan_carries_past_1024_workgroups():
+    """The count scan is one workgroup of 1024 threads: from 1025 counts on it loops and carries the running total. The smallest such
+    map: one view of two rows, 1024 * MAP_BLOCK + 2 pixels, so the last workgroup holds the last two pixels and its offsets are the carry."""
+    W = 1024 * L.MAP_BLOCK // 2 + 1
+    pts_h, keep_h = scenes.random_keep_scene(S=1, H=2, W=W, seed=11)
+    n = keep_h.size
+    assert -(-n // L.MAP_BLOCK) == 1025
+    keep_h[:, :, -2:] = 1                                                      # the last quad is emitted: vertices in the last workgroup
+    want_z = twin.map_depth(depth=pts_h[..., 2])
+    want = twin.triangulate(want_z, pts_h, keep_h, None, None, 0.03)
+    assert want["pixel_index"][-1] == n - 1 and want["pixel_index"][-2] == n - 2
+    pts, keep = _dev(pts_h), _dev(keep_h)
+    z = _depth(depth=_dev(np.ascontiguousarray(pts_h[..., 2])))
+    _same(z, want_z, "z")
+    for rep in range(2):
+        M, Fc, got = _mesh(z, pts, 0.03, keep)
+        assert (M, Fc) == (len(want["vertices"]), len(want["faces"])) and M > 100000 and Fc > 50000
+        _same_mesh(got, want, "carry")
+
+
 # ---------------------------------------------------------------------------------------------
 # winding and orientation
 # ---------------------------------------------------------------------------------------------
