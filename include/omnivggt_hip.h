@@ -76,7 +76,9 @@ extern "C" {
  *       ovg_deptheval_sums, ovg_deptheval_solve, ovg_deptheval_median_workspace_bytes, ovg_deptheval_sums_workspace_bytes): added the
  *       same way
  *     + image-space map geometry: usable depth, normals, edge flags and the grid mesh of the prediction maps (ovg_map_depth,
- *       ovg_map_normals, ovg_map_edges, ovg_map_triangulate, ovg_map_triangulate_workspace_bytes): added the same way */
+ *       ovg_map_normals, ovg_map_edges, ovg_map_triangulate, ovg_map_triangulate_workspace_bytes): added the same way
+ *     + mesh simplification by vertex clustering on the grid of ovg_voxel_downsample, duplicate faces merged (ovg_mesh_simplify,
+ *       ovg_mesh_simplify_workspace_bytes): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -1548,6 +1550,68 @@ typedef struct {
 } ovg_map_triangulate_params;
 int64_t ovg_map_triangulate_workspace_bytes(int32_t S, int32_t H, int32_t W);
 int ovg_map_triangulate(const ovg_map_triangulate_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Mesh simplification (added under ABI 13): vertex clustering on a uniform grid (Rossignac-Borrel) with degenerate and duplicate faces
+ * removed, by an exact rule that names no schedule and that tests/meshsimp_twin.py restates in numpy bit for bit.
+ *   vertices [M][3] f32, faces [F][3] int32, normals [M][3] f32 (optional), colors [M][3] u8 (optional); voxel: DEVICE f32 scalar,
+ *   the cell edge v. 1 <= M < 2^31, 1 <= F < 2^32 - 1.
+ *   1. a vertex is VALID when its three coordinates are finite;
+ *   2. the grid is the one of ovg_voxel_downsample: origin = component-wise minimum of the valid vertices; per axis g = (p - origin) / v
+ *      in f32 (one subtraction, one correctly rounded division) and the cell c = floor(g). A valid vertex with any c > 2^21 - 1 raises
+ *      OVG_MS_OVERFLOW, a v that is not a positive finite number OVG_MS_BAD_VOXEL; a call that raised either keeps nothing;
+ *   3. the LEADER of a cell is its lowest valid vertex index;
+ *   4. a face is LIVE when its three indices lie in [0, M) and its three vertices are valid; a live face whose three cells are not
+ *      pairwise different is dropped as DEGENERATE;
+ *   5. two live, non-degenerate faces with the same unordered set of three cells are DUPLICATES: the lowest input face index survives
+ *      and keeps its own corner order (an opposite-facing copy disappears too);
+ *   6. one output vertex per cell that a surviving face names, in ascending leader index; cells of unreferenced or all-degenerate
+ *      geometry produce nothing;
+ *   7. the output faces are the survivors in input order, int32, corners mapped to output vertex numbers;
+ *   8. position OVG_MS_POS_FIRST: the leader's own twelve bytes;
+ *   9. position OVG_MS_POS_MEAN: per valid vertex and axis r = g - c in f32 (exact, in [0, 1)), q = llrint((double)r * 2^24) (to
+ *      nearest, ties to even), Q = sum of q over the cell (int64), n = the cell's valid vertices; the output coordinate is
+ *      (float)((double)origin + (double)v * ((double)c + (double)Q / ((double)n * 16777216.0))), every operation rounded on its own, in
+ *      that order, in float64: a mean that does not depend on the order of the vertices;
+ *  10. colours: per channel (2 S + n) / (2 n) in integers, S the channel's sum over the cell: the mean rounded half up;
+ *  11. normals: a vertex's normal takes part when its three components are finite and each has magnitude <= 4; per component the sum
+ *      of llrint((double)x * 2^20) in int64; the output is that integer vector (nx, ny, nz) as float64 divided by
+ *      l = sqrt((nx nx + ny ny) + nz nz) (the order of ovg_map_normals) and rounded to f32 when l is finite and > 0, else (0, 0, 0);
+ *  12. out_source_index [M'] int64 is the leader's input index, out_vertex_count [M'] int32 the cell's n (both optional).
+ *   stage OVG_MS_COUNT: both tables, the sums, the keep bytes, the ranks and the scans into ws; out_count[0..5] = M', F', the OVG_MS_*
+ *   flags raised, the occupied cells, the degenerate faces, the duplicate faces that were dropped (six int64, device; the last three
+ *   are 0 in a flagged call). stage OVG_MS_SCATTER reads what COUNT left in ws and writes the first vertex_capacity vertices
+ *   (out_vertices, with normals out_normals, with colors out_colors -- each output required exactly when its input is given --,
+ *   out_source_index, out_vertex_count) and the first face_capacity faces (out_faces; a face may then name a dropped vertex).
+ *   Cell table: open addressing, linear probing, max(1024, 2 M) slots; the 63-bit cell key is claimed by a 64-bit compare-and-swap;
+ *   leader (32-bit min), n and the nine integer sums live in arrays indexed by the slot, every vertex stores its slot once. Face
+ *   table: max(1024, 2 F) slots of one 32-bit face index; a prober compares its sorted triple of cell slots with the triple of the
+ *   face the slot names and issues one 32-bit min of its own index when they agree. Integer atomics only (relaxed, agent scope): no
+ *   result depends on arrival order, two runs give identical bytes. Nothing is allocated, nothing is read back, every launch goes to
+ *   the caller's stream.
+ *   ws: >= ovg_mesh_simplify_workspace_bytes(M, F) bytes, 16-byte aligned: with C = max(1024, 2 M), T = max(1024, 2 F), tv =
+ *   ceil(M / 4096), tf = ceil(F / 4096) the parts 256, 8 C, 4 C, 4 C, 4 C, 72 C, 4 M, M, 4 T, F, 8 tv, 8 tv, 8 tf, 8 tf, each rounded
+ *   up to 256. The query returns -1 for M <= 0, F <= 0, M >= 2^31 or F >= 2^32 - 1.
+ *   OVG_E_ARG before the first HIP call: NULL params / vertices / faces / voxel / ws, sizes outside the limits, an unknown stage or
+ *   position, COUNT without out_count, in SCATTER a negative capacity, a NULL out_vertices (vertex_capacity > 0) or out_faces
+ *   (face_capacity > 0), out_normals / out_colors not matching normals / colors, a pointer that is not aligned to its element, a
+ *   misaligned or undersized workspace.
+ *   Not in it: quadric placement, edge collapse, smoothing, a guarantee of manifoldness (clustering can pinch a surface).
+ * ------------------------------------------------------------------ */
+enum { OVG_MS_COUNT = 1, OVG_MS_SCATTER = 2 };
+enum { OVG_MS_OVERFLOW = 1, OVG_MS_BAD_VOXEL = 2 };
+enum { OVG_MS_POS_MEAN = 0, OVG_MS_POS_FIRST = 1 };
+typedef struct {
+  const float* vertices; const int32_t* faces; const float* normals; const uint8_t* colors; const float* voxel;
+  int64_t num_vertices; int64_t num_faces;
+  int32_t stage; int32_t position;
+  int64_t vertex_capacity; int64_t face_capacity;
+  float* out_vertices; float* out_normals; uint8_t* out_colors; int64_t* out_source_index; int32_t* out_vertex_count;
+  int32_t* out_faces; int64_t* out_count;
+  void* ws; int64_t ws_bytes;
+} ovg_mesh_simplify_params;
+int64_t ovg_mesh_simplify_workspace_bytes(int64_t vertices, int64_t faces);
+int ovg_mesh_simplify(const ovg_mesh_simplify_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

@@ -414,6 +414,18 @@ class MapTriangulateParams(C.Structure):
                 ("ws_bytes", i64)]
 
 
+MS_COUNT, MS_SCATTER = 1, 2                                  # ovg_mesh_simplify_params.stage
+MS_OVERFLOW, MS_BAD_VOXEL = 1, 2                             # flags in out_count[2]
+MS_POS_MEAN, MS_POS_FIRST = 0, 1                             # ovg_mesh_simplify_params.position
+
+
+class MeshSimplifyParams(C.Structure):
+    _fields_ = [("vertices", vp), ("faces", vp), ("normals", vp), ("colors", vp), ("voxel", vp), ("num_vertices", i64), ("num_faces", i64),
+                ("stage", i32), ("position", i32), ("vertex_capacity", i64), ("face_capacity", i64), ("out_vertices", vp),
+                ("out_normals", vp), ("out_colors", vp), ("out_source_index", vp), ("out_vertex_count", vp), ("out_faces", vp),
+                ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -518,6 +530,8 @@ SYMBOLS = {
     "ovg_map_edges": (i32, [C.POINTER(MapEdgesParams), vp]),
     "ovg_map_triangulate": (i32, [C.POINTER(MapTriangulateParams), vp]),
     "ovg_map_triangulate_workspace_bytes": (i64, [i32, i32, i32]),
+    "ovg_mesh_simplify": (i32, [C.POINTER(MeshSimplifyParams), vp]),
+    "ovg_mesh_simplify_workspace_bytes": (i64, [i64, i64]),
 }
 
 

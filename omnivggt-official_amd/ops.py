@@ -1730,3 +1730,69 @@ def map_triangulate(stage, z, points, ws, rel_tol=0.03, keep=None, normals=None,
     p.out_pixel_index, p.out_faces, p.out_count = L.ptr(pixel_index), L.ptr(faces), L.ptr(out_count)
     p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
     L.call("ovg_map_triangulate", p, _stream())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# mesh simplification by vertex clustering (ovg_mesh_simplify)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def mesh_simplify_workspace_bytes(vertices, faces):
+    for v in (vertices, faces):
+        if not -(1 << 63) <= int(v) < (1 << 63):
+            raise L.OvgError("ovg_mesh_simplify_workspace_bytes: unsupported (vertices=%d, faces=%d)" % (vertices, faces))
+    b = L.load().ovg_mesh_simplify_workspace_bytes(int(vertices), int(faces))
+    if b < 0:
+        raise L.OvgError("ovg_mesh_simplify_workspace_bytes: unsupported (vertices=%d, faces=%d)" % (vertices, faces))
+    return int(b)
+
+
+def mesh_simplify(stage, vertices, faces, voxel, ws, normals=None, colors=None, position=L.MS_POS_MEAN, out_count=None, vertex_capacity=0,
+                  face_capacity=0, out_vertices=None, out_normals=None, out_colors=None, source_index=None, vertex_count=None, out_faces=None):
+    """ovg_mesh_simplify on contiguous device tensors: vertices f32 [M, 3], faces int32 [F, 3], voxel a 0-d / 1-element f32 device
+    tensor, normals f32 [M, 3] and colors u8 [M, 3] or None; ws a uint8 tensor of at least mesh_simplify_workspace_bytes(M, F) bytes.
+    stage L.MS_COUNT writes (M', F', flags, cells, degenerate, duplicates) to the six int64 of out_count; L.MS_SCATTER writes the
+    first vertex_capacity vertices to out_vertices f32 [., 3] (out_normals f32 [., 3] / out_colors u8 [., 3] exactly when normals /
+    colors are given; source_index int64 [.] and vertex_count int32 [.] optional) and the first face_capacity faces to out_faces int32
+    [., 3] from what the COUNT stage left in ws. position: L.MS_POS_MEAN or L.MS_POS_FIRST."""
+    what = "mesh_simplify"
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or not 1 <= vertices.shape[0] < 1 << 31:
+        raise L.OvgError("%s: vertices must be a tensor [M, 3], 1 <= M < 2^31" % what)
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or not 1 <= faces.shape[0] < (1 << 32) - 1:
+        raise L.OvgError("%s: faces must be a tensor [F, 3], 1 <= F < 2^32 - 1" % what)
+    M, F = int(vertices.shape[0]), int(faces.shape[0])
+    _map_tensor(what, vertices, "vertices", torch.float32, (M, 3))
+    _map_tensor(what, faces, "faces", torch.int32, (F, 3))
+    _map_tensor(what, normals, "normals", torch.float32, (M, 3), True)
+    _map_tensor(what, colors, "colors", torch.uint8, (M, 3), True)
+    if not isinstance(voxel, torch.Tensor) or voxel.dtype != torch.float32 or voxel.numel() != 1 or not voxel.is_contiguous():
+        raise L.OvgError("%s: voxel must be a contiguous f32 tensor of one element" % what)
+    if stage not in (L.MS_COUNT, L.MS_SCATTER, L.MS_COUNT | L.MS_SCATTER):
+        raise L.OvgError("%s: unknown stage %r" % (what, stage))
+    if position not in (L.MS_POS_MEAN, L.MS_POS_FIRST):
+        raise L.OvgError("%s: unknown position %r" % (what, position))
+    for name, v in (("vertex_capacity", vertex_capacity), ("face_capacity", face_capacity)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 62:
+            raise L.OvgError("%s: %s must be a non-negative integer, got %r" % (what, name, v))
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    if stage & L.MS_SCATTER:
+        if vertex_capacity and ((normals is None) != (out_normals is None) or (colors is None) != (out_colors is None)):
+            raise L.OvgError("%s: out_normals / out_colors go with normals / colors" % what)
+        outs = ((out_vertices, torch.float32, 3 * vertex_capacity, True), (out_normals, torch.float32, 3 * vertex_capacity, False),
+                (out_colors, torch.uint8, 3 * vertex_capacity, False), (source_index, torch.int64, vertex_capacity, False),
+                (vertex_count, torch.int32, vertex_capacity, False), (out_faces, torch.int32, 3 * face_capacity, True))
+        for t, dt, need, required in outs:
+            if need and (t is not None or required) and \
+                    (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < need):
+                raise L.OvgError("%s: output buffers must be contiguous and hold the capacities" % what)
+    if (stage & L.MS_COUNT or out_count is not None) and \
+            (not isinstance(out_count, torch.Tensor) or out_count.dtype != torch.int64 or out_count.numel() < 6 or not out_count.is_contiguous()):
+        raise L.OvgError("%s: out_count must be a contiguous int64 device tensor of six elements" % what)
+    _chk_dev(vertices, faces, voxel, ws, normals, colors, out_count, out_vertices, out_normals, out_colors, source_index, vertex_count, out_faces)
+    p = L.MeshSimplifyParams()
+    p.vertices, p.faces, p.normals, p.colors, p.voxel = L.ptr(vertices), L.ptr(faces), L.ptr(normals), L.ptr(colors), L.ptr(voxel)
+    p.num_vertices, p.num_faces, p.stage, p.position = M, F, int(stage), int(position)
+    p.vertex_capacity, p.face_capacity = vertex_capacity, face_capacity
+    p.out_vertices, p.out_normals, p.out_colors = L.ptr(out_vertices), L.ptr(out_normals), L.ptr(out_colors)
+    p.out_source_index, p.out_vertex_count, p.out_faces = L.ptr(source_index), L.ptr(vertex_count), L.ptr(out_faces)
+    p.out_count, p.ws, p.ws_bytes = L.ptr(out_count), L.ptr(ws), nbytes(ws)
+    L.call("ovg_mesh_simplify", p, _stream())

@@ -2955,3 +2955,121 @@ def predictions_to_mesh(predictions, conf_thres=50.0, filter_by_frames="all", pr
         keep = keep & ((flags & ops.L.MAP_DEPTH_EDGE) == 0)
     normals = ops.map_normals(pts, z, rel_tol=tol32) if with_normals else None
     return _triangulate(what, pts, z, keep.to(torch.uint8), _tsdf_colors(img.float(), S, H, W), normals, tol32, extrinsic, conf_threshold)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Mesh simplification: vertex clustering on the grid of voxel_downsample, duplicate faces merged (ovg_mesh_simplify)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class SimplifiedMesh(Mesh):
+    """A Mesh from simplify_mesh: additionally source_index (M',) int64, the input index of every output vertex's leader (the lowest
+    valid vertex of its cell); vertex_count (M',) int32, the valid input vertices of that cell; pixel_index (M',) int64 =
+    mesh.pixel_index[source_index] when the input was a MapMesh, else None; and the host integers cells (occupied cells),
+    degenerate_faces and duplicate_faces (faces dropped by either rule)."""
+    __slots__ = ("source_index", "vertex_count", "pixel_index", "cells", "degenerate_faces", "duplicate_faces")
+
+    def __init__(self, vertices, faces, normals, colors, transform, extrinsic=None, scene_scale=None, source_index=None, vertex_count=None,
+                 pixel_index=None, cells=0, degenerate_faces=0, duplicate_faces=0):
+        Mesh.__init__(self, vertices, faces, normals, colors, transform, extrinsic, scene_scale)
+        self.source_index, self.vertex_count, self.pixel_index = source_index, vertex_count, pixel_index
+        self.cells, self.degenerate_faces, self.duplicate_faces = cells, degenerate_faces, duplicate_faces
+
+
+MESH_POSITIONS = {"mean": 0, "first": 1}
+
+
+def simplify_mesh(mesh, voxel_size=None, rel_size=None, position="mean"):
+    """Vertex clustering of a Mesh on the device (ovg_mesh_simplify): the vertices that share a cell of a regular grid become one, the
+    faces that collapse disappear. The first reducer to reach for when a mesh is too large to write or view; linear and order-free.
+
+    Exactly one of voxel_size (the cell edge in the mesh's units: a positive float or a 0-d f32 device tensor) and rel_size (a positive
+    float; the edge is f32(rel_size) * mesh.scene_scale, one f32 multiply on the device) must be given, as for voxel_downsample, whose
+    grid this is: vertices with a non-finite coordinate are dropped, the grid starts at the component-wise minimum of the others, cell
+    = floor((p - origin) / edge) in f32. The rule is exact (tests/meshsimp_twin.py restates it): a face with an index outside the
+    mesh or an invalid vertex is dropped; a face whose three cells are not pairwise different is dropped as degenerate; of the faces
+    with the same unordered set of three cells the lowest input index survives with its own winding (a back-to-back copy goes too:
+    render_mesh draws both sides by default). One output vertex per cell a surviving face names, in the order of the cells' lowest
+    vertex index; faces in input order. position "mean": the order-free integer mean of the cell's vertices; "first": the lowest
+    vertex of the cell as it is. Colours are the channel means rounded half up, normals the normalised integer sum of the cell's
+    usable normals ((0, 0, 0) when they cancel); a mesh without normals / colours gives a mesh without. Two calls give identical bytes.
+
+    -> SimplifiedMesh: transform, extrinsic and scene_scale passed through unchanged, so write_mesh_ply, write_mesh_glb, render_mesh
+    and mesh_to_point_cloud take it as it is; source_index, vertex_count, pixel_index (for a MapMesh) and the three host counts.
+    Not in it: quadric placement, edge collapse, smoothing, a guarantee of manifoldness (clustering can pinch a surface).
+
+    Exactly one device -> host synchronisation (the six counts in one copy). A grid of more than 2^21 cells along an axis, or an edge
+    that is not positive on the device, raises ValueError, as does rel_size on a mesh without scene_scale. A mesh without vertices or
+    without faces returns an empty mesh without a launch. CPU tensors raise OvgError: there is no CPU fallback."""
+    import math
+    L = ops.L
+    what = "simplify_mesh"
+    if not isinstance(mesh, Mesh):
+        raise ValueError("%s: expected a Mesh" % what)
+    if (voxel_size is None) == (rel_size is None):
+        raise ValueError("%s: give exactly one of voxel_size and rel_size" % what)
+    if not isinstance(position, str) or position not in MESH_POSITIONS:
+        raise ValueError("%s: position must be one of %r, got %r" % (what, sorted(MESH_POSITIONS), position))
+    given = voxel_size if rel_size is None else rel_size
+    if isinstance(given, torch.Tensor):
+        if rel_size is not None or given.numel() != 1:
+            raise ValueError("%s: rel_size must be a float, voxel_size a float or a one-element tensor" % what)
+    else:
+        given = float(given)
+        if not (given > 0.0 and math.isfinite(given)):
+            raise ValueError("%s: the size must be positive and finite, got %r" % (what, given))
+    if rel_size is not None and mesh.scene_scale is None:
+        raise ValueError("%s: rel_size needs a mesh with scene_scale" % what)
+    vert, faces, nrm, col = mesh.vertices, mesh.faces, mesh.normals, mesh.colors
+    if vert is None or faces is None:
+        raise ValueError("%s: the mesh has no vertices or no faces tensor" % what)
+    pix = getattr(mesh, "pixel_index", None)
+    for t in (vert, faces, nrm, col, pix, given if isinstance(given, torch.Tensor) else None):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
+    M, F = int(vert.shape[0]), int(faces.shape[0])
+    if M >= 1 << 31 or F >= (1 << 32) - 1:
+        raise ValueError("%s: the mesh has 2^31 vertices or 2^32 - 1 faces or more" % what)
+    dev = vert.device
+
+    def result(v, f, n, c, src, cnt, cells=0, degenerate=0, duplicates=0):
+        return SimplifiedMesh(v, f, n, c, mesh.transform, mesh.extrinsic, mesh.scene_scale, src, cnt, None if pix is None else pix[src],
+                              cells, degenerate, duplicates)
+
+    def empty(cells=0, degenerate=0, duplicates=0):
+        return result(torch.empty(0, 3, device=dev, dtype=torch.float32), torch.empty(0, 3, device=dev, dtype=torch.int32),
+                      None if nrm is None else torch.empty(0, 3, device=dev, dtype=torch.float32),
+                      None if col is None else torch.empty(0, 3, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.int64),
+                      torch.empty(0, device=dev, dtype=torch.int32), cells, degenerate, duplicates)
+    if M == 0 or F == 0:
+        return empty()
+    vert = vert.reshape(M, 3).float().contiguous()
+    faces = faces.reshape(F, 3).to(torch.int32).contiguous()
+    nrm = None if nrm is None else nrm.reshape(M, 3).float().contiguous()
+    col = None if col is None else col.reshape(M, 3).to(torch.uint8).contiguous()
+    if isinstance(given, torch.Tensor):
+        voxel = given.detach().to(torch.float32).reshape(())
+    else:
+        voxel = torch.full((), given, device=dev, dtype=torch.float32)
+        if rel_size is not None:
+            voxel = voxel * mesh.scene_scale.to(device=dev, dtype=torch.float32).reshape(())
+    ws = torch.empty(ops.mesh_simplify_workspace_bytes(M, F), device=dev, dtype=torch.uint8)
+    count = torch.empty(6, device=dev, dtype=torch.int64)
+    args = dict(vertices=vert, faces=faces, voxel=voxel, ws=ws, normals=nrm, colors=col, position=MESH_POSITIONS[position], out_count=count)
+    ops.mesh_simplify(L.MS_COUNT, **args)
+    Mo, Fo, flags, cells, degenerate, duplicates = (int(v) for v in count.cpu().tolist())       # the one synchronisation
+    if flags:
+        ok = torch.isfinite(vert).all(dim=1)
+        extent = (vert[ok].max(dim=0).values - vert[ok].min(dim=0).values).tolist() if bool(ok.any()) else []
+        why = "is not a positive finite number" if flags & L.MS_BAD_VOXEL else "gives more than 2^21 cells along an axis"
+        raise ValueError("%s: voxel size %r %s (extent of the mesh %r)" % (what, float(voxel), why, extent))
+    if Mo == 0:
+        return empty(cells, degenerate, duplicates)
+    out_v = torch.empty(Mo, 3, device=dev, dtype=torch.float32)
+    out_n = None if nrm is None else torch.empty(Mo, 3, device=dev, dtype=torch.float32)
+    out_c = None if col is None else torch.empty(Mo, 3, device=dev, dtype=torch.uint8)
+    src = torch.empty(Mo, device=dev, dtype=torch.int64)
+    cnt = torch.empty(Mo, device=dev, dtype=torch.int32)
+    out_f = torch.empty(Fo, 3, device=dev, dtype=torch.int32)
+    ops.mesh_simplify(L.MS_SCATTER, vertex_capacity=Mo, face_capacity=Fo, out_vertices=out_v, out_normals=out_n, out_colors=out_c,
+                      source_index=src, vertex_count=cnt, out_faces=out_f, **args)
+    return result(out_v, out_f, out_n, out_c, src, cnt, cells, degenerate, duplicates)
