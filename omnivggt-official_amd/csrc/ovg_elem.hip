@@ -252,10 +252,23 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(ovg_attn_merge_params p
     if constexpr (X3) {
       const f16_t* al = static_cast<const f16_t*>(p.a_lo) + row * p.lda + c * 4;
       const f16_t* bl = static_cast<const f16_t*>(p.b_lo) + row * p.ldb + c * 4;
+      f16_t* oh = static_cast<f16_t*>(p.out) + row * p.ldo + c * 4;
+      f16_t* ol = static_cast<f16_t*>(p.out_lo) + row * p.ldo + c * 4;
+      // A weight of exactly 0 (log-sum-exps further apart than f32's exponent range) makes the result the other input: its pair is handed
+      // through. hi + lo in f32 would round it -- a pair can hold more bits than an f32 (where the stored value is a product, store4_hilo's
+      // `a - hi` is fused with it, so lo comes from the unrounded product: 47 of 82 944 attention outputs in tests/test_gpu_attn_spread.py).
+      if (wa == 0.f || wb == 0.f) {
+        const f16_t* sh = wb == 0.f ? a : b;
+        const f16_t* sl = wb == 0.f ? al : bl;
+        const f16_t h[4] = {sh[0], sh[1], sh[2], sh[3]}, l[4] = {sl[0], sl[1], sl[2], sl[3]};   // out may alias a or b: read before writing
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { oh[i] = h[i]; ol[i] = l[i]; }
+        continue;
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         r[i] = (wa * (static_cast<float>(a[i]) + static_cast<float>(al[i])) + wb * (static_cast<float>(b[i]) + static_cast<float>(bl[i]))) * inv;
-      store4_hilo(static_cast<f16_t*>(p.out) + row * p.ldo + c * 4, static_cast<f16_t*>(p.out_lo) + row * p.ldo + c * 4, r[0], r[1], r[2], r[3]);
+      store4_hilo(oh, ol, r[0], r[1], r[2], r[3]);
       continue;
     }
 #pragma unroll
