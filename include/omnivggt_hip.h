@@ -78,7 +78,9 @@ extern "C" {
  *     + image-space map geometry: usable depth, normals, edge flags and the grid mesh of the prediction maps (ovg_map_depth,
  *       ovg_map_normals, ovg_map_edges, ovg_map_triangulate, ovg_map_triangulate_workspace_bytes): added the same way
  *     + mesh simplification by vertex clustering on the grid of ovg_voxel_downsample, duplicate faces merged (ovg_mesh_simplify,
- *       ovg_mesh_simplify_workspace_bytes): added the same way */
+ *       ovg_mesh_simplify_workspace_bytes): added the same way
+ *     + mesh cleaning: connected components and edge statistics, ordered sub-meshes, Laplacian / Taubin smoothing (ovg_mesh_topology,
+ *       ovg_mesh_select, ovg_mesh_smooth and their *_workspace_bytes queries): added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -1612,6 +1614,113 @@ typedef struct {
 } ovg_mesh_simplify_params;
 int64_t ovg_mesh_simplify_workspace_bytes(int64_t vertices, int64_t faces);
 int ovg_mesh_simplify(const ovg_mesh_simplify_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Mesh cleaning (added under ABI 13): connected components and edge statistics (ovg_mesh_topology), an ordered sub-mesh
+ * (ovg_mesh_select) and Laplacian / Taubin smoothing with vertex normals (ovg_mesh_smooth), by exact rules that name no schedule and
+ * that tests/meshops_twin.py restates in numpy bit for bit.
+ *   vertices [M][3] f32, faces [F][3] int32. 1 <= M < 2^31, 1 <= F < 2^31.
+ *   1. a vertex is VALID when its three coordinates are finite;
+ *   2. a face is LIVE when its three indices lie in [0, M), are pairwise different and name valid vertices; a face of zero area with
+ *      three different indices is live;
+ *   3. a vertex is REFERENCED when a live face names it;
+ *   4. a live face has three EDGES, its unordered index pairs; an edge's multiplicity is the number of live faces that hold it (a
+ *      duplicated face counts twice). A BOUNDARY edge has multiplicity 1, a NON-MANIFOLD edge multiplicity >= 3; a vertex carries
+ *      OVG_MT_BOUNDARY when it ends a boundary edge and OVG_MT_NONMANIFOLD when it ends a non-manifold edge;
+ *   5. two referenced vertices are CONNECTED when a live face names both; the components are the transitive closure, each named by
+ *      its LOWEST vertex index. This is vertex connectivity: two faces that meet in one corner only are one component (Open3D's
+ *      cluster_connected_triangles joins faces across shared edges only and would split them).
+ *
+ * ovg_mesh_topology: vertex_root [M] int32 (the component's lowest vertex index, -1 for an unreferenced vertex), face_root [F] int32
+ *   (-1 for a face that is not live), vertex_flags [M] u8 (OVG_MT_REFERENCED | OVG_MT_BOUNDARY | OVG_MT_NONMANIFOLD) and out_count
+ *   [8] int64 on the device: live faces, referenced vertices, distinct edges, boundary edges, non-manifold edges, boundary vertices,
+ *   non-manifold vertices, status flags. The one status flag is OVG_MT_INTERNAL, raised like OVG_CL_INTERNAL when the union-find
+ *   leaves its bounds: a bug ends as an error, never as a hang. Components: the lock-free union-find of ovg_cluster (csrc/ovg_geom.h
+ *   carries it with its proof) over (a, b) and (b, c) of every live face; vertex_root is its parent array while the launches run.
+ *   Edges: open addressing, linear probing, E = max(1024, 6 F) slots; the key (lo << 32 | hi) is claimed by a 64-bit compare-and-swap,
+ *   a 32-bit count per slot; one pass over the slots derives the edge counts and ORs the vertex flags.
+ *   ws: >= ovg_mesh_topology_workspace_bytes(M, F) bytes, 16-byte aligned: the parts 256, 4 M, 8 E, 4 E, each rounded up to 256.
+ *
+ * ovg_mesh_select: a face SURVIVES when it is live, face_keep[f] != 0 (where face_keep is given) and vertex_keep != 0 at its three
+ *   corners (where vertex_keep is given). One output vertex per vertex a surviving face names, in ascending input index; the
+ *   surviving faces in input order, corners mapped to output numbers.
+ *   stage OVG_MSEL_COUNT: the keep bytes, the ranks and the scans into ws; out_count[0..1] = M', F' (two int64, device). stage
+ *   OVG_MSEL_SCATTER reads what COUNT left in ws and writes the first vertex_capacity entries of out_vertices [.][3] f32 (the input's
+ *   twelve bytes) and out_source_index [.] int64 (optional), and the first face_capacity entries of out_faces [.][3] int32 and
+ *   out_face_index [.] int64 (optional). Other attributes are gathered by the caller through out_source_index.
+ *   ws: >= ovg_mesh_select_workspace_bytes(M, F) bytes, 16-byte aligned: with tv = ceil(M / 4096), tf = ceil(F / 4096) the parts M,
+ *   F, 4 M, 8 tv, 8 tv, 8 tf, 8 tf, each rounded up to 256.
+ *
+ * ovg_mesh_smooth: `iterations` times one step with factor lambda and, when mu != 0, a second step with factor mu (Taubin; mu == 0 is
+ *   plain Laplacian smoothing). The live set, the flags and the neighbour multisets are fixed from the INPUT. A vertex is MOVABLE
+ *   when it is valid, referenced, fixed[i] == 0 (where fixed is given) and, with fix_boundary != 0, no OVG_MT_BOUNDARY vertex; every
+ *   other vertex keeps its twelve input bytes through every step. One step with factor f on the current positions P, every operation
+ *   rounded on its own, in float64 unless it says otherwise:
+ *   a. frame: o = component-wise minimum and max = component-wise maximum of the current positions of the valid vertices (integer
+ *      min / max of order-preserving keys: exact and order-free); ext = the largest over the axes of (double)max - (double)o; e = the
+ *      binary exponent of ext as frexp gives it (ext = mantissa * 2^e, mantissa in [0.5, 1)), e = 0 for ext = 0; u = 2^(e - 30). A
+ *      current coordinate of a valid vertex that is not finite raises OVG_MSM_NONFINITE in out_status; the outputs are then unspecified;
+ *   b. per valid vertex and axis q = llrint(((double)p - (double)o) / u), to nearest, ties to even; 0 <= q <= 2^30;
+ *   c. the neighbour multiset of vertex a holds b and c once for EVERY live face that names a, b and c, whatever the corner order: on
+ *      a manifold interior every neighbour appears twice and the mean is the umbrella mean; duplicated faces and non-manifold edges
+ *      weigh in by multiplicity. S = the int64 sum of the neighbours' q per axis, n = the multiset's size (n <= 2 F < 2^32, |S| < 2^62);
+ *   d. a movable vertex moves to p' = (float)((double)p + (double)f * (m - (double)p)) with m = (double)o + u * ((double)S / (double)n).
+ *   out_vertices [M][3] f32. out_normals [M][3] f32 (optional), from the final positions: per live face d1 = (double)pb - (double)pa,
+ *   d2 = (double)pc - (double)pa, c = (d1y d2z - d1z d2y, d1z d2x - d1x d2z, d1x d2y - d1y d2x), l = sqrt((cx cx + cy cy) + cz cz); a
+ *   face with l finite and > 0 adds llrint(c_k / l * 2^20) per component to the int64 sums of its three vertices; the output is
+ *   normalised exactly as rule 11 of ovg_mesh_simplify, a vertex without such a face gets (0, 0, 0). iterations == 0 copies the
+ *   vertices and only computes normals. out_status [1] int64: the OVG_MSM_* flags raised.
+ *   The neighbour multisets are a CSR adjacency built once per call (integer atomics count and fill; the order inside a row may differ
+ *   from run to run, which integer sums do not see); a step is then a gather without atomics: q in one 16-byte record per vertex, one
+ *   thread per vertex, a row of more than 64 neighbours summed by the thread's whole wave. The frame of the next step is reduced by
+ *   the update of the one before.
+ *   ws: >= ovg_mesh_smooth_workspace_bytes(M, F) bytes, 16-byte aligned: with E and tv as above the parts 256, 4 M, 8 E, 4 E, 4 M,
+ *   8 (M + 1), 8 tv, 8 tv, 24 F, 16 M, 24 M, each rounded up to 256.
+ *
+ * All three: integer atomics only (relaxed, agent scope): no result depends on arrival order, two runs give identical bytes. Every
+ * loop is bounded and no workgroup waits for another. Nothing is allocated, nothing is read back, every launch goes to the caller's
+ * stream. The three queries return -1 for M <= 0, F <= 0, M >= 2^31 or F >= 2^31.
+ * OVG_E_ARG before the first HIP call, and then nothing is written: NULL params / vertices / faces / ws or a NULL required output
+ * (topology: all four; select: out_count in COUNT, out_vertices when vertex_capacity > 0 and out_faces when face_capacity > 0 in
+ * SCATTER; smooth: out_vertices and out_status), sizes outside the limits, an unknown stage, a negative capacity, iterations outside
+ * [0, 65536], a lambda or mu that is not finite, fix_boundary other than 0 / 1, out_vertices == vertices (smoothing reads the input to
+ * the end), a pointer that is not aligned to its element, a misaligned or undersized workspace.
+ * Not in it: hole filling, edge-adjacency components, pinch-vertex detection (two fans meeting in one vertex pass as manifold),
+ * cotangent or area weights, quadric simplification, any guarantee that smoothing keeps a mesh free of self-intersections.
+ * ------------------------------------------------------------------ */
+enum { OVG_MT_REFERENCED = 1, OVG_MT_BOUNDARY = 2, OVG_MT_NONMANIFOLD = 4 };   /* vertex_flags */
+enum { OVG_MT_INTERNAL = 1 };                                                  /* out_count[7] */
+enum { OVG_MSEL_COUNT = 1, OVG_MSEL_SCATTER = 2 };
+enum { OVG_MSM_NONFINITE = 1 };                                                /* out_status[0] */
+typedef struct {
+  const float* vertices; const int32_t* faces;
+  int64_t num_vertices; int64_t num_faces;
+  int32_t* vertex_root; int32_t* face_root; uint8_t* vertex_flags; int64_t* out_count;
+  void* ws; int64_t ws_bytes;
+} ovg_mesh_topology_params;
+int64_t ovg_mesh_topology_workspace_bytes(int64_t vertices, int64_t faces);
+int ovg_mesh_topology(const ovg_mesh_topology_params*, void* stream);
+
+typedef struct {
+  const float* vertices; const int32_t* faces; const uint8_t* face_keep; const uint8_t* vertex_keep;
+  int64_t num_vertices; int64_t num_faces;
+  int32_t stage; int32_t pad;
+  int64_t vertex_capacity; int64_t face_capacity;
+  float* out_vertices; int64_t* out_source_index; int32_t* out_faces; int64_t* out_face_index; int64_t* out_count;
+  void* ws; int64_t ws_bytes;
+} ovg_mesh_select_params;
+int64_t ovg_mesh_select_workspace_bytes(int64_t vertices, int64_t faces);
+int ovg_mesh_select(const ovg_mesh_select_params*, void* stream);
+
+typedef struct {
+  const float* vertices; const int32_t* faces; const uint8_t* fixed;
+  int64_t num_vertices; int64_t num_faces;
+  int32_t iterations; int32_t fix_boundary; float lambda; float mu;
+  float* out_vertices; float* out_normals; int64_t* out_status;
+  void* ws; int64_t ws_bytes;
+} ovg_mesh_smooth_params;
+int64_t ovg_mesh_smooth_workspace_bytes(int64_t vertices, int64_t faces);
+int ovg_mesh_smooth(const ovg_mesh_smooth_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Input preprocessing (ABI 13): everything the reference's loaders (visual_util.py:679-845, omnivggt/utils/load_fn.py:53-146) do

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libomnivggt_hip.so")
 SOURCES = ["ovg_gemm.hip", "ovg_attn.hip", "ovg_elem.hip", "ovg_block.hip", "ovg_head.hip", "ovg_camhead.hip", "ovg_camtab.hip", "ovg_pointcloud.hip",
            "ovg_preprocess.hip", "ovg_render.hip", "ovg_consistency.hip", "ovg_nn.hip", "ovg_fps.hip", "ovg_radius.hip", "ovg_normals.hip",
-           "ovg_align.hip", "ovg_plane.hip", "ovg_tsdf.hip", "ovg_raster.hip", "ovg_deptheval.hip", "ovg_mapgeom.hip", "ovg_meshsimp.hip"]
+           "ovg_align.hip", "ovg_plane.hip", "ovg_tsdf.hip", "ovg_raster.hip", "ovg_deptheval.hip", "ovg_mapgeom.hip", "ovg_meshops.hip", "ovg_meshsimp.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # every exact-arithmetic unit restates a numpy twin (tests/*_twin.py) operation for operation, one rounding each: no FMA contraction
 # anywhere in it, the inlined HIP header helpers and the shared primitives of csrc/ovg_geom.h and csrc/ovg_project.h included
@@ -24,7 +24,8 @@ EXACT_UNITS = ("ovg_pointcloud.hip", "ovg_render.hip", "ovg_consistency.hip", "o
 # attention: no NaN can occur on valid inputs (masked scores are -inf, never inf-inf), and without
 # this hipcc inserts a canonicalising v_max before every fmaxf on an MFMA output (64 VALU / tile)
 EXTRA_FLAGS = {"ovg_attn.hip": ["-fno-honor-nans"], **{unit: ["-ffp-contract=off"] for unit in EXACT_UNITS},
-               "ovg_meshsimp.hip": ["-ffp-contract=off"]}      # exact like the thirteen: the mean position and the normalisation restate numpy
+               "ovg_meshsimp.hip": ["-ffp-contract=off"],      # exact like the thirteen: the mean position and the normalisation restate numpy
+               "ovg_meshops.hip": ["-ffp-contract=off"]}       # and so do the quantisation, the update and the normals of the smoother
 
 
 # attn16_kernel<bf16, QB, WAVES, MODE 0, RING, X3 0>: the three launches of the bf16 plan (mangled-name fragment -> QB)

@@ -1,6 +1,7 @@
 // The small primitives shared by the exact-arithmetic geometry units (point clouds, rendering, consistency, neighbour searches,
-// normals, registration, planes, fusion, rasterisation, depth scoring, map geometry): finite tests, wave and workgroup scans and
-// reductions, the fixed-order float64 fold, the symmetric 3 x 3 Jacobi solve, a hash finaliser, and the hosts' argument helpers.
+// normals, registration, planes, fusion, rasterisation, depth scoring, map geometry, mesh operations): finite tests, float order
+// keys, wave and workgroup scans and reductions, the ordered tile compaction, the fixed-order float64 fold, the symmetric 3 x 3 Jacobi solve, a hash finaliser, the
+// lock-free union-find, and the hosts' argument helpers.
 // Every one of them is part of a bit-exactness contract with a numpy twin in tests/*_twin.py: a change here changes all its users at
 // once, which is the point. Units that include this are compiled with -ffp-contract=off (build.py); the pragma below covers the
 // functions of this header whatever the order of the including unit's own pragma and its #include.
@@ -17,6 +18,13 @@ OVG_DEV bool finite_f32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 
 OVG_DEV bool finite_f64(double d) { return (__double_as_longlong(d) & 0x7FF0000000000000ll) != 0x7FF0000000000000ll; }
 OVG_DEV bool finite3(float x, float y, float z) { return finite_f32(x) && finite_f32(y) && finite_f32(z); }
 OVG_DEV bool finite3(const float* __restrict__ p) { return finite3(p[0], p[1], p[2]); }
+
+// order-preserving u32 of a finite f32 and back: an unsigned integer min / max over the keys is the float min / max, exact and order-free
+OVG_DEV uint32_t order_key32(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+OVG_DEV float key_value32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // murmur3's 64-bit finaliser
 OVG_DEV uint64_t mix_murmur64(uint64_t h) {
@@ -101,6 +109,42 @@ template <int THREADS, typename T, class Op> OVG_DEV T block_reduce(T v, T* red,
   return t;
 }
 
+// order-preserving compaction of one tile of keep bytes by a workgroup of THREADS (ovg_mesh_simplify, ovg_mesh_select): entry i of tile
+// blockIdx.x lands at offsets[blockIdx.x] + (kept entries before it in the tile); the order inside a tile is j-major (j * THREADS +
+// thread), which is the index order. emit(i, pos) for every kept entry. Every thread calls it, once per kernel.
+template <int THREADS, int TILE, class Emit>
+OVG_DEV void compact_tile(const uint8_t* keep, int64_t n, const int64_t* offsets, Emit emit) {
+  constexpr int J = TILE / THREADS, W = THREADS / 64;
+  static_assert(J * W == 64 && J <= 32, "the group counts are scanned by one wave, the kept bits live in one word");
+  __shared__ uint32_t cnt[J * W];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * TILE;
+  uint32_t bits = 0;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int64_t i = base + (int64_t)j * THREADS + threadIdx.x;
+    const bool k = i < n && keep[i];
+    bits |= (uint32_t)k << j;
+    const uint64_t bal = __ballot(k);
+    if (lane == 0) cnt[j * W + wave] = __popcll(bal);
+  }
+  __syncthreads();
+  if (wave == 0) {                                     // 64 groups: one exclusive scan in wave 0
+    const uint64_t v = cnt[lane];
+    cnt[lane] = (uint32_t)(wave_incl_scan(v) - v);
+  }
+  __syncthreads();
+  const int64_t off = offsets[blockIdx.x];
+  const uint64_t below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const bool k = (bits >> j) & 1u;
+    const uint64_t bal = __ballot(k);
+    if (!k) continue;
+    emit(base + (int64_t)j * THREADS + threadIdx.x, off + cnt[j * W + wave] + __popcll(bal & below));
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the float64 fold of a workgroup of THREADS = 256 in a FIXED order (include/omnivggt_hip.h, ovg_align_moments): v[l] = v[l] + v[l + s]
 // for s = 32 .. 1 inside every wave, then (w0 + w1) + (w2 + w3). Thread k < NSUMS leaves with sum k, thread NSUMS + k with count k.
@@ -181,6 +225,64 @@ OVG_DEV double jacobi_smallest(double xx, double yy, double zz, const double (&v
   const double len = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
   e[0] = e[0] / len, e[1] = e[1] / len, e[2] = e[2] / len;
   return lam;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the lock-free union-find of ovg_cluster (csrc/ovg_radius.hip: cl_degree, cl_link, cl_flatten) and of ovg_mesh_topology
+// (csrc/ovg_meshops.hip: mo_faces hooks, mt_finish flattens). What follows was written for ovg_cluster and names its launches; the
+// other user keeps the same discipline: parent[x] = x before the first hook, hooks in one launch, the final finds in a later one.
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The union-find. parent[x] of a core point x, read and written in cl_link / cl_flatten ONLY through relaxed agent-scope atomics (a
+// plain load may be served from a CU's L1 or another XCD's L2 and go stale). Writes are of two kinds: a HOOK, the 32-bit
+// compare-and-swap parent[hi]: hi -> lo with lo < hi, and a HALVING, the atomic min of parent[x] with a value read from parent[parent[x]].
+// Invariants, by induction over the writes in the order the memory system performs them on each slot (cl_degree left parent[x] = x):
+//   (a) parent[x] <= x. A hook stores lo < hi; a min never raises a slot.
+//   (b) a slot only ever decreases: a hook replaces hi by lo < hi, a min is a min.
+//   (c) every value ever stored in parent[x] is a member of x's component (of the graph of rule 5). A hook stores lo, a point reached
+//       by following parents from b, where a, b are neighbours and hi was reached from a: by (c) for the slots followed, lo ~ b ~ a ~ hi.
+//       A halving stores a value once held by parent[p], p once held by parent[x]: a member of p's component, which is x's.
+//   (d) the parents form a forest: a non-root slot holds a strictly smaller index, so following parents descends and ends, after at most
+//       x steps, at an r with parent[r] == r; a hook succeeds only on a slot that still holds its own index, a root at that instant,
+//       and so hangs hi's whole tree under lo: under the root of another tree, or (when lo has been hooked itself since it was
+//       read) under an inner node of one -- one tree fewer either way; a halving moves x under a former ancestor g, which by (b)
+//       and (d) is still in x's tree. Trees only ever merge.
+// After cl_link has ended every neighbour pair of core points is in one tree: cl_unite returns only after a successful hook between
+// the two trees or after both walks ended at the same root. With (c) the trees are exactly the components, and by (a) along the path
+// a tree's root is <= every member and is a member: the component's LOWEST index, whatever the schedule.
+// Termination: nothing waits. cl_find descends by at least one index per step. A failed compare-and-swap returns the slot's new
+// value, < hi by (a) and (b): another thread's hook or halving made progress, and this thread's cursor moves down to that value. So
+// the two cursors of a cl_unite only move down from a0, b0 < n: find steps plus failed swaps < 2 n, and the step budget 4 n + 4
+// (every outer round spends at least two steps) is never met by correct code. A value outside [0, x], or a spent budget, sets
+// OVG_CL_INTERNAL and leaves: a bug ends as an error, never as a hang, and no index outside [0, n) is ever followed.
+OVG_DEV int32_t cl_ld(int32_t* a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x's tree at some instant during the call, halving the path on the way; -1 on a broken invariant or a spent budget
+OVG_DEV int32_t cl_find(int32_t* parent, int32_t x, uint64_t& budget) {
+  while (budget) {
+    --budget;
+    const int32_t p = cl_ld(parent + x);
+    if (p == x) return x;
+    if ((uint32_t)p > (uint32_t)x) return -1;
+    const int32_t g = cl_ld(parent + p);
+    if ((uint32_t)g > (uint32_t)p) return -1;
+    if (g != p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = p;
+  }
+  return -1;
+}
+
+OVG_DEV bool cl_unite(int32_t* parent, int32_t a, int32_t b, uint64_t budget) {
+  for (;;) {
+    a = cl_find(parent, a, budget);
+    b = cl_find(parent, b, budget);
+    if ((a | b) < 0) return false;
+    if (a == b) return true;
+    const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+    int32_t seen = hi;
+    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return true;
+    if ((uint32_t)seen >= (uint32_t)hi) return false;
+    a = seen, b = lo;                                  // hi is no root any more: go on from what it points to now
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

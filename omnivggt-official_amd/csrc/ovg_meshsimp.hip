@@ -61,12 +61,6 @@ int64_t ms_layout(int64_t m, int64_t f, uint8_t* base, MsWs* ws) {
   return off[14];
 }
 
-OVG_DEV uint32_t order_key32(float f) {             // order-preserving u32 of a finite f32
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-OVG_DEV float key_value32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
 template <typename T> OVG_DEV T ld(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 OVG_DEV void add64(uint64_t* p, uint64_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 OVG_DEV void raise_flag(MsHead* head, uint32_t flag) {
@@ -287,43 +281,9 @@ __global__ __launch_bounds__(1024) void ms_scan(MsWs ws, int64_t vtiles, int64_t
   }
 }
 
-// order-preserving compaction of a tile of keep bytes: entry i lands at offsets[tile] + (kept entries before it in the tile); the order
-// inside a tile is j-major (j * 256 + thread). emit(i, pos) for every kept entry; every thread of the workgroup calls this once
-template <class Emit>
-OVG_DEV void ms_compact_tile(const uint8_t* keep, int64_t n, const int64_t* offsets, Emit emit) {
-  constexpr int J = kTile / kThreads;
-  __shared__ uint32_t cnt[J * (kThreads / 64)];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t base = (int64_t)blockIdx.x * kTile;
-  uint32_t bits = 0;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int64_t i = base + (int64_t)j * kThreads + threadIdx.x;
-    const bool k = i < n && keep[i];
-    bits |= (uint32_t)k << j;
-    const uint64_t bal = __ballot(k);
-    if (lane == 0) cnt[j * (kThreads / 64) + wave] = __popcll(bal);
-  }
-  __syncthreads();
-  if (wave == 0) {                                     // 64 groups: one exclusive scan in wave 0
-    const uint64_t v = cnt[lane];
-    cnt[lane] = (uint32_t)(wave_incl_scan(v) - v);
-  }
-  __syncthreads();
-  const int64_t off = offsets[blockIdx.x];
-  const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const bool k = (bits >> j) & 1u;
-    const uint64_t bal = __ballot(k);
-    if (!k) continue;
-    emit(base + (int64_t)j * kThreads + threadIdx.x, off + cnt[j * (kThreads / 64) + wave] + __popcll(bal & below));
-  }
-}
-
 // the output number of every kept cell: its leader's rank among the kept leaders
 __global__ __launch_bounds__(kThreads) void ms_ranks(MsWs ws, int64_t m) {
-  ms_compact_tile(ws.vkeep, m, ws.voffsets, [&](int64_t i, int64_t pos) {
+  compact_tile<kThreads, kTile>(ws.vkeep, m, ws.voffsets, [&](int64_t i, int64_t pos) {
     const int64_t s = ws.vslot[i];
     if (s < ws.ncs) ws.rank[s] = (uint32_t)pos;        // always, after this call's COUNT stage
   });
@@ -373,7 +333,7 @@ __global__ __launch_bounds__(kThreads) void ms_scatter_vertices(ovg_mesh_simplif
 
 // the survivors in input order, their corners as output vertex numbers: vertex -> slot -> rank
 __global__ __launch_bounds__(kThreads) void ms_scatter_faces(ovg_mesh_simplify_params p, MsWs ws) {
-  ms_compact_tile(ws.fkeep, p.num_faces, ws.foffsets, [&](int64_t f, int64_t pos) {
+  compact_tile<kThreads, kTile>(ws.fkeep, p.num_faces, ws.foffsets, [&](int64_t f, int64_t pos) {
     if (pos < 0 || pos >= p.face_capacity) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {

@@ -351,58 +351,8 @@ __global__ __launch_bounds__(kThreads) void knn_search(ovg_radius_params p, RsWs
 // neighbour pairs of core points), flatten (root = find), border (non-core points join their nearest core neighbour's cluster).
 // `root` IS the union-find's parent array while the launches run.
 //
-// The union-find. parent[x] of a core point x, read and written in cl_link / cl_flatten ONLY through relaxed agent-scope atomics (a
-// plain load may be served from a CU's L1 or another XCD's L2 and go stale). Writes are of two kinds: a HOOK, the 32-bit
-// compare-and-swap parent[hi]: hi -> lo with lo < hi, and a HALVING, the atomic min of parent[x] with a value read from parent[parent[x]].
-// Invariants, by induction over the writes in the order the memory system performs them on each slot (cl_degree left parent[x] = x):
-//   (a) parent[x] <= x. A hook stores lo < hi; a min never raises a slot.
-//   (b) a slot only ever decreases: a hook replaces hi by lo < hi, a min is a min.
-//   (c) every value ever stored in parent[x] is a member of x's component (of the graph of rule 5). A hook stores lo, a point reached
-//       by following parents from b, where a, b are neighbours and hi was reached from a: by (c) for the slots followed, lo ~ b ~ a ~ hi.
-//       A halving stores a value once held by parent[p], p once held by parent[x]: a member of p's component, which is x's.
-//   (d) the parents form a forest: a non-root slot holds a strictly smaller index, so following parents descends and ends, after at most
-//       x steps, at an r with parent[r] == r; a hook succeeds only on a slot that still holds its own index, a root at that instant,
-//       and so hangs hi's whole tree under lo: under the root of another tree, or (when lo has been hooked itself since it was
-//       read) under an inner node of one -- one tree fewer either way; a halving moves x under a former ancestor g, which by (b)
-//       and (d) is still in x's tree. Trees only ever merge.
-// After cl_link has ended every neighbour pair of core points is in one tree: cl_unite returns only after a successful hook between
-// the two trees or after both walks ended at the same root. With (c) the trees are exactly the components, and by (a) along the path
-// a tree's root is <= every member and is a member: the component's LOWEST index, whatever the schedule.
-// Termination: nothing waits. cl_find descends by at least one index per step. A failed compare-and-swap returns the slot's new
-// value, < hi by (a) and (b): another thread's hook or halving made progress, and this thread's cursor moves down to that value. So
-// the two cursors of a cl_unite only move down from a0, b0 < n: find steps plus failed swaps < 2 n, and the step budget 4 n + 4
-// (every outer round spends at least two steps) is never met by correct code. A value outside [0, x], or a spent budget, sets
-// OVG_CL_INTERNAL and leaves: a bug ends as an error, never as a hang, and no index outside [0, n) is ever followed.
-OVG_DEV int32_t cl_ld(int32_t* a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x's tree at some instant during the call, halving the path on the way; -1 on a broken invariant or a spent budget
-OVG_DEV int32_t cl_find(int32_t* parent, int32_t x, uint64_t& budget) {
-  while (budget) {
-    --budget;
-    const int32_t p = cl_ld(parent + x);
-    if (p == x) return x;
-    if ((uint32_t)p > (uint32_t)x) return -1;
-    const int32_t g = cl_ld(parent + p);
-    if ((uint32_t)g > (uint32_t)p) return -1;
-    if (g != p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = p;
-  }
-  return -1;
-}
-
-OVG_DEV bool cl_unite(int32_t* parent, int32_t a, int32_t b, uint64_t budget) {
-  for (;;) {
-    a = cl_find(parent, a, budget);
-    b = cl_find(parent, b, budget);
-    if ((a | b) < 0) return false;
-    if (a == b) return true;
-    const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-    int32_t seen = hi;
-    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return true;
-    if ((uint32_t)seen >= (uint32_t)hi) return false;
-    a = seen, b = lo;                                  // hi is no root any more: go on from what it points to now
-  }
-}
+// The union-find (cl_ld, cl_find, cl_unite) and the invariant / termination proof that stands above it live in ovg_geom.h: ovg_mesh_topology
+// runs the same code over the corners of the live faces.
 
 // rs_search's walk over the box of point i of the one cloud: visit(bits(d), j) for every neighbour record (rule 2: j != i)
 template <class Visit>

@@ -426,6 +426,29 @@ class MeshSimplifyParams(C.Structure):
                 ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
+MT_REFERENCED, MT_BOUNDARY, MT_NONMANIFOLD = 1, 2, 4          # ovg_mesh_topology: bits of vertex_flags
+MT_INTERNAL = 1                                              # flag in out_count[7]
+MSEL_COUNT, MSEL_SCATTER = 1, 2                              # ovg_mesh_select_params.stage
+MSM_NONFINITE = 1                                            # ovg_mesh_smooth: flag in out_status[0]
+
+
+class MeshTopologyParams(C.Structure):
+    _fields_ = [("vertices", vp), ("faces", vp), ("num_vertices", i64), ("num_faces", i64), ("vertex_root", vp), ("face_root", vp),
+                ("vertex_flags", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
+class MeshSelectParams(C.Structure):
+    _fields_ = [("vertices", vp), ("faces", vp), ("face_keep", vp), ("vertex_keep", vp), ("num_vertices", i64), ("num_faces", i64),
+                ("stage", i32), ("pad", i32), ("vertex_capacity", i64), ("face_capacity", i64), ("out_vertices", vp), ("out_source_index", vp),
+                ("out_faces", vp), ("out_face_index", vp), ("out_count", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
+class MeshSmoothParams(C.Structure):
+    _fields_ = [("vertices", vp), ("faces", vp), ("fixed", vp), ("num_vertices", i64), ("num_faces", i64), ("iterations", i32),
+                ("fix_boundary", i32), ("lam", f32), ("mu", f32), ("out_vertices", vp), ("out_normals", vp), ("out_status", vp), ("ws", vp),
+                ("ws_bytes", i64)]
+
+
 RS_F32_CHW, RS_U8_HWC = 0, 1
 
 
@@ -532,6 +555,12 @@ SYMBOLS = {
     "ovg_map_triangulate_workspace_bytes": (i64, [i32, i32, i32]),
     "ovg_mesh_simplify": (i32, [C.POINTER(MeshSimplifyParams), vp]),
     "ovg_mesh_simplify_workspace_bytes": (i64, [i64, i64]),
+    "ovg_mesh_topology": (i32, [C.POINTER(MeshTopologyParams), vp]),
+    "ovg_mesh_topology_workspace_bytes": (i64, [i64, i64]),
+    "ovg_mesh_select": (i32, [C.POINTER(MeshSelectParams), vp]),
+    "ovg_mesh_select_workspace_bytes": (i64, [i64, i64]),
+    "ovg_mesh_smooth": (i32, [C.POINTER(MeshSmoothParams), vp]),
+    "ovg_mesh_smooth_workspace_bytes": (i64, [i64, i64]),
 }
 
 

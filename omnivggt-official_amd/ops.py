@@ -1796,3 +1796,125 @@ def mesh_simplify(stage, vertices, faces, voxel, ws, normals=None, colors=None, 
     p.out_source_index, p.out_vertex_count, p.out_faces = L.ptr(source_index), L.ptr(vertex_count), L.ptr(out_faces)
     p.out_count, p.ws, p.ws_bytes = L.ptr(out_count), L.ptr(ws), nbytes(ws)
     L.call("ovg_mesh_simplify", p, _stream())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# mesh cleaning: components and edge statistics, ordered sub-meshes, Laplacian / Taubin smoothing (ovg_mesh_topology / _select / _smooth)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _meshops_workspace_bytes(name, vertices, faces):
+    if not all(-(1 << 63) <= int(v) < (1 << 63) for v in (vertices, faces)):
+        raise L.OvgError("%s: unsupported (vertices=%d, faces=%d)" % (name, vertices, faces))
+    b = getattr(L.load(), name)(int(vertices), int(faces))
+    if b < 0:
+        raise L.OvgError("%s: unsupported (vertices=%d, faces=%d)" % (name, vertices, faces))
+    return int(b)
+
+
+def mesh_topology_workspace_bytes(vertices, faces):
+    return _meshops_workspace_bytes("ovg_mesh_topology_workspace_bytes", vertices, faces)
+
+
+def mesh_select_workspace_bytes(vertices, faces):
+    return _meshops_workspace_bytes("ovg_mesh_select_workspace_bytes", vertices, faces)
+
+
+def mesh_smooth_workspace_bytes(vertices, faces):
+    return _meshops_workspace_bytes("ovg_mesh_smooth_workspace_bytes", vertices, faces)
+
+
+def _meshops_mesh(what, vertices, faces, ws):
+    """The checks the three entries share -> (M, F)."""
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or not 1 <= vertices.shape[0] < 1 << 31:
+        raise L.OvgError("%s: vertices must be a tensor [M, 3], 1 <= M < 2^31" % what)
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or not 1 <= faces.shape[0] < 1 << 31:
+        raise L.OvgError("%s: faces must be a tensor [F, 3], 1 <= F < 2^31" % what)
+    M, F = int(vertices.shape[0]), int(faces.shape[0])
+    _map_tensor(what, vertices, "vertices", torch.float32, (M, 3))
+    _map_tensor(what, faces, "faces", torch.int32, (F, 3))
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    return M, F
+
+
+def mesh_topology(vertices, faces, ws, vertex_root, face_root, vertex_flags, out_count):
+    """ovg_mesh_topology on contiguous device tensors: vertices f32 [M, 3], faces int32 [F, 3]; ws a uint8 tensor of at least
+    mesh_topology_workspace_bytes(M, F) bytes. Writes vertex_root int32 [M], face_root int32 [F], vertex_flags u8 [M] (the L.MT_* bits)
+    and the eight int64 of out_count: live faces, referenced vertices, edges, boundary edges, non-manifold edges, boundary vertices,
+    non-manifold vertices, status flags (L.MT_INTERNAL)."""
+    what = "mesh_topology"
+    M, F = _meshops_mesh(what, vertices, faces, ws)
+    _map_tensor(what, vertex_root, "vertex_root", torch.int32, (M,))
+    _map_tensor(what, face_root, "face_root", torch.int32, (F,))
+    _map_tensor(what, vertex_flags, "vertex_flags", torch.uint8, (M,))
+    _map_tensor(what, out_count, "out_count", torch.int64, (8,))
+    _chk_dev(vertices, faces, ws, vertex_root, face_root, vertex_flags, out_count)
+    p = L.MeshTopologyParams()
+    p.vertices, p.faces, p.num_vertices, p.num_faces = L.ptr(vertices), L.ptr(faces), M, F
+    p.vertex_root, p.face_root, p.vertex_flags, p.out_count = L.ptr(vertex_root), L.ptr(face_root), L.ptr(vertex_flags), L.ptr(out_count)
+    p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
+    L.call("ovg_mesh_topology", p, _stream())
+
+
+def mesh_select(stage, vertices, faces, ws, face_keep=None, vertex_keep=None, out_count=None, vertex_capacity=0, face_capacity=0,
+                out_vertices=None, source_index=None, out_faces=None, face_index=None):
+    """ovg_mesh_select on contiguous device tensors: vertices f32 [M, 3], faces int32 [F, 3], face_keep u8 [F] and vertex_keep u8 [M]
+    or None; ws a uint8 tensor of at least mesh_select_workspace_bytes(M, F) bytes. stage L.MSEL_COUNT writes (M', F') to the two
+    int64 of out_count; L.MSEL_SCATTER writes the first vertex_capacity vertices to out_vertices f32 [., 3] (source_index int64 [.]
+    optional) and the first face_capacity faces to out_faces int32 [., 3] (face_index int64 [.] optional) from what the COUNT stage
+    left in ws."""
+    what = "mesh_select"
+    M, F = _meshops_mesh(what, vertices, faces, ws)
+    _map_tensor(what, face_keep, "face_keep", torch.uint8, (F,), True)
+    _map_tensor(what, vertex_keep, "vertex_keep", torch.uint8, (M,), True)
+    if stage not in (L.MSEL_COUNT, L.MSEL_SCATTER, L.MSEL_COUNT | L.MSEL_SCATTER):
+        raise L.OvgError("%s: unknown stage %r" % (what, stage))
+    for name, v in (("vertex_capacity", vertex_capacity), ("face_capacity", face_capacity)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 62:
+            raise L.OvgError("%s: %s must be a non-negative integer, got %r" % (what, name, v))
+    if stage & L.MSEL_SCATTER:
+        outs = ((out_vertices, torch.float32, 3 * vertex_capacity, True), (source_index, torch.int64, vertex_capacity, False),
+                (out_faces, torch.int32, 3 * face_capacity, True), (face_index, torch.int64, face_capacity, False))
+        for t, dt, need, required in outs:
+            if need and (t is not None or required) and \
+                    (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < need):
+                raise L.OvgError("%s: output buffers must be contiguous and hold the capacities" % what)
+    if (stage & L.MSEL_COUNT or out_count is not None) and \
+            (not isinstance(out_count, torch.Tensor) or out_count.dtype != torch.int64 or out_count.numel() < 2 or not out_count.is_contiguous()):
+        raise L.OvgError("%s: out_count must be a contiguous int64 device tensor of two elements" % what)
+    _chk_dev(vertices, faces, ws, face_keep, vertex_keep, out_count, out_vertices, source_index, out_faces, face_index)
+    p = L.MeshSelectParams()
+    p.vertices, p.faces, p.face_keep, p.vertex_keep = L.ptr(vertices), L.ptr(faces), L.ptr(face_keep), L.ptr(vertex_keep)
+    p.num_vertices, p.num_faces, p.stage, p.pad = M, F, int(stage), 0
+    p.vertex_capacity, p.face_capacity = vertex_capacity, face_capacity
+    p.out_vertices, p.out_source_index, p.out_faces, p.out_face_index = L.ptr(out_vertices), L.ptr(source_index), L.ptr(out_faces), L.ptr(face_index)
+    p.out_count, p.ws, p.ws_bytes = L.ptr(out_count), L.ptr(ws), nbytes(ws)
+    L.call("ovg_mesh_select", p, _stream())
+
+
+def mesh_smooth(vertices, faces, ws, iterations, lam, mu, out_vertices, out_status, fixed=None, fix_boundary=True, out_normals=None):
+    """ovg_mesh_smooth on contiguous device tensors: vertices f32 [M, 3], faces int32 [F, 3], fixed u8 [M] or None; ws a uint8 tensor of
+    at least mesh_smooth_workspace_bytes(M, F) bytes. `iterations` steps with factor f32(lam), each followed by one with f32(mu) when
+    mu != 0. Writes out_vertices f32 [M, 3] (not the input tensor), out_normals f32 [M, 3] when given, and the L.MSM_* flags to the
+    one int64 of out_status."""
+    what = "mesh_smooth"
+    M, F = _meshops_mesh(what, vertices, faces, ws)
+    _map_tensor(what, fixed, "fixed", torch.uint8, (M,), True)
+    _map_tensor(what, out_vertices, "out_vertices", torch.float32, (M, 3))
+    _map_tensor(what, out_normals, "out_normals", torch.float32, (M, 3), True)
+    _map_tensor(what, out_status, "out_status", torch.int64, (1,))
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= 65536:
+        raise L.OvgError("%s: iterations must be an integer in [0, 65536], got %r" % (what, iterations))
+    for name, v in (("lam", lam), ("mu", mu)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not abs(float(v)) <= 3.4028234663852886e38:
+            raise L.OvgError("%s: %s must be a finite float32 value, got %r" % (what, name, v))
+    if not isinstance(fix_boundary, bool):
+        raise L.OvgError("%s: fix_boundary must be True or False, got %r" % (what, fix_boundary))
+    if out_vertices.data_ptr() == vertices.data_ptr():
+        raise L.OvgError("%s: out_vertices must not be the input tensor" % what)
+    _chk_dev(vertices, faces, ws, fixed, out_vertices, out_normals, out_status)
+    p = L.MeshSmoothParams()
+    p.vertices, p.faces, p.fixed, p.num_vertices, p.num_faces = L.ptr(vertices), L.ptr(faces), L.ptr(fixed), M, F
+    p.iterations, p.fix_boundary, p.lam, p.mu = iterations, int(fix_boundary), float(lam), float(mu)
+    p.out_vertices, p.out_normals, p.out_status = L.ptr(out_vertices), L.ptr(out_normals), L.ptr(out_status)
+    p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
+    L.call("ovg_mesh_smooth", p, _stream())

@@ -3073,3 +3073,263 @@ def simplify_mesh(mesh, voxel_size=None, rel_size=None, position="mean"):
     ops.mesh_simplify(L.MS_SCATTER, vertex_capacity=Mo, face_capacity=Fo, out_vertices=out_v, out_normals=out_n, out_colors=out_c,
                       source_index=src, vertex_count=cnt, out_faces=out_f, **args)
     return result(out_v, out_f, out_n, out_c, src, cnt, cells, degenerate, duplicates)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Mesh cleaning: connected components, small-piece removal and Laplacian / Taubin smoothing (ovg_mesh_topology / _select / _smooth)
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Not in any of it: hole filling, edge-adjacency components, pinch-vertex detection, cotangent or area weights, quadric simplification,
+# any guarantee that smoothing keeps a mesh free of self-intersections.
+
+MT_REFERENCED, MT_BOUNDARY, MT_NONMANIFOLD = ops.L.MT_REFERENCED, ops.L.MT_BOUNDARY, ops.L.MT_NONMANIFOLD
+
+
+class MeshTopology:
+    """Result of mesh_topology. Device tensors: vertex_root int32 (M,) (the lowest vertex index of the vertex's component, -1 for a
+    vertex no live face names), face_root int32 (F,) (-1 for a face that is not live), vertex_flags uint8 (M,) (MT_REFERENCED |
+    MT_BOUNDARY | MT_NONMANIFOLD), vertex_labels / face_labels int32 (the dense component number, -1 where the root is -1); per
+    component, in label order: roots int32 (C,), face_sizes and vertex_sizes int64 (C,). Host integers: num_components, live_faces,
+    referenced_vertices, edges, boundary_edges, nonmanifold_edges, boundary_vertices, nonmanifold_vertices, euler (= referenced_vertices
+    - edges + live_faces); closed: there is a live face and no boundary edge."""
+    __slots__ = ("vertex_root", "face_root", "vertex_flags", "vertex_labels", "face_labels", "roots", "face_sizes", "vertex_sizes",
+                 "num_components", "live_faces", "referenced_vertices", "edges", "boundary_edges", "nonmanifold_edges", "boundary_vertices",
+                 "nonmanifold_vertices", "euler", "closed")
+
+    def __init__(self, vertex_root, face_root, vertex_flags, vertex_labels, face_labels, roots, face_sizes, vertex_sizes, counts=(0,) * 7):
+        self.vertex_root, self.face_root, self.vertex_flags = vertex_root, face_root, vertex_flags
+        self.vertex_labels, self.face_labels, self.roots, self.face_sizes, self.vertex_sizes = vertex_labels, face_labels, roots, face_sizes, vertex_sizes
+        self.num_components = int(roots.numel())
+        (self.live_faces, self.referenced_vertices, self.edges, self.boundary_edges, self.nonmanifold_edges, self.boundary_vertices,
+         self.nonmanifold_vertices) = (int(c) for c in counts)
+        self.euler = self.referenced_vertices - self.edges + self.live_faces
+        self.closed = self.live_faces > 0 and self.boundary_edges == 0
+
+
+class MeshSubset(Mesh):
+    """A Mesh from select_faces / remove_small_components: additionally source_index (M',) int64, the input index of every output vertex;
+    face_index (F',) int64, the input index of every output face; pixel_index (M',) int64 = mesh.pixel_index[source_index] when the
+    input carried one (a MapMesh, a SimplifiedMesh of one), else None."""
+    __slots__ = ("source_index", "face_index", "pixel_index")
+
+    def __init__(self, vertices, faces, normals, colors, transform, extrinsic=None, scene_scale=None, source_index=None, face_index=None,
+                 pixel_index=None):
+        Mesh.__init__(self, vertices, faces, normals, colors, transform, extrinsic, scene_scale)
+        self.source_index, self.face_index, self.pixel_index = source_index, face_index, pixel_index
+
+
+def _mesh_arrays(what, mesh, *more):
+    """The checks the mesh operations share -> (vertices f32 (M,3), faces int32 (F,3), M, F, device); tensors are None for an empty mesh."""
+    if not isinstance(mesh, Mesh):
+        raise ValueError("%s: expected a Mesh" % what)
+    vert, faces = mesh.vertices, mesh.faces
+    if vert is None or faces is None:
+        raise ValueError("%s: the mesh has no vertices or no faces tensor" % what)
+    for t in (vert, faces, mesh.normals, mesh.colors, getattr(mesh, "pixel_index", None)) + more:
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise ops.L.OvgError("%s needs HIP device tensors: there is no CPU fallback" % what)
+    M, F = int(vert.shape[0]), int(faces.shape[0])
+    if M >= 1 << 31 or F >= 1 << 31:
+        raise ValueError("%s: the mesh has 2^31 vertices or faces or more" % what)
+    if M == 0 or F == 0:
+        return None, None, M, F, vert.device
+    return vert.reshape(M, 3).float().contiguous(), faces.reshape(F, 3).to(torch.int32).contiguous(), M, F, vert.device
+
+
+def _mesh_mask(what, name, mask, n):
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.numel() != n:
+        raise ValueError("%s: %s must be a bool / uint8 tensor of %d elements" % (what, name, n))
+    return mask
+
+
+def mesh_topology(mesh, order="size"):
+    """What hangs together in a Mesh, and how its edges are used, on the device (ovg_mesh_topology; tests/meshops_twin.py restates the
+    rule). A vertex is valid when its coordinates are finite; a face is live when its indices lie in the mesh, are pairwise different
+    and name valid vertices (zero area does not matter). Two vertices are connected when a live face names both, and a component is
+    named by its lowest vertex index. This is VERTEX connectivity: two faces that meet in one corner only are one component, where
+    Open3D's cluster_connected_triangles (faces joined across shared edges) would give two. An edge held by one live face is a boundary
+    edge, by three or more a non-manifold edge (a duplicated face counts twice); their end vertices carry MT_BOUNDARY / MT_NONMANIFOLD.
+
+    order: "size" (default) numbers the components by descending face count, equal counts by ascending root, exactly as cluster_points
+    numbers clusters, so label 0 is the largest piece; "index" numbers them by ascending root.
+
+    -> MeshTopology. One read of the eight counts (the dense labels read the number of components back as well, as cluster_points
+    does). A mesh without vertices or without faces returns empty results without a launch. CPU tensors raise OvgError (there is no
+    CPU fallback), OVG_MT_INTERNAL (the union-find left its bounds: a bug) raises OvgError too.
+    Not in it: hole filling, edge-adjacency components, pinch-vertex detection (two fans meeting in one vertex pass as manifold),
+    cotangent or area weights, quadric simplification, any guarantee that smoothing keeps a mesh free of self-intersections."""
+    what = "mesh_topology"
+    if order not in ("size", "index"):
+        raise ValueError("%s: order must be \"size\" or \"index\", got %r" % (what, order))
+    vert, faces, M, F, dev = _mesh_arrays(what, mesh)
+    if vert is None:
+        none32 = lambda n: torch.full((n,), -1, device=dev, dtype=torch.int32)
+        return MeshTopology(none32(M), none32(F), torch.zeros(M, device=dev, dtype=torch.uint8), none32(M), none32(F), none32(0),
+                            torch.zeros(0, device=dev, dtype=torch.int64), torch.zeros(0, device=dev, dtype=torch.int64))
+    vroot, froot = torch.empty(M, device=dev, dtype=torch.int32), torch.empty(F, device=dev, dtype=torch.int32)
+    vflags, count = torch.empty(M, device=dev, dtype=torch.uint8), torch.empty(8, device=dev, dtype=torch.int64)
+    ws = torch.empty(ops.mesh_topology_workspace_bytes(M, F), device=dev, dtype=torch.uint8)
+    ops.mesh_topology(vert, faces, ws, vroot, froot, vflags, count)
+    counts = count.cpu().tolist()                                                                    # the one read of the counts
+    if counts[7] & ops.L.MT_INTERNAL:
+        raise ops.L.OvgError("%s: the union-find left its bounds (OVG_MT_INTERNAL): no result" % what)
+    fmember, vmember = froot >= 0, vroot >= 0
+    roots, finverse, fsizes = torch.unique(froot[fmember], return_inverse=True, return_counts=True)   # ascending root
+    vinverse = torch.searchsorted(roots, vroot[vmember])                                             # every component holds a live face
+    vsizes = torch.bincount(vinverse, minlength=roots.numel())
+    if order == "size":
+        by_size = torch.sort(fsizes, descending=True, stable=True).indices                           # equal sizes: ascending root
+        rank = torch.empty_like(by_size)
+        rank[by_size] = torch.arange(by_size.numel(), device=dev)
+        roots, fsizes, vsizes, finverse, vinverse = roots[by_size], fsizes[by_size], vsizes[by_size], rank[finverse], rank[vinverse]
+    flabels, vlabels = torch.full_like(froot, -1), torch.full_like(vroot, -1)
+    flabels[fmember] = finverse.to(torch.int32)
+    vlabels[vmember] = vinverse.to(torch.int32)
+    return MeshTopology(vroot, froot, vflags, vlabels, flabels, roots, fsizes.to(torch.int64), vsizes.to(torch.int64), counts[:7])
+
+
+def select_faces(mesh, face_mask=None, vertex_mask=None):
+    """The sub-mesh of the live faces that face_mask keeps (bool / uint8 (F,), None: all) and whose three corners vertex_mask keeps
+    (bool / uint8 (M,), None: all), on the device (ovg_mesh_select): one output vertex per vertex a kept face names, in ascending input
+    index; the kept faces in input order with their corners renumbered. Called without a mask it drops the faces that are not live
+    (an index outside the mesh, a repeated index, a vertex with a non-finite coordinate) and the vertices nothing names.
+
+    -> MeshSubset: normals, colours and pixel_index gathered through source_index; transform, extrinsic and scene_scale passed through
+    unchanged, so the writers, render_mesh, simplify_mesh and smooth_mesh take it as it is. Exactly one device -> host synchronisation
+    (the two counts). A mesh without vertices or without faces returns an empty mesh without a launch. CPU tensors raise OvgError."""
+    what = "select_faces"
+    if not isinstance(mesh, Mesh):
+        raise ValueError("%s: expected a Mesh" % what)
+    M0 = 0 if mesh.vertices is None else int(mesh.vertices.shape[0])
+    F0 = 0 if mesh.faces is None else int(mesh.faces.shape[0])
+    face_mask, vertex_mask = _mesh_mask(what, "face_mask", face_mask, F0), _mesh_mask(what, "vertex_mask", vertex_mask, M0)
+    vert, faces, M, F, dev = _mesh_arrays(what, mesh, face_mask, vertex_mask)
+    nrm, col, pix = mesh.normals, mesh.colors, getattr(mesh, "pixel_index", None)
+
+    def result(v, f, src, fidx):
+        return MeshSubset(v, f, None if nrm is None else nrm.reshape(M, 3)[src], None if col is None else col.reshape(M, 3)[src], mesh.transform,
+                          mesh.extrinsic, mesh.scene_scale, src, fidx, None if pix is None else pix.reshape(M)[src])
+    Mo = Fo = 0
+    if vert is not None:
+        ws = torch.empty(ops.mesh_select_workspace_bytes(M, F), device=dev, dtype=torch.uint8)
+        count = torch.empty(2, device=dev, dtype=torch.int64)
+        args = dict(vertices=vert, faces=faces, ws=ws, face_keep=None if face_mask is None else face_mask.reshape(F).to(torch.uint8).contiguous(),
+                    vertex_keep=None if vertex_mask is None else vertex_mask.reshape(M).to(torch.uint8).contiguous(), out_count=count)
+        ops.mesh_select(ops.L.MSEL_COUNT, **args)
+        Mo, Fo = (int(c) for c in count.cpu().tolist())                                              # the one synchronisation
+    out_v, out_f = torch.empty(Mo, 3, device=dev, dtype=torch.float32), torch.empty(Fo, 3, device=dev, dtype=torch.int32)
+    src, fidx = torch.empty(Mo, device=dev, dtype=torch.int64), torch.empty(Fo, device=dev, dtype=torch.int64)
+    if Fo:
+        ops.mesh_select(ops.L.MSEL_SCATTER, vertex_capacity=Mo, face_capacity=Fo, out_vertices=out_v, source_index=src, out_faces=out_f,
+                        face_index=fidx, **args)
+    return result(out_v, out_f, src, fidx)
+
+
+def remove_small_components(mesh, min_faces=None, rel_faces=None, keep_largest=None):
+    """A Mesh without its detached pieces (mesh_topology followed by select_faces): the shells a fused volume keeps where a few lattice
+    points survived carving, the islands map_edges cut loose from a grid mesh. Exactly one of the three must be given: min_faces (a
+    positive integer: the components with at least that many live faces stay), rel_faces (a float in (0, 1]: those with at least
+    rel_faces x the mesh's live faces), keep_largest=True (the component with the most live faces alone, equal counts going to the
+    lowest root). Components are mesh_topology's: vertex connectivity. -> MeshSubset, faces and vertices in input order."""
+    import math
+    what = "remove_small_components"
+    if keep_largest is not None and not isinstance(keep_largest, bool):
+        raise ValueError("%s: keep_largest must be True, False or None, got %r" % (what, keep_largest))
+    if (min_faces is not None) + (rel_faces is not None) + bool(keep_largest) != 1:
+        raise ValueError("%s: give exactly one of min_faces, rel_faces and keep_largest" % what)
+    if min_faces is not None and (isinstance(min_faces, bool) or not isinstance(min_faces, int) or min_faces < 1):
+        raise ValueError("%s: min_faces must be a positive integer, got %r" % (what, min_faces))
+    if rel_faces is not None:
+        if isinstance(rel_faces, bool) or not isinstance(rel_faces, (int, float)) or not (math.isfinite(rel_faces) and 0.0 < rel_faces <= 1.0):
+            raise ValueError("%s: rel_faces must be a float in (0, 1], got %r" % (what, rel_faces))
+    topo = mesh_topology(mesh, order="size")
+    if topo.num_components == 0:
+        return select_faces(mesh, face_mask=torch.zeros_like(topo.face_root, dtype=torch.bool))
+    if keep_largest:
+        keep = topo.face_labels == 0
+    else:
+        least = float(min_faces) if min_faces is not None else float(rel_faces) * topo.live_faces
+        keep = (topo.face_labels >= 0) & (topo.face_sizes[topo.face_labels.clamp_min(0).long()].double() >= least)
+    return select_faces(mesh, face_mask=keep)
+
+
+MESH_NORMALS = ("recompute", "keep", None)
+
+
+def _smooth(what, mesh, iterations, lam, mu, fix_boundary, fixed, want_normals):
+    """-> (vertices, normals or None) of ovg_mesh_smooth on the mesh, or None for a mesh without vertices or faces."""
+    M0 = 0 if not isinstance(mesh, Mesh) or mesh.vertices is None else int(mesh.vertices.shape[0])
+    fixed = _mesh_mask(what, "fixed", fixed, M0)
+    vert, faces, M, F, dev = _mesh_arrays(what, mesh, fixed)
+    if vert is None:
+        return None
+    out_v = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    out_n = torch.empty(M, 3, device=dev, dtype=torch.float32) if want_normals else None
+    status = torch.empty(1, device=dev, dtype=torch.int64)
+    ws = torch.empty(ops.mesh_smooth_workspace_bytes(M, F), device=dev, dtype=torch.uint8)
+    ops.mesh_smooth(vert, faces, ws, iterations, lam, mu, out_v, status, fixed=None if fixed is None else fixed.reshape(M).to(torch.uint8).contiguous(),
+                    fix_boundary=fix_boundary, out_normals=out_n)
+    if iterations and int(status.cpu()) & ops.L.MSM_NONFINITE:                                       # the one synchronisation
+        raise ValueError("%s: a vertex left the finite float32 range (OVG_MSM_NONFINITE)" % what)
+    return out_v, out_n
+
+
+def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, fixed=None, normals="recompute"):
+    """Laplacian / Taubin smoothing of a Mesh on the device (ovg_mesh_smooth; tests/meshops_twin.py restates the rule bit for bit).
+    Every iteration moves each movable vertex by lam towards the mean of its neighbours and then, when mu != 0, by mu (negative: away
+    from it) -- Taubin's pair, which takes the noise out without the shrinking of the plain Laplacian (mu = 0). The neighbours of a
+    vertex are the other two corners of every live face that names it, so a neighbour across a manifold edge counts twice and the mean
+    is the umbrella mean; duplicated faces and non-manifold edges weigh in by their multiplicity. The sums run in integers on a 2^30
+    grid that is laid over the mesh anew in every step: two calls, and any schedule, give identical bytes.
+
+    A vertex moves when its coordinates are finite, a live face names it, fixed (bool / uint8 (M,), optional) is 0 there and, with
+    fix_boundary (default), it ends no boundary edge; every other vertex keeps its bytes. All of that is decided on the input mesh.
+    lam in (0, 1], mu <= 0 and finite, iterations an int in [0, 1000]. normals: "recompute" (default: area-free face normals of the
+    smoothed mesh summed per vertex and normalised, (0, 0, 0) where none is usable), "keep" (the input's) or None.
+
+    -> a mesh of the input's own class with new vertices and normals, everything else shared with the input. One device -> host
+    synchronisation (the status). A mesh without vertices or without faces is returned as it is, without a launch. A vertex that
+    leaves the finite float32 range raises ValueError; CPU tensors raise OvgError: there is no CPU fallback.
+    Not in it: hole filling, edge-adjacency components, pinch-vertex detection, cotangent or area weights, quadric simplification,
+    any guarantee that smoothing keeps a mesh free of self-intersections."""
+    import copy
+    import math
+    what = "smooth_mesh"
+    if not isinstance(mesh, Mesh):
+        raise ValueError("%s: expected a Mesh" % what)
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= 1000:
+        raise ValueError("%s: iterations must be an integer in [0, 1000], got %r" % (what, iterations))
+    for name, v in (("lam", lam), ("mu", mu)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError("%s: %s must be a finite number, got %r" % (what, name, v))
+    if not 0.0 < lam <= 1.0:
+        raise ValueError("%s: lam must lie in (0, 1], got %r" % (what, lam))
+    if mu > 0.0:
+        raise ValueError("%s: mu must be <= 0, got %r" % (what, mu))
+    if not isinstance(fix_boundary, bool):
+        raise ValueError("%s: fix_boundary must be True or False, got %r" % (what, fix_boundary))
+    if not (normals is None or isinstance(normals, str)) or normals not in MESH_NORMALS:
+        raise ValueError("%s: normals must be one of %r, got %r" % (what, MESH_NORMALS, normals))
+    got = _smooth(what, mesh, iterations, float(lam), float(mu), fix_boundary, fixed, normals == "recompute")
+    out = copy.copy(mesh)
+    if got is not None:
+        out.vertices = got[0]
+        out.normals = got[1] if normals == "recompute" else (mesh.normals if normals == "keep" else None)
+    elif normals is None:
+        out.normals = None
+    return out
+
+
+def mesh_vertex_normals(mesh):
+    """Vertex normals of a Mesh from its faces, on the device (ovg_mesh_smooth with no iteration): per live face the unit normal
+    (pb - pa) x (pc - pa) in float64, summed per vertex in integers (order-free) and normalised; (0, 0, 0) for a vertex without a
+    usable face. -> f32 (M, 3) device tensor; an empty (0, 3) or all-zero tensor for a mesh without vertices or faces."""
+    what = "mesh_vertex_normals"
+    if not isinstance(mesh, Mesh):
+        raise ValueError("%s: expected a Mesh" % what)
+    got = _smooth(what, mesh, 0, 0.5, 0.0, False, None, True)
+    if got is None:
+        M = 0 if mesh.vertices is None else int(mesh.vertices.shape[0])
+        return torch.zeros(M, 3, device=mesh.vertices.device if mesh.vertices is not None else "cpu", dtype=torch.float32)
+    return got[1]
