@@ -6,6 +6,8 @@ guarded()            an output view inside a larger byte buffer pre-filled with 
 poison_*()           large finite values of alternating sign in the padding a kernel must not depend on
 elementwise_budget() |got - ref| <= u_out |ref| + c u_acc mag for EVERY element (gpu_selftest.report gates the tensor-global maximum only)
 *_budget()           the constants c, each derived from the rounding points of its kernel (never fitted to a kernel's output)
+upsample_window()    the 16-bit roundings a bilinear kernel may hold per element; dpt_tail_budget() carries them through the fused output stage
+                     (test_dpt_tail_budget_host.py); camera_tables_budget() for ovg_camera_tables (test_camera_tables_budget_host.py)
 """
 import math
 
@@ -283,3 +285,342 @@ def qk_norm_rope_error(z, ez, w, b, eps, pos, cos, sin, scale=1.0):
         a, b_ = t.chunk(2, dim=-1)
         return torch.cat((one_axis(a, pos[..., 0]), one_axis(b_, pos[..., 1])), dim=-1)
     return scale * (rope_abs(ey) + MARGIN * 3 * U_ACC * rope_abs(y.abs()))
+
+
+# ---- bilinear resize (align_corners = True) ---------------------------------------------------
+# The specification both kernels document (csrc/ovg_head.hip upsample_kernel, csrc/ovg_dpt_tail.h xgeo / ygeo) and ATen implements:
+#   s = (in - 1) / (out - 1) an f32 quotient, f = s o an f32 product, i0 = min(int(f), in - 1), i1 = i0 + (i0 < in - 1), l = f - i0 (exact:
+#   f < 2^24 and i0 = floor(f) unless clamped, where l stays tiny), value = (1-ly)(1-lx) a + (1-ly) lx b + ly (1-lx) c + ly lx d + table.
+# The coordinate arithmetic is part of the specification: a float64 s o differs from the f32 product by up to u f, which moves the weights by
+# (in - 1) u -- orders of magnitude more than the interpolation's own rounding.
+# `fused` evaluates a DEVIATION from it, exactly: `fx = sx * oc; lx = fx - x0` contracted into one multiply-subtract, l' = fl(s o - i0) with
+# the product unrounded (the default -ffp-contract=fast would permit it; a product of two f32 values and its difference with an integer
+# < 2^24 are exact in float64). It moves l by up to half an ulp of f, and the window below is sharp enough to tell the two apart: the host
+# test uses it as a mutant, and on the MI355X ovg_upsample held the plain form on every one of 1.1e7 elements of a 148 -> 296 map while the
+# fused form left 0.3 % (bf16) / 1.8 % (f16) of them outside the window.
+def _axis_spec(n_in, n_out, fused):
+    s = torch.tensor(float(n_in - 1), dtype=torch.float32) / torch.tensor(float(n_out - 1), dtype=torch.float32)
+    o = torch.arange(n_out, dtype=torch.float32)
+    f = s * o
+    i0 = f.to(torch.int64).clamp_max(n_in - 1)
+    i1 = i0 + (i0 < n_in - 1).to(torch.int64)
+    l = ((s.double() * o.double() - i0.double()).float() if fused else f - i0.float()).double()
+    return i0, i1, l
+
+
+def bilinear_spec(x, OH, OW, pos=None, fused=(False, False)):
+    """x [n, H, W, C] float64 (the values of the stored inputs), pos = (pos_x [OW, C/2], pos_y [OH, C/2]) or None ->
+    (up, mag) [n, OH, OW, C] float64: the interpolated value + table entry with the weights of the specification above, the four taps and the
+    table combined in float64, and its magnitude sum w |tap| + |table|. fused = (y, x): the contracted form of l per axis (a mutant, see above)."""
+    x = x.double()
+    n, H, W, C = x.shape
+    y0, y1, ly = _axis_spec(H, OH, fused[0])
+    x0, x1, lx = _axis_spec(W, OW, fused[1])
+    ly, lx = ly.view(1, OH, 1, 1), lx.view(1, 1, OW, 1)
+    up, mag = torch.zeros(n, OH, OW, C, dtype=torch.float64), torch.zeros(n, OH, OW, C, dtype=torch.float64)
+    for yi, wy in ((y0, 1.0 - ly), (y1, ly)):
+        for xi, wx in ((x0, 1.0 - lx), (x1, lx)):
+            tap = x[:, yi][:, :, xi]
+            up += wy * wx * tap
+            mag += wy * wx * tap.abs()
+    if pos is not None:
+        half = C // 2
+        px, py = pos[0].double()[None, None, :, :], pos[1].double()[None, :, None, :]
+        up[..., :half] += px
+        up[..., half:] += py
+        mag[..., :half] += px.abs()
+        mag[..., half:] += py.abs()
+    return up, mag
+
+
+# The f32 value a kernel holds before its 16-bit store is within C_UP u_acc mag of `up`:
+#   both kernels: hx = fl(1 - lx), hy = fl(1 - ly): one rounding each (lx, ly themselves are exact, see above)
+#   ovg_dpt_tail.h phase 1: w00 = fl(hy hx) carries 3 roundings, w01 = fl(hy lx) and w10 = fl(ly hx) 2, w11 = fl(ly lx) 1 -> at most 3 on
+#     sum w |tap|; then four FMAs o = fma(w, tap, o) starting from the table entry, one rounding each on a partial sum <= mag -> 4.  Total 7.
+#   upsample_kernel: hy (hx a + lx b) + ly (hx c + lx d) + table: hx a: hx's rounding + the product's (2), lx b: 1, their sum 1 -> 3 on the
+#     inner sum; times hy: its rounding + the product's -> 5; the outer sum 1 -> 6; + table 1 -> 7 (a contraction to FMAs only removes roundings).
+C_UP = MARGIN * 7
+
+
+def round16(v, mode):
+    """float64 -> the nearest value of the 16-bit format, ties to even, as float64, WITHOUT a detour through f32 (a double rounding could
+    cross a tie): the quantum is 2^(e - bits) for |v| in [2^(e-1), 2^e), not below the format's subnormal spacing. Monotone."""
+    bits, qmin = {"bf16": (8, -133), "f16": (11, -24)}[mode]
+    v = v.double()
+    _, e = torch.frexp(v)
+    q = torch.ldexp(torch.ones_like(v), (e - bits).clamp_min(qmin))
+    return torch.round(v / q) * q
+
+
+def upsample_window(x, OH, OW, pos, mode):
+    """The 16-bit map a correct kernel may hold. -> dict: up / mag (the specification, float64), r16 = round16(up) (what the reference
+    chain continues with), lo16 <= hi16 (the roundings of the two ends of [up - e_up, up + e_up],
+    e_up = C_UP u_acc mag: rounding is monotone, so the kernel's value lies between them), delta = max(hi16 - r16, r16 - lo16) (zero
+    wherever both ends round to r16: there the kernel must hold exactly r16), window = lo16 != hi16."""
+    up, mag = bilinear_spec(x, OH, OW, pos)
+    e_up = C_UP * U_ACC * mag
+    r16, lo16, hi16 = round16(up, mode), round16(up - e_up, mode), round16(up + e_up, mode)
+    return {"up": up, "mag": mag, "r16": r16, "lo16": lo16, "hi16": hi16, "delta": torch.maximum(hi16 - r16, r16 - lo16), "window": lo16 != hi16}
+
+
+def check_upsampled_map(name, got, win):
+    """The strict gate of a 16-bit upsampled map: lo16 <= got <= hi16 for every element, i.e. bit-equal to the reference outside the
+    rounding window and one of the admissible roundings inside it. -> (share of elements inside the window, share that differs from r16)."""
+    got = got.detach().double().cpu()
+    bad = ~((got >= win["lo16"]) & (got <= win["hi16"]))
+    differs = got != win["r16"]
+    share, dshare = float(win["window"].double().mean()), float(differs.double().mean())
+    print("[%s] %-52s window holds %.3f%% of the map, %d elements differ from the reference's rounding, %d outside the window" % (
+        "FAIL" if bool(bad.any()) else "PASS", name + ".window", 100 * share, int(differs.sum()), int(bad.sum())), flush=True)
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad.flatten())[0])
+        raise AssertionError("%s: %d of %d map elements are not an admissible rounding; first @flat %d got=%.9g lo=%.9g hi=%.9g up=%.12g" % (
+            name, int(bad.sum()), bad.numel(), i, float(got.flatten()[i]), float(win["lo16"].flatten()[i]), float(win["hi16"].flatten()[i]),
+            float(win["up"].flatten()[i])))
+    STATS["numeric"] += 1
+    return share, dshare
+
+
+# ---- the fused DPT output stage (csrc/ovg_dpt_tail.h; the same arithmetic as ovg_upsample -> ovg_conv -> ovg_dpt_out) -----------
+# up16 (above) -> h = relu(conv3x3(up16, w1) + b1) -> o = w2 h + b2 -> val = exp(o) | sign(o) expm1(|o|), conf = 1 + exp(o).
+#  * hidden layer: the kernel's map differs from r16 by at most delta per element (zero outside the window), which the convolution carries
+#    as conv(|w1|, delta); its own f32 accumulation over K = 9 x 128 exact products + the bias is the GEMM bound on
+#    mag_h = conv(|w1|, |r16|) + |b1|:  e_h = conv(|w1|, delta) + gemm_c(1152) u_acc mag_h.  (|r16| <= the kernel's |map| + delta: second order.)
+#  * ReLU is 1-Lipschitz: e_h passes unchanged.
+#  * output layer, plain f32: 32 products (one rounding each unless fused) and the bias, summed as 8 FMAs per lane, a 4-lane exchange and the
+#    bias (kernel), or sequentially (dpt_out_kernel): a term passes through at most 32 additions in any order -> 33 on mag_o = |w2| h + |b2|:
+#    e_o = |w2| e_h + C_OUT u_acc mag_o.
+#  * activations: exp(o + d) - exp(o) = exp(o) expm1(d); sign(o) expm1(|o|) has the derivative exp(|o|) and is odd, and expm1 is
+#    superadditive, so across zero too |f(o + d) - f(o)| <= exp(|o|) expm1(|d|). The confidence 1 + exp(o) carries the factor on exp(o) ALONE:
+#    a low-confidence pixel (exp(o) << 1) gets a budget of expm1(e_o) exp(o) + one rounding of 1 + exp(o), not a share of the 1.
+#  * expf / expm1f: the device library documents <= 3 ulp = 6 u_acc relative for both (OpenCL full-profile bounds, which it meets); the final
+#    f32 rounding (val: inside those 3 ulp; conf: the addition) is elementwise_budget's u_out |ref|.
+C_OUT = MARGIN * 33
+C_EXP = MARGIN * 6
+
+
+def conv3x3_nhwc(x, w):
+    """x [n, H, W, C] float64, w [co, 9 C] taps-major (tap = 3 ky + kx, as ovg_conv orders them) -> the zero-padded 3 x 3 convolution
+    [n, H, W, co], as nine matrix products."""
+    n, H, W, C = x.shape
+    xp = torch.zeros(n, H + 2, W + 2, C, dtype=torch.float64)
+    xp[:, 1:-1, 1:-1] = x
+    y = torch.zeros(n, H, W, w.shape[0], dtype=torch.float64)
+    for ky in range(3):
+        for kx in range(3):
+            y += xp[:, ky:ky + H, kx:kx + W] @ w[:, (3 * ky + kx) * C:(3 * ky + kx + 1) * C].double().t()
+    return y
+
+
+def dpt_tail_budget(x, OH, OW, pos, w1, b1, w2, b2, activation, mode):
+    """x [n, H, W, 128] / w1 [>= 32, 1152] (the 16-bit values), b1 [32] or None, w2 [od, 32], b2 [od] -> dict with the float64 chain
+    (val [n, OH, OW, od - 1], conf [n, OH, OW]) and, per output, what elementwise_budget takes: *_mag, *_c, *_extra; + the window dict."""
+    win = upsample_window(x, OH, OW, pos, mode)
+    w1 = w1[:32].double()
+    b1 = torch.zeros(32, dtype=torch.float64) if b1 is None else b1.double()
+    w2, b2 = w2.double(), b2.double()
+    h = conv3x3_nhwc(win["r16"], w1) + b1
+    mag_h = conv3x3_nhwc(win["r16"].abs(), w1.abs()) + b1.abs()
+    e_h = conv3x3_nhwc(win["delta"], w1.abs()) + gemm_c(9 * 128, mode) * U_ACC * mag_h
+    hr = torch.relu(h)
+    o = hr @ w2.t() + b2
+    mag_o = hr @ w2.abs().t() + b2.abs()
+    e_o = e_h @ w2.abs().t() + C_OUT * U_ACC * mag_o
+    ov, oc = o[..., :-1], o[..., -1]
+    out = {"win": win, "o": o, "e_o": e_o, "c": C_EXP}
+    if activation == "exp":
+        out["val"], out["val_mag"] = torch.exp(ov), torch.exp(ov)
+    else:
+        out["val"], out["val_mag"] = torch.sign(ov) * torch.expm1(ov.abs()), torch.exp(ov.abs())
+    out["val_extra"] = out["val_mag"] * torch.expm1(e_o[..., :-1])
+    out["conf"], out["conf_mag"] = 1.0 + torch.exp(oc), torch.exp(oc)
+    out["conf_extra"] = out["conf_mag"] * torch.expm1(e_o[..., -1])
+    return out
+
+
+def check_dpt_tail(name, val, conf, B, quiet=False):
+    """Both outputs of the stage against dpt_tail_budget's result, every element. -> the worst used fraction of the two."""
+    a = elementwise_budget(name + ".val", val, B["val"], B["val_mag"], U_OUT["f32"], B["c"], extra=B["val_extra"], quiet=quiet)
+    b = elementwise_budget(name + ".conf", conf, B["conf"], B["conf_mag"], U_OUT["f32"], B["c"], extra=B["conf_extra"], quiet=quiet)
+    return max(a, b)
+
+
+DPT_TAIL_GATE = {"bf16": 4e-3, "f16": 5e-4}      # gpu_selftest.test_heads' global gates of the stage (max error / tensor maximum)
+
+# The shapes of the stage that the host test (the f32 twin and its mutants against the budget) and the GPU test (the kernels) share.
+# n = 0: as many images as give every workgroup two or three tiles with a partial last round (the GPU test takes it from the device; the
+# budget does not depend on it, the host test runs 3). Tiles are 16 rows x 14 columns of output. Ratios (in - 1) / (out - 1) are non-dyadic
+# where the shape is free: a dyadic ratio puts exact ties ((a + b) / 2 of two 16-bit values) into the window.
+#               n  H   W   OH  OW  od  activation  tables  b1     conf_ramp
+DPT_TAIL_CASES = {
+    "persist_exp_pos":  (0, 9, 11, 33, 29, 2, "exp", True, True, False),       # 3 x 3 tiles per image, the last row / column of tiles one pixel wide
+    "persist_exp":      (0, 9, 11, 33, 29, 2, "exp", False, True, False),
+    "persist_inv_pos":  (0, 9, 11, 33, 29, 4, "inv_log", True, True, False),
+    "persist_inv":      (0, 9, 11, 33, 29, 4, "inv_log", False, True, False),
+    "out_dim3":         (2, 7, 6, 20, 19, 3, "inv_log", True, True, False),
+    "no_b1":            (2, 7, 6, 20, 19, 2, "exp", True, False, False),
+    "oh2":              (2, 5, 4, 2, 31, 4, "inv_log", True, True, False),
+    "ow2":              (2, 4, 5, 35, 2, 2, "exp", True, True, False),
+    "whole_tiles":      (1, 8, 7, 32, 28, 4, "inv_log", True, True, False),    # OH = 16 k, OW = 14 k (k + 1: the persist shapes)
+    "src_1xW":          (2, 1, 6, 18, 15, 4, "inv_log", False, True, False),   # sy = 0: dy = 0 for every row
+    "src_Hx1":          (2, 7, 1, 17, 16, 2, "exp", True, True, False),        # sx = 0: x1 = x0 for every column
+    "downscale":        (2, 20, 23, 15, 17, 4, "inv_log", True, True, False),  # an output smaller than the source: accepted, must equal the reference
+    "conf_ramp":        (1, 7, 6, 20, 19, 2, "exp", False, True, True),        # confidences from below 1 + 1e-2 to above 10 (asserted on the reference)
+}
+
+
+def dpt_tail_inputs(case, mode, n=None):
+    """-> dict of CPU tensors for a DPT_TAIL_CASES entry: x [n, H, W, 128] and w1 [32, 1152] in the 16-bit dtype, b1 / w2 / b2 f32,
+    pos (pos_x [OW, 64], pos_y [OH, 64]) f32 or None. conf_ramp: a spatial ramp in x and a scaled confidence row of w2 / b2 spread exp(o)
+    over three decades (plain randn weights leave every confidence near 2, where a flush of small exp(o) to zero goes unseen)."""
+    n0, H, W, OH, OW, od, act, pos, has_b1, ramp = DPT_TAIL_CASES[case]
+    n = n if n is not None else (n0 if n0 else 3)
+    dt = {"bf16": torch.bfloat16, "f16": torch.float16}[mode]
+    g = torch.Generator().manual_seed(1000 + sorted(DPT_TAIL_CASES).index(case))
+    x = torch.randn(n, H, W, 128, generator=g)
+    w1 = torch.randn(32, 9 * 128, generator=g) * (9 * 128) ** -0.5
+    b1 = torch.randn(32, generator=g) * 0.3
+    w2, b2 = torch.randn(od, 32, generator=g) * 0.2, torch.randn(od, generator=g) * 0.1
+    ps = (torch.randn(OW, 64, generator=g) * 0.1, torch.randn(OH, 64, generator=g) * 0.1) if pos else None
+    if ramp:
+        x = 0.5 * x + torch.linspace(-2.0, 2.0, W).view(1, 1, W, 1) * torch.sign(torch.randn(128, generator=g))
+        w2[-1] *= 3.0
+        b2[-1] = 0.3
+    return {"x": x.to(dt), "w1": w1.to(dt), "b1": b1 if has_b1 else None, "w2": w2, "b2": b2, "pos": ps, "OH": OH, "OW": OW, "act": act, "od": od, "n": n}
+
+
+# ---- ovg_camera_tables (csrc/ovg_camtab.hip) -------------------------------------------------
+# enc [B, Sc, 9] = (t / scale, quaternion xyzw, fov_h, fov_w) of the selected cameras relative to the first, a fixed short chain of f32
+# operations on exact inputs E_r = [R_r | t_r], E_0; u = u_acc, x MARGIN throughout:
+#  * c = -R_0^T t_0: 3 products, 2 sums -> within 3 u m0, m0_j = sum_k |R_0[k][j]| |t_0[k]| (and |c_j| <= m0_j)
+#  * t_i = sum_j E[i][j] c_j + E[i][3]: 4 terms (4) + the inherited 3 -> e_t = 7 u mag_t, mag_t_i = sum_j |R[i][j]| m0_j + |t_r[i]|
+#  * scale = max(mean_r |t(r) - t(0)|, 1e-6): the norm and the clamp are 1-Lipschitz, so it moves by at most mean_r sum_i (e_t_i(r) + e_t_i(0))
+#    + the norm's own roundings (difference, squares, their sum halved by the root, the root: 4 u dist) + the sum over the cameras (a lane adds
+#    ceil(Sc / 256) values, then an 8-level tree) + the division: e_s. t / scale then carries (e_t + |t / scale| e_s) / (scale - e_s) + the division.
+#    With all cameras at one position scale is the clamp, 1e-6, and e_t / 1e-6 is the honest conditioning of that output.
+#  * R = R_r R_0^T: 3 exact-input products -> e_R = 3 u mR, mR = |R_r| |R_0|^T. raw_b = 1 +- R00 +- R11 +- R22: three additions on a
+#    magnitude <= 1 + |R00| + |R11| + |R22| + the three e_R: e_raw; q_best = sqrt(raw_best) >= 1 (the four raw values sum to 4):
+#    relative rho = e_raw / (2 raw_best) + u. The picked candidate row: q_best^2 (2 rho + u) or R[a][b] +- R[b][a] (2 max e_R + u (|Rab| + |Rba|)),
+#    divided by den = 2 max(q_best, 0.1) >= 2 (relative rho + u): every component within (2 max e_R + 2 u max|R|) / den + |q| (3 rho + 2 u).
+#    (The branch choice and the sign normalisation are discontinuous: the test keeps its cameras away from ties and from w = 0 and asserts so.)
+#  * fov = 2 atanf((size / 2) / f): the quotient's rounding moves atan(a) by a / (1 + a^2) u <= atan(a) u; atanf within 5 ulp (the OpenCL bound
+#    the device library meets) -> 11 u |fov|.
+# tables: emb = pose_w enc + pose_b, 9 FMAs and a sum (10 u on its magnitude) + |pose_w| e_enc; row = adapt_w emb + adapt_b on the exact-f32
+# matrix pipe: gemm_c(1024, "f32") u on its magnitude + |adapt_w| e_emb. Views without a camera hold adapt_b exactly.
+def camera_tables_budget(ext, intr, idx, hw, pose_w, pose_b, adapt_w, adapt_b):
+    """ext [B, S, 3, 4], intr [B, S, 3, 3] f32, idx: list of views, pose_w [G * 1024, 9], pose_b [G * 1024], adapt_w [G, 1024, 1024], adapt_b [G, 1024]
+    -> dict: enc [B, Sc, 9], e_enc (absolute), tables [G, B * S, 1024], e_tab (absolute), rows (the table rows that carry a camera), and the
+    conditions on the inputs (gap: raw_best - the runner-up, w: the quaternion's real part, es_rel: e_s / scale)."""
+    u = U_ACC
+    sel = torch.tensor(idx)
+    E, K = ext.double()[:, sel], intr.double()[:, sel]
+    B, Sc = E.shape[:2]
+    G = adapt_b.shape[0]
+    R, t = E[..., :3], E[..., 3]
+    R0, t0 = R[:, :1], t[:, :1]
+    c = -(R0.transpose(-1, -2) @ t0.unsqueeze(-1)).squeeze(-1)                       # [B, 1, 3]
+    m0 = (R0.abs().transpose(-1, -2) @ t0.abs().unsqueeze(-1)).squeeze(-1)
+    tr = (R @ c.unsqueeze(-1)).squeeze(-1) + t
+    e_t = MARGIN * 7 * u * ((R.abs() @ m0.unsqueeze(-1)).squeeze(-1) + t.abs())      # [B, Sc, 3]
+    if Sc > 1:
+        dist = (tr - tr[:, :1]).norm(dim=-1)[:, 1:]
+        scale = dist.mean(1, keepdim=True).clamp_min(1e-6)                           # [B, 1]
+        depth = (Sc + 255) // 256 + 8
+        e_s = (e_t.sum(-1)[:, 1:] + e_t.sum(-1)[:, :1]).mean(1, keepdim=True) + MARGIN * (4 + depth + 1) * u * dist.mean(1, keepdim=True)
+        tout = tr / scale.unsqueeze(-1)
+        e_tout = (e_t + tout.abs() * e_s.unsqueeze(-1)) / (scale - e_s).clamp_min(1e-300).unsqueeze(-1) + MARGIN * u * tout.abs()
+        es_rel = float((e_s / scale).max())
+    else:
+        tout, e_tout, es_rel = tr, e_t, 0.0
+    Rr = R @ R0.transpose(-1, -2)
+    e_R = MARGIN * 3 * u * (R.abs() @ R0.abs().transpose(-1, -2))
+    d0, d1, d2 = Rr[..., 0, 0], Rr[..., 1, 1], Rr[..., 2, 2]
+    raw = torch.stack([1 + d0 + d1 + d2, 1 + d0 - d1 - d2, 1 - d0 + d1 - d2, 1 - d0 - d1 + d2], -1)
+    top = raw.topk(2, dim=-1).values
+    e_raw = MARGIN * 3 * u * (1 + d0.abs() + d1.abs() + d2.abs()) + e_R[..., 0, 0] + e_R[..., 1, 1] + e_R[..., 2, 2]
+    rho = e_raw / (2 * top[..., 0]) + MARGIN * u
+    from omnivggt_official_amd import camera_math
+    q = camera_math.rotation_to_quaternion(Rr)
+    den = 2 * torch.sqrt(top[..., 0]).clamp_min(0.1)
+    e_q = ((2 * e_R.amax((-1, -2)) + MARGIN * 2 * u * Rr.abs().amax((-1, -2))) / den).unsqueeze(-1) + q.abs() * (3 * rho + MARGIN * 2 * u).unsqueeze(-1)
+    fov = torch.stack([2 * torch.atan((hw[0] / 2.0) / K[..., 1, 1]), 2 * torch.atan((hw[1] / 2.0) / K[..., 0, 0])], -1)
+    enc = torch.cat([tout, q, fov], -1)
+    e_enc = torch.cat([e_tout, e_q, MARGIN * 11 * u * fov.abs()], -1)
+    S = ext.shape[1]
+    tables = adapt_b.double().unsqueeze(1).repeat(1, B * S, 1)
+    e_tab = torch.zeros_like(tables)
+    rows = (torch.arange(B).unsqueeze(1) * S + sel.unsqueeze(0)).reshape(-1)
+    ef, ee = enc.reshape(-1, 9), e_enc.reshape(-1, 9)
+    for g_ in range(G):
+        pw, pb = pose_w[g_ * 1024:(g_ + 1) * 1024].double(), pose_b[g_ * 1024:(g_ + 1) * 1024].double()
+        aw, ab = adapt_w[g_].double(), adapt_b[g_].double()
+        emb = ef @ pw.t() + pb
+        e_emb = ee @ pw.abs().t() + MARGIN * 10 * u * (ef.abs() @ pw.abs().t() + pb.abs())
+        tables[g_, rows] = emb @ aw.t() + ab
+        e_tab[g_, rows] = e_emb @ aw.abs().t() + gemm_c(1024, "f32") * u * (emb.abs() @ aw.abs().t() + ab.abs())
+    return {"enc": enc, "e_enc": e_enc, "tables": tables, "e_tab": e_tab, "rows": rows, "gap": float((top[..., 0] - top[..., 1]).min()),
+            "w": float(q[..., 3].min()), "es_rel": es_rel}
+
+
+def camera_case(B, S, seed, position=None, spread=2.0, max_angle=0.7, flips=False):
+    """-> (ext [B, S, 3, 4], intr [B, S, 3, 3]) f32: cameras with rotations of at most max_angle rad about random axes (so that the rotation
+    relative to any of them stays below 2 max_angle: the quaternion's real part away from zero, its branch away from a tie) at random
+    positions (or all at `position`), fx != fy."""
+    g = torch.Generator().manual_seed(seed)
+    axis = torch.nn.functional.normalize(torch.randn(B, S, 3, generator=g, dtype=torch.float64), dim=-1)
+    ang = (torch.rand(B, S, 1, generator=g, dtype=torch.float64) * 2 - 1) * max_angle
+    if flips:                # views 1..3: 170 degrees about x, y, z seen from an almost unrotated view 0 -> the three other quaternion branches
+        ang[:, 0] = 0.05
+        ang[:, 1:4] = math.radians(170.0)
+        axis[:, 1:4] = torch.eye(3, dtype=torch.float64)
+    qv, qw = axis * torch.sin(ang / 2), torch.cos(ang / 2)
+    x, y, z = qv.unbind(-1)
+    w = qw.squeeze(-1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                     2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).reshape(B, S, 3, 3)
+    Cw = torch.randn(B, S, 3, generator=g, dtype=torch.float64) * spread if position is None else torch.tensor(position, dtype=torch.float64).expand(B, S, 3)
+    t = -(R @ Cw.unsqueeze(-1))
+    intr = torch.zeros(B, S, 3, 3)
+    intr[..., 0, 0] = 400 + 300 * torch.rand(B, S, generator=g)
+    intr[..., 1, 1] = 250 + 100 * torch.rand(B, S, generator=g)
+    intr[..., 0, 2], intr[..., 1, 2], intr[..., 2, 2] = 259.0, 196.0, 1.0
+    return torch.cat([R, t], -1).float(), intr
+
+
+#                          B  S    selected views                       camera_case arguments
+CAMERA_CASES = {
+    "branches_fx_ne_fy": (1, 5, [0, 1, 2, 3, 4], dict(flips=True)),                         # every quaternion branch; non-square frame, fx != fy (all cases)
+    "subset_two_batches": (2, 5, [1, 0, 4], dict()),
+    "one_camera": (1, 4, [2], dict()),                                                       # Sc = 1: no scale
+    "coincident_at_origin": (1, 4, [0, 1, 2, 3], dict(position=(0.0, 0.0, 0.0))),            # every distance exactly 0: the 1e-6 clamp, t = 0 / 1e-6 = 0
+    "coincident_near_origin": (2, 3, [2, 0, 1], dict(position=(0.004, -0.002, 0.003))),      # distances of rounding noise under the clamp
+    "Sc300": (1, 300, [(7 * i) % 300 for i in range(300)], dict()),                          # the r += 256 loops; 5 row blocks of cam_adapt_kernel, the last partial
+    "B2_Sc130": (2, 140, list(range(5, 135)), dict()),                                       # 260 camera rows: 5 row blocks, rows of batch 1 cross a block
+}
+CAMERA_HW = (392, 518)
+
+
+def camera_inputs(case):
+    B, S, idx, kw = CAMERA_CASES[case]
+    ext, intr = camera_case(B, S, 2000 + sorted(CAMERA_CASES).index(case), **kw)
+    return ext, intr, idx
+
+
+def camera_weights(G=2):
+    g = torch.Generator().manual_seed(1999)
+    return (torch.randn(G * 1024, 9, generator=g) * 0.3, torch.randn(G * 1024, generator=g) * 0.1,
+            torch.randn(G, 1024, 1024, generator=g) * 0.03, torch.randn(G, 1024, generator=g) * 0.1)
+
+
+def check_camera_tables(name, enc, tables, Bd, quiet=False):
+    """enc [B * Sc, 9] and tables [G, B * S, 1024] of a kernel against camera_tables_budget's result: the conditions on the inputs, every element
+    of both within its bound, rows without a camera exactly adapt_b. -> (used fraction of enc, of tables)."""
+    assert Bd["gap"] >= 0.1 and Bd["w"] >= 0.02 and Bd["es_rel"] <= 0.5, "%s: the cameras sit on a discontinuity of the encoding: %s" % (
+        name, {k: Bd[k] for k in ("gap", "w", "es_rel")})
+    zero = torch.zeros(())
+    a = elementwise_budget(name + ".enc", enc.reshape(Bd["enc"].shape), Bd["enc"], zero, U_OUT["f32"], 0.0, extra=Bd["e_enc"], quiet=quiet)
+    b = elementwise_budget(name + ".tables", tables, Bd["tables"], zero, U_OUT["f32"], 0.0, extra=Bd["e_tab"], quiet=quiet)
+    free = torch.ones(Bd["tables"].shape[1], dtype=torch.bool)
+    free[Bd["rows"]] = False
+    assert torch.equal(tables.detach().double().cpu()[:, free], Bd["tables"][:, free]), name + ": a view without a camera must hold adapt_b exactly"
+    return a, b

@@ -888,6 +888,10 @@ def test_upsample_edges_guarded(mode):
         # and the result by that times the difference of two neighbours (<= 2 max|x| of the channel); four products and three sums on top:
         # (8 max(H, W) + 8) u on mag = max|x| of the image's channel
         kg.elementwise_budget(tag, got, ref, mag, kg.U_OUT[mode], kg.MARGIN * (8 * max(H, W) + 8), extra=kg.f16_subnormal_floor(mode), quiet=True)
+        if mode != "f32":
+            # stricter, with the documented f32 coordinate arithmetic as the specification: bit-equal to its rounding outside the rounding
+            # window, one of the admissible roundings inside (kernel_guards.upsample_window)
+            kg.check_upsampled_map(tag, got, kg.upsample_window(x.double(), OH, OW, None, mode))
 
 
 def test_dpt_out_and_dpt_tail_small_maps_guarded():
@@ -930,9 +934,11 @@ def test_dpt_out_and_dpt_tail_small_maps_guarded():
                 gate = 4e-3 if mode == "bf16" else 5e-4           # gpu_selftest's dpt_tail gates (the 16-bit rounding of the upsampled map is inside)
                 _global("dpt_tail_%s_%s_%dx%d.val" % (act, mode, OH, OW), _val(tv.view), val, gate)
                 _global("dpt_tail_%s_%s_%dx%d.conf" % (act, mode, OH, OW), _val(tc.view).view(2, OH, OW), 1 + torch.exp(o[..., -1]), gate)
-                # global gates only: the fused kernel rounds the upsampled map to 16 bits where this reference does, but a value that sits on a
-                # rounding boundary may go the other way (one 16-bit ulp of a conv INPUT), so no per-element bound in u_acc holds
-                _global_only(2)
+                # per element too: against a float64 bilinear reference a map value on a rounding boundary may go the other way (one 16-bit
+                # ulp of a conv INPUT) and no bound in u_acc holds, but with the coordinate arithmetic the kernels document the boundary cases
+                # are a known small set (kernel_guards.upsample_window) whose ulp dpt_tail_budget carries through the stage
+                B = kg.dpt_tail_budget(x.double(), OH, OW, None, w1.double(), b1, w2, b2, act, mode)
+                kg.check_dpt_tail("dpt_tail_%s_%s_%dx%d" % (act, mode, OH, OW), _val(tv.view), _val(tc.view).view(2, OH, OW), B, quiet=True)
 
 
 def test_camera_head_every_row_block_edge_guarded():
