@@ -1799,6 +1799,18 @@ int ovg_heads_to_tokens(const ovg_heads_to_tokens_params*, void* stream);
  *   GEMM operands and the activation buffers between kernels are f32 too and the products run on the exact-f32 MFMA:
  *   no rounding point below f32 anywhere. dim must be 2048, heads 16 (head dim 128), trunk_depth <= OVG_CAMERA_MAX_TRUNK,
  *   S <= 4096. ws: caller-owned scratch of >= ovg_camera_head_workspace_bytes(S, dtype) bytes (returns -1 on bad args).
+ * Workspace layout (carve() in csrc/ovg_camhead.hip; tests/kernel_guards.py camera_ws_views restates it): nine buffers in this
+ * order, each starting on a multiple of 256 bytes from ws (sizes rounded up to 256), E = bytes per element of `dtype`:
+ *   tok  [S][2048]  f32    token_norm(tokens), written once
+ *   x    [S][2048]  f32    the residual stream, updated in place by every modulation and block
+ *   pose [S][9]     f32    the carried pose encoding, NOT activated (out holds the activated copy of every round)
+ *   part [S][32768] f32    split-K partials of the GEMM in flight, [ksplit][S][N] with ksplit * N <= 32768
+ *   xn   [S][2048]  dtype  the LayerNorm feeding the next GEMM (n1, n2, ... trunk_norm: overwritten by each)
+ *   e    [S][2048]  dtype  SiLU(embed_pose(pose)) of the round
+ *   qkv  [S][6144]  dtype  q | k | v of the block, 16 heads x 128 each
+ *   attn [S][2048]  dtype  attention output, token-major
+ *   hid  [S][8192]  dtype  GELU(fc1) of the block
+ * After the call the buffers hold the values of the last round's last block; nothing outside these ranges is written.
  * ------------------------------------------------------------------ */
 #define OVG_CAMERA_MAX_TRUNK 4
 typedef struct {

@@ -1034,6 +1034,9 @@ def test_camera_head(timing=False):
             tag = "camera_head_%s_B%d_S%d" % (name, B, S)
             report(tag + "_vs_twin", got, twin, tol_twin[name])
             report(tag + "_vs_f32_module", got, ref32, tol_mod[name])
+            for grp, sl in (("T", slice(0, 3)), ("quat", slice(3, 7)), ("fov", slice(7, 9))):      # each component group against its own maximum
+                report("%s_vs_twin.%s" % (tag, grp), got[..., sl], twin[..., sl], tol_twin[name])
+                report("%s_vs_f32_module.%s" % (tag, grp), got[..., sl], ref32[..., sl], tol_mod[name])
     if timing:
         toks = (rnd(1, 8, 1374, 2048, g=g) * 1.3).to(DEV)
         for label, fn in (("hip bf16", lambda: hip([toks], dtype=torch.bfloat16)), ("hip f32", lambda: hip([toks], dtype=torch.float32)),

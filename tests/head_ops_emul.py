@@ -89,3 +89,57 @@ def camera_head(tokens, W, dtype, iters=4, ws=None):
         pose = delta if pose is None else pose + delta
         outs.append(torch.cat([pose[:, :7], F.relu(pose[:, 7:])], dim=-1))
     return torch.stack(outs, 0)
+
+
+def camera_head_buffers(tokens, W, dtype, iters=1, hooks=None, pb1_slots=None):
+    """camera_head above, split where the kernel stores: -> dict of what an ovg_camera_head call leaves behind (tok, x, pose, xn, e, qkv,
+    attn, hid of the LAST round and block, out [iters, S, 9]) + x0 / xmid (the residual stream after the modulation / after the attention
+    update of the last round's last block). hooks: {name: callable} replacing one piece (tests plant defects through it):
+    lin(name, x, w, b), ln(name, x, w, b, eps), attn(q, k, v) -> [nh, S, hd], gelu(name, z), modulate(ln, shift, scale, gate, tok), carry(pose), pb2(hb, w2, b2).
+    pb1_slots: the split-K factor of the pose branch's GEMM: its partials are kept as part [slots, S, 1024] and folded as the kernel folds
+    them; None: one product, the arithmetic of camera_head above (test_camera_head_budget_host.py pins the two equal)."""
+    hooks = hooks or {}
+    f = lambda t: t.float()
+    rnd = lambda t: t.to(dtype).float()
+    lin = hooks.get("lin", lambda name, x, w, b: x @ f(w).t() + f(b))
+    ln = hooks.get("ln", lambda name, x, w, b, eps: F.layer_norm(x, (x.shape[-1],), None if w is None else f(w), None if b is None else f(b), eps))
+    attn_fn = hooks.get("attn", lambda q, k, v: torch.softmax(q @ k.transpose(1, 2) * q.shape[-1] ** -0.5, dim=-1) @ v)
+    gelu = hooks.get("gelu", lambda name, z: F.gelu(z))
+    modulate = hooks.get("modulate", lambda l, shift, scale, gate, tok: gate * (l * (1 + scale) + shift) + tok)
+    carry = hooks.get("carry", lambda pose: pose)
+    pb2 = hooks.get("pb2", lambda hb, w2, b2: hb @ w2.t() + b2)
+    S, nh = tokens.shape[0], W["heads"]
+    B = {"tok": ln("token_norm", tokens.float(), W["token_norm_w"], W["token_norm_b"], 1e-5)}
+    pose, outs = None, []
+    for it in range(iters):
+        pose = None if pose is None else carry(pose)            # the pose the kernel keeps in its workspace between the rounds
+        prev = f(W["empty_pose"]).expand(S, -1) if pose is None else pose
+        B["e"] = rnd(F.silu(prev @ f(W["embed_w"]).t() + f(W["embed_b"])))
+        shift, scale, gate = lin("mod", B["e"], W["mod_w"], W["mod_b"]).chunk(3, dim=-1)
+        x = modulate(ln("mod", B["tok"], None, None, 1e-6), shift, scale, gate, B["tok"])
+        for blk in W["blocks"]:
+            B["x0"] = x
+            B["qkv"] = rnd(lin("qkv", rnd(ln("n1", x, blk["n1_w"], blk["n1_b"], 1e-5)), blk["qkv_w"], blk["qkv_b"]))
+            q, k, v = B["qkv"].view(S, 3, nh, -1).permute(1, 2, 0, 3)
+            B["attn"] = rnd(attn_fn(q, k, v).permute(1, 0, 2).reshape(S, -1))
+            x = x + f(blk["ls1"]) * lin("proj", B["attn"], blk["proj_w"], blk["proj_b"])
+            B["xmid"] = x
+            B["hid"] = rnd(gelu("fc1", lin("fc1", rnd(ln("n2", x, blk["n2_w"], blk["n2_b"], 1e-5)), blk["fc1_w"], blk["fc1_b"])))
+            x = x + f(blk["ls2"]) * lin("fc2", B["hid"], blk["fc2_w"], blk["fc2_b"])
+        B["x"] = x
+        B["xn"] = rnd(ln("trunk_norm", x, W["trunk_norm_w"], W["trunk_norm_b"], 1e-5))
+        if pb1_slots is None:
+            z = lin("pb1", B["xn"], W["pb1_w"], W["pb1_b"])
+        else:                                                    # the split-K partials the kernel leaves behind, folded onto the bias in slot order
+            kc = B["xn"].shape[1] // pb1_slots
+            zero = torch.zeros_like(f(W["pb1_b"]))
+            B["part"] = torch.stack([lin("pb1", B["xn"][:, k * kc:(k + 1) * kc], W["pb1_w"][:, k * kc:(k + 1) * kc], zero) for k in range(pb1_slots)], 0)
+            z = f(W["pb1_b"]).expand(S, -1)
+            for k in range(pb1_slots):
+                z = z + B["part"][k]
+        hb = gelu("pb1", z)
+        delta = pb2(hb, f(W["pb2_w"]), f(W["pb2_b"]))
+        pose = delta if pose is None else pose + delta
+        outs.append(torch.cat([pose[:, :7], F.relu(pose[:, 7:])], dim=-1))
+    B["pose"], B["out"] = pose, torch.stack(outs, 0)
+    return B

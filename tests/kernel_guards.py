@@ -8,6 +8,9 @@ elementwise_budget() |got - ref| <= u_out |ref| + c u_acc mag for EVERY element 
 *_budget()           the constants c, each derived from the rounding points of its kernel (never fitted to a kernel's output)
 upsample_window()    the 16-bit roundings a bilinear kernel may hold per element; dpt_tail_budget() carries them through the fused output stage
                      (test_dpt_tail_budget_host.py); camera_tables_budget() for ovg_camera_tables (test_camera_tables_budget_host.py)
+camera_*()           ovg_camera_head stage by stage from the buffers it leaves in its workspace: camera_ws_views() (the layout), camera_ksplit()
+                     (the split-K plan), one budget per stage, rounding_window() for the overwritten 16-bit xn buffers, check_camera_stages() /
+                     check_camera_round2() (test_camera_head_budget_host.py, test_gpu_camera_head_stages.py)
 """
 import math
 
@@ -124,8 +127,9 @@ def poison_vt(vt, nk, sixteen_bit):
 def elementwise_budget(name, got, ref, mag, u_out, c, extra=None, u_acc=U_ACC, quiet=False):
     """Asserts |got - ref| <= u_out |ref| + c u_acc mag (+ extra) for every element; got: the kernel's result, ref / mag (/ extra): float64,
     c: a number or a float64 tensor broadcastable to ref (a per-row constant). Returns the worst used fraction of the budget."""
-    got = got.detach().to("cpu", torch.float64)
-    ref = ref.detach().to("cpu", torch.float64)
+    dev = ref.device if (ref.is_cuda and torch.is_tensor(mag) and mag.device == ref.device) else "cpu"    # the camera head's large references stay on their device
+    got = got.detach().to(dev, torch.float64)
+    ref = ref.detach().to(dev, torch.float64)
     assert got.shape == ref.shape, (name, got.shape, ref.shape)
     budget = u_out * ref.abs() + c * u_acc * mag.to(torch.float64)
     if extra is not None:
@@ -624,3 +628,394 @@ def check_camera_tables(name, enc, tables, Bd, quiet=False):
     free[Bd["rows"]] = False
     assert torch.equal(tables.detach().double().cpu()[:, free], Bd["tables"][:, free]), name + ": a view without a camera must hold adapt_b exactly"
     return a, b
+
+
+# ---- ovg_camera_head (csrc/ovg_camhead.hip), stage by stage -----------------------------------
+# The entry leaves its intermediates in the caller's workspace, so every stage is gated against a float64 reference computed from the
+# kernel's OWN stored input of that stage: tok <- tokens, e <- pose, x0 <- tok, e, qkv <- x0, attn <- qkv, x_mid <- x0, attn, hid <- x_mid,
+# x <- x_mid, hid (and <- tok, e, attn, hid through all three GEMMs), xn <- x, out <- xn. With iters = 1 and one trunk block the workspace
+# holds all of these but three after the call: the 16-bit xn buffer is overwritten twice (LN_n1(x0), LN_n2(x_mid), trunk_norm(x)), and x
+# is updated in place. Two ways round that, both used:
+#  * carried: x0 / x_mid are recomputed in float64 from tok, e, attn with their f32 error bounds (the GEMM budgets folded in), the LayerNorm
+#    carries the bound, and an xn element whose float64 value lies within that bound of a rounding midpoint may be stored one ulp away:
+#    rounding_window() turns that into a per-element delta which the next GEMM carries as `extra` = delta |w|^T. In the f32 mode there is no
+#    rounding point and the bound itself is carried. In the 16-bit modes the worst-case bound of a K = 2048 accumulation (gemm_c, ~2.5e-4 of
+#    sum |x||w|) is as large as a 16-bit ulp of xn, i.e. EVERY element would count as ambiguous and the gate would see nothing;
+#  * stored: the same call with ls1 = ls2 = 0 leaves x = x0 in the workspace, with ls2 = 0 it leaves x = x_mid (x += 0 * y is exact), and its
+#    qkv / attn / hid are bit-identical to the real call's (asserted by the caller). Then only the LayerNorm's own f32 budget (~70 u_acc) decides
+#    which xn elements are ambiguous: about 2 % of a row in f16, 0.2 % in bf16, capped at CAMERA_AMBIGUOUS_CAP per row.
+CAM_C, CAM_HEADS, CAM_HD, CAM_HID, CAM_MOD, CAM_PB, CAM_T = 2048, 16, 128, 8192, 6144, 1024, 9
+CAM_PART_COLS, CAM_MAX_S = 32768, 4096
+CAMERA_GEMMS = {"mod": (CAM_MOD, CAM_C), "qkv": (3 * CAM_C, CAM_C), "proj": (CAM_C, CAM_C), "fc1": (CAM_HID, CAM_C), "fc2": (CAM_C, CAM_HID),
+                "pb1": (CAM_PB, CAM_C)}            # name -> (N, K)
+CAMERA_AMBIGUOUS_CAP = 0.05
+CAMERA_TOL_TWIN = {"bf16": 1.5e-2, "f16": 2e-3, "f32": 1e-5}       # gpu_selftest.test_camera_head's global gates against the rounding twin
+CAMERA_DT = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
+
+
+def camera_ws_views(ws, S, dtype):
+    """ws: the uint8 workspace tensor of an ovg_camera_head call -> dict of typed views in the order of carve(): tok, x [S, 2048] f32,
+    pose [S, 9] f32, part [S, 32768] f32 (the split-K partials, [ksplit][S][N] of the last GEMM), xn, e [S, 2048], qkv [S, 6144],
+    attn [S, 2048], hid [S, 8192] in the compute dtype; every buffer starts on a multiple of 256 bytes."""
+    from omnivggt_official_amd import ops
+    f32 = torch.float32
+    plan = (("tok", f32, CAM_C), ("x", f32, CAM_C), ("pose", f32, CAM_T), ("part", f32, CAM_PART_COLS), ("xn", dtype, CAM_C), ("e", dtype, CAM_C),
+            ("qkv", dtype, 3 * CAM_C), ("attn", dtype, CAM_C), ("hid", dtype, CAM_HID))
+    off, views = 0, {}
+    for name, dt, cols in plan:
+        nbytes = S * cols * torch.empty((), dtype=dt).element_size()
+        views[name] = ws[off:off + nbytes].view(dt).view(S, cols)
+        off += (nbytes + 255) // 256 * 256
+    assert off == ops.camera_head_workspace_bytes(S, dtype), (off, ops.camera_head_workspace_bytes(S, dtype))
+    return views
+
+
+def camera_ksplit(S, N, K):
+    """pick_ksplit, restated: doubled until the grid has 512 workgroups, never above 16, never below 256 k per slot, never more than
+    32768 partial columns."""
+    zs, ks = (S + 63) // 64, 1
+    while (N // 64) * zs * ks < 512 and ks < 16 and K // (ks * 2) >= 256 and ks * 2 * N <= CAM_PART_COLS:
+        ks *= 2
+    return ks
+
+
+def camera_ksplit_table(S):
+    return {name: camera_ksplit(S, N, K) for name, (N, K) in CAMERA_GEMMS.items()}
+
+
+def camera_gemm_c(name, mode):
+    """gemm_c for the K of that GEMM + one addition per split-K slot (the consumer folds the slots one after the other onto the bias), with
+    the largest ksplit the plan can pick for it (S = 1)."""
+    N, K = CAMERA_GEMMS[name]
+    return gemm_c(K, mode) + MARGIN * camera_ksplit(1, N, K)
+
+
+def camera_w64(W, dev):
+    """The packed weights (heads_hip.HipCameraHead._pack) as float64 on `dev`."""
+    cv = lambda v: v.detach().to(dev, torch.float64) if torch.is_tensor(v) else v
+    out = {k: cv(v) for k, v in W.items() if k != "blocks"}
+    out["blocks"] = [{k: cv(v) for k, v in blk.items()} for blk in W["blocks"]]
+    return out
+
+
+def rounding_window(v, b, mode):
+    """v float64, b >= 0 the f32 budget of the value a kernel holds before its store -> (r, delta, ambiguous): r = the reference's stored
+    value, delta = how far the kernel's stored value may be from r (rounding is monotone: it lies between the roundings of v - b and
+    v + b; zero wherever both equal r), ambiguous = the two ends round differently. f32: nothing is rounded below the arithmetic's own
+    precision, delta = b + one f32 rounding."""
+    if mode == "f32":
+        return v, b + U_ACC * v.abs(), torch.zeros_like(v, dtype=torch.bool)
+    r, lo, hi = round16(v, mode), round16(v - b, mode), round16(v + b, mode)
+    return r, torch.maximum(hi - r, r - lo), lo != hi
+
+
+def _ln_abs(x, w, b, eps):
+    ref, mag, c, extra = layernorm_budget(x, w, b, eps)
+    return ref, c * U_ACC * mag + extra
+
+
+def ln_carry(x, ex, w, eps):
+    """An absolute error ex of x through y = (x - mean) rstd w + b, first order as in qk_norm_rope_error."""
+    x = x.double()
+    mean = x.mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((x - mean) ** 2).mean(-1, keepdim=True) + eps)
+    zh = (x - mean) * rstd
+    return w.abs() * rstd * (ex + ex.mean(-1, keepdim=True) + zh.abs() * (zh.abs() * ex).mean(-1, keepdim=True))
+
+
+# row_layernorm (2048 values on 256 threads): a thread adds its 8 values one after the other (7), a 6-level butterfly, the four wave sums
+# (3): depth 16 <= the 3 + 2048 / 256 + 6 = 17 layernorm_budget charges for n = 2048. Covered; no depth of its own.
+CAMERA_LN_DEPTH = 7 + 6 + 3
+assert CAMERA_LN_DEPTH <= 3 + CAM_C // 256 + 6
+
+
+# e = SiLU(v), v = b + sum_9 w_i p_i in f32: nine products and nine sums, a term passes through at most 10 roundings -> ev = 10 u mag_v,
+# mag_v = |b| + sum |w||p|. s(v) = v / (1 + exp(-v)): |s'| <= 1.0999 carries ev; expf within 3 ulp (6 u, C_EXP's bound) moves the denominator
+# by at most 6 u of itself, the sum 1, the division 1 -> 8 u |s|, and |s(v)| <= |v| <= mag_v: c = 1.1 x 10 + 8 on mag_v (x margin).
+def camera_embed_budget(pose, W, mode):
+    """pose [S, 9] (or [9]: the empty pose, one row for all) float64 -> (ref [S, 2048], mag, c, extra)."""
+    pose = pose.double()
+    w, b = W["embed_w"], W["embed_b"]
+    v = pose @ w.t() + b
+    mag = pose.abs() @ w.abs().t() + b.abs()
+    ref = v * torch.sigmoid(v)
+    return ref, mag, MARGIN * (1.1 * 10 + 8), f16_subnormal_floor(mode)
+
+
+# x0 = gate (ln (1 + scale) + shift) + tok, (shift, scale, gate) = e mod_w^T + mod_b folded from the split-K slots, ln = LayerNorm(tok) without
+# affine parameters, eps 1e-6. Each of the three GEMM values within em = c_gemm u mag_mod, ln within layernorm_budget's bound; 1 + scale, the
+# two products and the two sums: 5 roundings on |gate| (|ln||1 + scale| + |shift|) + |tok|.
+def camera_x0(tok, e, W, mode):
+    """tok [S, 2048], e [S, 2048] float64 (the stored buffers) -> (x0, e_x0) float64."""
+    tok, e = tok.double(), e.double()
+    mod = e @ W["mod_w"].t() + W["mod_b"]
+    em = camera_gemm_c("mod", mode) * U_ACC * (e.abs() @ W["mod_w"].abs().t() + W["mod_b"].abs())
+    (h, s, g), (eh, es, eg) = mod.chunk(3, -1), em.chunk(3, -1)
+    one, zero = torch.ones(CAM_C, dtype=torch.float64, device=tok.device), torch.zeros(CAM_C, dtype=torch.float64, device=tok.device)
+    l, el = _ln_abs(tok, one, zero, 1e-6)
+    inner = l * (1 + s) + h
+    e_inner = (1 + s).abs() * el + l.abs() * es + eh
+    x0 = g * inner + tok
+    e_x0 = g.abs() * e_inner + inner.abs() * eg + eg * e_inner + MARGIN * 5 * U_ACC * (g.abs() * (l.abs() * (1 + s).abs() + h.abs()) + tok.abs())
+    return x0, e_x0
+
+
+def camera_residual(x, ex, a, w, bias, ls, name, mode):
+    """x' = x + ls (a w^T + bias), the partials folded onto the bias by the consumer: the GEMM's budget through |ls| + three roundings (res_c).
+    -> (x', e_x')."""
+    a = a.double()
+    y, mg = a @ w.t() + bias, a.abs() @ w.abs().t() + bias.abs()
+    return x + ls * y, ex + ls.abs() * camera_gemm_c(name, mode) * U_ACC * mg + MARGIN * 3 * U_ACC * (x.abs() + ls.abs() * mg)
+
+
+# gelu_c carries z's error through the global bound |gelu'| <= 1.13. At K = 2048 that error (c_gemm u mag, mag ~ 30 |z|) is ~5e-3, more than
+# the whole difference between the erf form and its tanh approximation (4.7e-4). The mean value theorem gives the same bound with the
+# LOCAL supremum of |gelu'| over [z - ez, z + ez]: gelu'(t) = Phi(t) + t phi(t), its derivative phi(t) (2 - t^2) vanishes at +-sqrt 2 only, so
+# the supremum is attained at an end of the interval or at +-sqrt 2 (|gelu'| = 1.129 / 0.129) where the interval holds it. Never above 1.13 ez;
+# in the negative tail, where gelu' ~ 1e-2, two orders tighter. The evaluation's own 8 roundings stay on mag as in gelu_c.
+def gelu_carry(z, ez):
+    d = lambda t: 0.5 * (1 + torch.erf(t / math.sqrt(2.0))) + t * torch.exp(-0.5 * t * t) / math.sqrt(2.0 * math.pi)
+    lo, hi = z - ez, z + ez
+    sup = torch.maximum(d(lo).abs(), d(hi).abs())
+    for t0, v in ((math.sqrt(2.0), 1.13), (-math.sqrt(2.0), 0.13)):
+        sup = torch.where((lo <= t0) & (hi >= t0), sup.clamp_min(v), sup)
+    return sup * ez
+
+
+def camera_ln_gemm(x, ex, nw, nb, w, bias, name, mode, gelu=False):
+    """LayerNorm (eps 1e-5) of x (known within ex), stored in the mode's dtype, then the GEMM `name` (+ exact-erf GELU) and the store.
+    -> dict(ref, mag, c, extra, share): extra = the stored xn's rounding window carried through |w| (and, with the GEMM's own budget, through
+    gelu_carry, which never exceeds |gelu'| <= 1.13), share = the fraction of ambiguous xn elements per row."""
+    v, b = _ln_abs(x, nw, nb, 1e-5)
+    b = b + ln_carry(x, ex, nw, 1e-5)
+    r, delta, amb = rounding_window(v, b, mode)
+    z, mg = r @ w.t() + bias, r.abs() @ w.abs().t() + bias.abs()
+    extra = delta @ w.abs().t()
+    cg = camera_gemm_c(name, mode)
+    if gelu:
+        return {"ref": torch.nn.functional.gelu(z), "mag": mg, "c": MARGIN * 8, "extra": gelu_carry(z, cg * U_ACC * mg + extra) + f16_subnormal_floor(mode),
+                "share": amb.double().mean(-1)}
+    return {"ref": z, "mag": mg, "c": cg, "extra": extra + f16_subnormal_floor(mode), "share": amb.double().mean(-1)}
+
+
+# attention of the trunk (ch_attn_kernel): head dim 128, everything f32, P never rounded. qs = q / sqrt(128) (1 rounding), s = sum_128 qs k
+# one after the other (a product and a sum per term: a term passes through at most 128 + 1 roundings) -> e_s = 130 u A, A = max_k sum_d |qs||k|;
+# s - max: one rounding on |s - max| <= 2 Smax; expf 3 ulp -> p relative (130 A + 2 Smax + 6) u, numerator and denominator both (x 2).
+# The row sum: a thread adds ceil(S / 128) values, a 6-level butterfly, the two wave sums, then the reciprocal -> ceil(S / 128) + 8;
+# PV: S products and S sums one key after the other -> S + 1; the product with the reciprocal 1. mag = sum p |v| / sum p.
+def camera_attn_budget(qkv, mode):
+    """qkv [S, 6144] float64 (the stored buffer) -> (ref [S, 2048], mag, c [S, 2048])."""
+    S = qkv.shape[0]
+    q, k, v = qkv.double().view(S, 3, CAM_HEADS, CAM_HD).permute(1, 2, 0, 3)
+    scale = CAM_HD ** -0.5
+    ref, mag, c = (torch.empty(S, CAM_HEADS, CAM_HD, dtype=torch.float64, device=qkv.device) for _ in range(3))
+    for h in range(0, CAM_HEADS, 4):
+        qq, kk, vv = q[h:h + 4] * scale, k[h:h + 4], v[h:h + 4]
+        s = qq @ kk.transpose(-1, -2)
+        A = (qq.abs() @ kk.abs().transpose(-1, -2)).amax(-1)
+        p = torch.softmax(s, -1)
+        ch = MARGIN * (2 * (130 * A + 2 * s.abs().amax(-1) + 6) + (S + 127) // 128 + 8 + S + 1 + 1)
+        ref[:, h:h + 4], mag[:, h:h + 4] = (p @ vv).permute(1, 0, 2), (p @ vv.abs()).permute(1, 0, 2)
+        c[:, h:h + 4] = ch.t().unsqueeze(-1)
+    return ref.reshape(S, CAM_C), mag.reshape(S, CAM_C), c.reshape(S, CAM_C)
+
+
+# pose branch. pb1 is the LAST GEMM of a call, so its split-K partials part[ks][S][1024] are still in the workspace afterwards: the GEMM
+# and its consumer are gated apart.
+#  * every slot against xn[:, slot] pb1_w[:, slot]^T: gemm_c for the slot's K / ksplit products, on sum |xn||w| over the slot;
+#  * ch_pose_kernel against the STORED partials: z = b1 + the slots one after the other (ksplit roundings on |b1| + sum |part|),
+#    g = GELU(z) in f32 (gelu_carry of that + the evaluation's 8 roundings on |z|; never stored), delta = g pb2^T + b2 with f32 operands:
+#    a product (1), a thread adds 4 terms (3), a 6-level butterfly, the four wave sums (3), the bias (1) -> 14 + 1 = 15 on |g||pb2|^T + |b2|;
+#    pose = previous + delta (one more rounding from the second round on), out = pose with ReLU on the two FoV components (1-Lipschitz).
+#    Nothing of the K = 2048 accumulation's worst case enters: the budget is of order 1e-6 of a component.
+def camera_part_view(part, S, ks, N=CAM_PB):
+    """The [S, 32768] partial buffer of camera_ws_views -> the [ks, S, N] partials the last GEMM left at its start."""
+    return part.reshape(-1)[:ks * S * N].view(ks, S, N)
+
+
+def check_camera_pb1(name, part, xn, W, mode, quiet=False):
+    """part [ks, S, 1024] (stored) against the stored xn, slot by slot. -> the worst used fraction."""
+    xn, w = xn.double(), W["pb1_w"]
+    ks = part.shape[0]
+    kc = CAM_C // ks
+    used = 0.0
+    for k in range(ks):
+        xs, ws = xn[:, k * kc:(k + 1) * kc], w[:, k * kc:(k + 1) * kc]
+        used = max(used, elementwise_budget("%s.pb1_slot%d" % (name, k), part[k], xs @ ws.t(), xs.abs() @ ws.abs().t(), U_OUT["f32"], gemm_c(kc, mode), quiet=True))
+    if not quiet:
+        print("[PASS] %-52s budget used %.3f" % (name + ".pb1_slots(%d).elementwise" % ks, used), flush=True)
+    return used
+
+
+def camera_pose_budget(part, W, mode, prev=None):
+    """part [ks, S, 1024] float64 (the stored partials), prev [S, 9] the carried pose or None -> (pose [S, 9] un-activated, out [S, 9],
+    e [S, 9] absolute)."""
+    part = part.double()
+    z, mz = W["pb1_b"] + part.sum(0), W["pb1_b"].abs() + part.abs().sum(0)
+    eg = gelu_carry(z, MARGIN * part.shape[0] * U_ACC * mz) + MARGIN * 8 * U_ACC * z.abs()
+    g = torch.nn.functional.gelu(z)
+    delta = g @ W["pb2_w"].t() + W["pb2_b"]
+    e = eg @ W["pb2_w"].abs().t() + MARGIN * 15 * U_ACC * (g.abs() @ W["pb2_w"].abs().t() + W["pb2_b"].abs())
+    pose = delta
+    if prev is not None:
+        pose = prev.double() + delta
+        e = e + MARGIN * U_ACC * (prev.double().abs() + delta.abs())
+    out = torch.cat([pose[:, :7], torch.relu(pose[:, 7:])], -1)
+    return pose, out, e
+
+
+CAMERA_COMPONENTS = ("tx", "ty", "tz", "qx", "qy", "qz", "qw", "fov_h", "fov_w")
+
+
+def _abs_gate(name, got, ref, err, quiet=False):
+    return elementwise_budget(name, got, ref, torch.zeros_like(ref), U_OUT["f32"], 0.0, extra=err, quiet=quiet)
+
+
+def check_camera_pose(name, out, pose, part, W, mode, prev=None, quiet=False):
+    """out [S, 9] (the activated encodings of the round) and pose [S, 9] or None (the carried, un-activated pose in the workspace) against
+    the stored pb1 partials, each of the nine components gated on its own. -> the worst used fraction."""
+    rp, ro, e = camera_pose_budget(part, W, mode, prev)
+    used = 0.0
+    for i, comp in enumerate(CAMERA_COMPONENTS):
+        used = max(used, _abs_gate("%s.out.%s" % (name, comp), out[:, i:i + 1], ro[:, i:i + 1], e[:, i:i + 1], quiet=quiet))
+        if pose is not None:
+            used = max(used, _abs_gate("%s.pose.%s" % (name, comp), pose[:, i:i + 1], rp[:, i:i + 1], e[:, i:i + 1], quiet=True))
+    return used
+
+
+def check_camera_embed(name, e, pose, W, mode, quiet=False):
+    ref, mag, c, extra = camera_embed_budget(pose, W, mode)
+    return elementwise_budget(name, e, ref.expand(e.shape), mag.expand(e.shape), U_OUT[mode], c, extra=extra, quiet=quiet)
+
+
+def check_camera_stages(tag, B, tokens, W, mode, quiet=False):
+    """Every stage gate of an iters = 1, one-block call. B: the buffers after the call (camera_ws_views' keys tok, x, pose, xn, e, qkv, attn,
+    hid, part as camera_part_view gives it + out: [S, 9]) and, where the caller has them, x0 and xmid (the stored residual stream after the modulation / after the attention
+    update, see above); without them, or in the f32 mode, qkv and hid are gated with the carried bounds. tokens [S, 2048] f32; W: camera_w64
+    on the device of the buffers. Asserts every budget and the cap on the ambiguous xn elements; -> ({stage: used fraction}, the largest ambiguous share of a row)."""
+    dev = B["tok"].device
+    d = lambda t: t.detach().to(dev, torch.float64)
+    blk = W["blocks"][0]
+    u, uT = U_OUT["f32"], U_OUT[mode]
+    floor = f16_subnormal_floor(mode)
+    used, shares = {}, {}
+
+    def gate(stage, got, ref, mag, u_out, c, extra=None):
+        used[stage] = max(used.get(stage, 0.0), elementwise_budget("%s.%s" % (tag, stage), got, ref, mag, u_out, c, extra=extra, quiet=quiet))
+
+    def abs_gate(stage, got, ref, err):
+        used[stage] = max(used.get(stage, 0.0), _abs_gate("%s.%s" % (tag, stage), got, ref, err, quiet=quiet))
+
+    # (c) tok <- tokens
+    ref, mag, c, extra = layernorm_budget(d(tokens), W["token_norm_w"], W["token_norm_b"], 1e-5)
+    gate("tok", B["tok"], ref, mag, u, c, extra)
+    # (d) e <- empty_pose
+    used["e"] = check_camera_embed(tag + ".e", B["e"], W["empty_pose"].view(1, CAM_T), W, mode, quiet=quiet)
+    # x0 <- stored tok, e
+    tok, e, attn, hid = d(B["tok"]), d(B["e"]), d(B["attn"]), d(B["hid"])
+    x0, e_x0 = camera_x0(tok, e, W, mode)
+    zero = torch.zeros_like(x0)
+    if "x0" in B:
+        abs_gate("x0", B["x0"], x0, e_x0)
+    # (e) qkv: carried in the f32 mode (and where no stored x0 exists), from the stored x0 otherwise
+    carried = mode == "f32" or "x0" not in B
+    G = camera_ln_gemm(x0, e_x0, blk["n1_w"], blk["n1_b"], blk["qkv_w"], blk["qkv_b"], "qkv", mode) if carried else \
+        camera_ln_gemm(d(B["x0"]), zero, blk["n1_w"], blk["n1_b"], blk["qkv_w"], blk["qkv_b"], "qkv", mode)
+    gate("qkv", B["qkv"], G["ref"], G["mag"], uT, G["c"], G["extra"])
+    shares["xn_n1"] = float(G["share"].max())
+    if mode == "f32" and "x0" in B:
+        G = camera_ln_gemm(d(B["x0"]), zero, blk["n1_w"], blk["n1_b"], blk["qkv_w"], blk["qkv_b"], "qkv", mode)
+        gate("qkv", B["qkv"], G["ref"], G["mag"], uT, G["c"], G["extra"])
+    del G
+    # (f) attn <- stored qkv
+    ref, mag, c = camera_attn_budget(d(B["qkv"]), mode)
+    gate("attn", B["attn"], ref, mag, uT, c, floor)
+    # x_mid <- x0, stored attn
+    xm, e_xm = camera_residual(x0, e_x0, attn, blk["proj_w"], blk["proj_b"], blk["ls1"], "proj", mode)
+    if "xmid" in B:
+        if "x0" in B:
+            r2, e2 = camera_residual(d(B["x0"]), zero, attn, blk["proj_w"], blk["proj_b"], blk["ls1"], "proj", mode)
+            abs_gate("xmid", B["xmid"], r2, e2)
+        else:
+            abs_gate("xmid", B["xmid"], xm, e_xm)
+    # (g) hid
+    carried = mode == "f32" or "xmid" not in B
+    G = camera_ln_gemm(xm, e_xm, blk["n2_w"], blk["n2_b"], blk["fc1_w"], blk["fc1_b"], "fc1", mode, gelu=True) if carried else \
+        camera_ln_gemm(d(B["xmid"]), zero, blk["n2_w"], blk["n2_b"], blk["fc1_w"], blk["fc1_b"], "fc1", mode, gelu=True)
+    gate("hid", B["hid"], G["ref"], G["mag"], uT, G["c"], G["extra"])
+    shares["xn_n2"] = float(G["share"].max())
+    if mode == "f32" and "xmid" in B:
+        G = camera_ln_gemm(d(B["xmid"]), zero, blk["n2_w"], blk["n2_b"], blk["fc1_w"], blk["fc1_b"], "fc1", mode, gelu=True)
+        gate("hid", B["hid"], G["ref"], G["mag"], uT, G["c"], G["extra"])
+    del G
+    # (h) x <- stored tok, e, attn, hid: three GEMM budgets and the residual roundings (and <- the stored x_mid, hid where there is one)
+    xf, e_xf = camera_residual(xm, e_xm, hid, blk["fc2_w"], blk["fc2_b"], blk["ls2"], "fc2", mode)
+    abs_gate("x", B["x"], xf, e_xf)
+    if "xmid" in B:
+        r2, e2 = camera_residual(d(B["xmid"]), zero, hid, blk["fc2_w"], blk["fc2_b"], blk["ls2"], "fc2", mode)
+        abs_gate("x", B["x"], r2, e2)
+        if not quiet:       # how wide this gate is: the fc2 accumulation's worst case (K = 8192) against the size of the stream it is added to
+            print("%s: the budget of x from the stored x_mid is at most %.2f%% of the row's rms" % (tag, 100 * float((e2 / r2.pow(2).mean(-1, keepdim=True).sqrt()).max())), flush=True)
+    # (i) xn <- stored x
+    ref, mag, c, extra = layernorm_budget(d(B["x"]), W["trunk_norm_w"], W["trunk_norm_b"], 1e-5)
+    gate("xn", B["xn"], ref, mag, uT, c, extra + floor)
+    # (j) the pb1 partials <- stored xn, slot by slot; out, pose <- the stored partials
+    used["pb1"] = check_camera_pb1(tag, d(B["part"]), d(B["xn"]), W, mode, quiet=quiet)
+    used["out"] = check_camera_pose(tag, B["out"], B["pose"], d(B["part"]), W, mode, quiet=quiet)
+    # (l) the ambiguous share of the two overwritten xn buffers
+    if not quiet:
+        print("%s: ambiguous xn elements per row at most %.2f%% (n1), %.2f%% (n2)" % (tag, 100 * shares["xn_n1"], 100 * shares["xn_n2"]), flush=True)
+    if mode != "f32":
+        assert max(shares.values()) < CAMERA_AMBIGUOUS_CAP, "%s: %s of a row's xn elements count as ambiguous: the gate would hide failures" % (tag, shares)
+    return used, max(shares.values())
+
+
+def camera_group_gate(name, got, ref, tol):
+    """The global gate per component group: translation, quaternion and field of view each normalised by their own maximum.
+    got / ref [..., 9] -> True when all three hold (printed through gpu_selftest.report)."""
+    import gpu_selftest as st
+    ok = True
+    for grp, sl in (("T", slice(0, 3)), ("quat", slice(3, 7)), ("fov", slice(7, 9))):
+        ok = st.report("%s.%s" % (name, grp), got[..., sl].detach().double().cpu(), ref[..., sl].detach().double().cpu(), tol) and ok
+    return ok
+
+
+def check_camera_round2(tag, B1, B2, W, mode, positive, quiet=False):
+    """The round transition. B1 / B2: the buffers after an iters = 1 / iters = 2 call on the same input (pose, e, xn, part [ks, S, 1024], out [iters, S, 9]).
+    The pose after round 1 is read from out[0] where both FoV components are positive (ReLU the identity); where they are negative out[0]
+    holds zeros there and the un-activated pose is the one the iters = 1 call left in its workspace. Gates round 2's e against
+    SiLU(embed(pose)), the pb1 partials against the stored xn, out[1] and the carried pose against pose + the delta from the stored partials. -> the worst used fraction."""
+    dev = B2["xn"].device
+    o1, o2 = B1["out"].detach().to(dev), B2["out"].detach().to(dev)
+    p1 = B1["pose"].detach().to(dev)
+    assert torch.equal(o1[0], o2[0]), tag + ": round 1 of the two-round call differs from the one-round call"
+    assert torch.equal(o2[0][:, :7], p1[:, :7]), tag + ": translation and quaternion are stored un-activated"
+    if positive:
+        assert float(o2[0][:, 7:].min()) > 0 and torch.equal(o2[0], p1), tag + ": the FoV components were to be positive after round 1"
+        pose1 = o2[0].double()
+    else:
+        assert float(p1[:, 7:].max()) < 0 and float(o2[0][:, 7:].abs().max()) == 0, tag + ": the FoV components were to be negative after round 1, and clamped in out[0]"
+        pose1 = p1.double()
+    a = check_camera_embed(tag + ".e_round2", B2["e"], pose1, W, mode, quiet=quiet)
+    b = max(check_camera_pb1(tag + ".round2", B2["part"].to(dev), B2["xn"].to(dev), W, mode, quiet=quiet),
+            check_camera_pose(tag + ".round2", o2[1], B2["pose"], B2["part"].to(dev), W, mode, prev=pose1, quiet=quiet))
+    if not positive:
+        rp, _, e = camera_pose_budget(B2["part"].to(dev), W, mode, pose1)
+        assert float((rp[:, 7:] + e[:, 7:]).max()) < 0, tag + ": the FoV components were to stay negative after round 2"
+        assert float(B2["pose"][:, 7:].max()) < 0 and float(o2[1][:, 7:].abs().max()) == 0, tag + ": out[1] clamped, the carried pose not"
+    return max(a, b)
+
+
+# Token counts at which every GEMM takes every ksplit value the rule can give it (test_camera_head_budget_host.py asserts that), the last
+# z slice holds 1, 2, 3 or 4 16-row blocks, z slices are ragged and the attention's 128-key loops make 2 .. 32 trips.
+CAMERA_S_SET = (1, 17, 40, 65, 129, 193, 321, 513, 961, 1985, 4096)
+
+
+def camera_tokens(S, seed):
+    """[S, 2048] f32 camera tokens for the stage gates: 1.3 (1 + 0.3 n) with a random sign, n normal. Values away from zero keep the
+    share of tiny LayerNorm outputs low: an xn element counts as ambiguous when the LayerNorm's budget -- dominated, for small elements,
+    by the error of the row mean, an absolute term -- reaches a rounding midpoint, which in f16 is 3.3 % of a normal row on average and up
+    to 4.6 % in a few hundred rows, too close to the cap of 5 % for 4096 rows; with these tokens 1.4 % and 2.4 %."""
+    g = torch.Generator().manual_seed(seed)
+    sign = torch.sign(torch.randn(S, CAM_C, generator=g))
+    return sign * (1.0 + 0.3 * torch.randn(S, CAM_C, generator=g)) * 1.3

@@ -979,4 +979,7 @@ def test_camera_head_every_row_block_edge_guarded():
             # through 4 refinement rounds of a 4-block trunk; a boundary case of any of those roundings moves an element by a 16-bit ulp
             # of an intermediate, so there is no per-element budget in u_acc to derive
             _global("camera_head_%s_S%d_vs_twin" % (mode, S), _val(slot.view).view(4, S, 9), twin.double(), tol_twin[mode])
+            # the same gate per component group (translation, quaternion, field of view each against its own maximum); the stages of the
+            # head have per-element budgets in test_gpu_camera_head_stages.py
+            assert kg.camera_group_gate("camera_head_%s_S%d_vs_twin" % (mode, S), _val(slot.view).view(4, S, 9), twin.double(), tol_twin[mode])
             _global_only()
