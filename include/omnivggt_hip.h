@@ -487,7 +487,8 @@ int ovg_conv(const ovg_conv_params*, void* stream);
 
 /* Bilinear resize, align_corners = True (F.interpolate at dpt_head.py:242-247, :466), NHWC, C % 8 == 0:
  * y[i, oy, ox, :] = lerp of x[i, :, :, :] at (oy*(H-1)/(OH-1), ox*(W-1)/(OW-1)), plus the optional UV
- * position embedding (pos_x [OW, C/2], pos_y [OH, C/2], dpt_head.py:249-250) -- both in `dtype`. */
+ * position embedding (pos_x [OW, C/2], pos_y [OH, C/2], dpt_head.py:249-250) -- both in `dtype`.
+ * OH == 1 / OW == 1 (one-row / one-column patch grids) take source row / column 0, like ATen. */
 typedef struct {
   const void* x; int64_t ldx; void* y; int64_t ldy;
   const float* pos_x; const float* pos_y;

@@ -537,6 +537,11 @@ class ZeroAggregator(nn.Module):
             raise ValueError(f"Expected 3 input channels, got {C_in}")
         if not images.is_cuda:
             raise L.OvgError("ZeroAggregator.forward needs HIP device tensors: there is no CPU fallback")
+        # on every call and before anything is queued: the device kernels index the views with these lists unchecked, and a
+        # cached index tensor (camera_tables) says nothing about the view count of THIS call
+        for name, index in (("camera_gt_index", camera_gt_index), ("depth_gt_index", depth_gt_index)):
+            if len(index) and (min(int(i) for i in index) < 0 or max(int(i) for i in index) >= S):
+                raise IndexError("%s out of range for %d views" % (name, S))
         if self.shard is not None:
             return self.shard.forward(self, images, extrinsics, intrinsics, depth, mask, depth_gt_index, camera_gt_index)
         device = images.device

@@ -432,12 +432,14 @@ extern "C" int ovg_conv(const ovg_conv_params* p, void* stream) {
 }
 
 extern "C" int ovg_upsample(const ovg_upsample_params* p, void* stream) {
-  if (!p || !p->x || !p->y || p->n_img <= 0 || p->H <= 0 || p->W <= 0 || p->OH <= 1 || p->OW <= 1) return OVG_E_ARG;
+  if (!p || !p->x || !p->y || p->n_img <= 0 || p->H <= 0 || p->W <= 0 || p->OH <= 0 || p->OW <= 0) return OVG_E_ARG;
   if (p->C <= 0 || p->C % 8 || p->ldx < p->C || p->ldy < p->C || (p->ldx % 8) || (p->ldy % 8)) return OVG_E_ARG;
   if ((p->pos_x == nullptr) != (p->pos_y == nullptr) || (p->pos_x && (p->C % 16))) return OVG_E_ARG;
   if (!al16(p->x) || !al16(p->y)) return OVG_E_ARG;
   const int64_t total = p->n_img * p->OH * p->OW * (p->C / 8);
-  const float sy = (float)(p->H - 1) / (float)(p->OH - 1), sx = (float)(p->W - 1) / (float)(p->OW - 1);
+  // an output side of one pixel (the DPT pyramid of a one-row / one-column patch grid) samples source row / column 0: the scale ATen uses
+  // for align_corners with output_size <= 1 (area_pixel_compute_scale)
+  const float sy = p->OH > 1 ? (float)(p->H - 1) / (float)(p->OH - 1) : 0.f, sx = p->OW > 1 ? (float)(p->W - 1) / (float)(p->OW - 1) : 0.f;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(grid_1d(total, 256, 1 << 20)), block(256);
   switch (p->dtype) {

@@ -245,13 +245,15 @@ def _rms_rel(a, b):
     return float((a - b).pow(2).mean().sqrt() / b.pow(2).mean().sqrt().clamp(min=1e-30))
 
 
-@pytest.mark.parametrize("name", TWIN_CASES)
+@pytest.mark.parametrize("name", TWIN_CASES + tuple(common.TINY_TWIN_CASES))
 def test_low_precision_modes_vs_twin(full_model, name):
     """SURVEY 8c Gate 2: the 16-bit throughput modes at FULL depth (24 + 24 + 24 blocks, HIP DPT heads) against the f32
     reference golden AND against the same-precision twin -- the reference itself under torch.autocast('cpu', bfloat16)
     on the same weights / inputs (oracle/gen_golden_bf16twin.py). Gate: on every aggregator layer and on pose_enc the
     HIP error vs the f32 reference is <= 2x the twin's own error (max-rel AND rms-rel); the dense predictions, which pass
     through the 16-bit DPT heads (a "next" row), <= 3x. The measured table is appended to gpurun_out/lowprec_parity.txt."""
+    # the tiny / long grids that have a twin (common.TINY_TWIN_CASES: 14 x 14 ... 14 x 1778) run under the same rule, on their fixtures'
+    # own sampling (all token rows, the dense maps whole)
     S, dgi, cgi, hw = common.case(name)
     gold, twin = common.load_golden(name), common.load_golden(name + "_bf16twin")
     keys = ["tok_L%d" % l for l in common.TOK_LAYERS] + ["pose_enc", "depth", "depth_conf", "world_points", "world_points_conf"]
@@ -259,16 +261,20 @@ def test_low_precision_modes_vs_twin(full_model, name):
     for dtype, tag in ((torch.bfloat16, "bf16"), (torch.float16, "f16")):
         full_model.set_compute_dtype(dtype)
         full_model.hip_heads = True
-        out = run_full(full_model, S, dgi, cgi, hw=hw)
-        toks, _ = run_agg(full_model, S, dgi, cgi, hw=hw)
-        assert all(torch.isfinite(t).all() for t in toks)
-        got = {"tok_L%d" % l: common.sample_tokens([t.cpu() for t in toks], l) for l in common.TOK_LAYERS}
-        got["pose_enc"] = out["pose_enc"].cpu()
-        got["depth"] = out["depth"][0, :, ::37, ::37, 0].cpu()
-        got["depth_conf"] = out["depth_conf"][0, :, ::37, ::37].cpu()
-        got["world_points"] = out["world_points"][0, :, ::37, ::37].cpu()
-        got["world_points_conf"] = out["world_points_conf"][0, :, ::37, ::37].cpu()
+        if name in common.TINY_CASES:
+            got = _tiny_forward(full_model, name)
+        else:
+            out = run_full(full_model, S, dgi, cgi, hw=hw)
+            toks, _ = run_agg(full_model, S, dgi, cgi, hw=hw)
+            assert all(torch.isfinite(t).all() for t in toks)
+            got = {"tok_L%d" % l: common.sample_tokens([t.cpu() for t in toks], l) for l in common.TOK_LAYERS}
+            got["pose_enc"] = out["pose_enc"].cpu()
+            got["depth"] = out["depth"][0, :, ::37, ::37, 0].cpu()
+            got["depth_conf"] = out["depth_conf"][0, :, ::37, ::37].cpu()
+            got["world_points"] = out["world_points"][0, :, ::37, ::37].cpu()
+            got["world_points_conf"] = out["world_points_conf"][0, :, ::37, ::37].cpu()
         for k in keys:
+            assert torch.isfinite(torch.as_tensor(got[k])).all(), (tag, k)
             rows[k][tag] = (common.max_rel(got[k], gold[k]), _rms_rel(got[k], gold[k]))
             rows[k][tag + "_vs_twin"] = common.max_rel(got[k], twin[k])
     full_model.set_compute_dtype(torch.float32)
@@ -701,3 +707,80 @@ def test_early_dpt_levels_are_bit_identical_to_the_late_order():
             del outs
             torch.cuda.empty_cache()
     m.early_dpt_levels = True
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Tiny and long patch grids at FULL depth against the reference fixtures of oracle/gen_golden_tiny.py (common.TINY_CASES:
+# 14 x 14 = one patch ... 14 x 1778 = the 127-patch RoPE limit), on the module's one full model, through OmniVGGT.forward.
+# The fixtures hold all token rows of TOK_LAYERS, pose_enc_list and the dense maps whole; gen_golden_tiny.sample is applied
+# to the device result, so both sides are cut the same way.
+# ----------------------------------------------------------------------------------------------------------------------
+def _tiny_forward(m, name):
+    import gen_golden_tiny as gt
+    import small_grids as sg
+    S, dgi, cgi, hw = common.case(name)
+    toks, out = sg.forward_raw(m, common.inputs_for(S, DEV, hw=hw), dgi, cgi)
+    assert all(torch.isfinite(t).all() for t in toks)
+    got = gt.sample([t.cpu() for t in toks], {k: ([p.cpu() for p in v] if k == "pose_enc_list" else v.cpu()) for k, v in out.items()}, hw, with_list=True)
+    got["tok_absmean"] = torch.tensor([float(t.abs().mean()) for t in toks]).numpy()
+    return got
+
+
+@pytest.mark.parametrize("name", list(common.TINY_CASES))
+@pytest.mark.parametrize("mode", ["f32", "f32x"])
+def test_tiny_grids_f32_modes_full_depth_vs_reference_golden(full_model, mode, name):
+    """f32 and split-f16 modes: all token rows of layers 0 / 4 / 11 / 17 / 23, the per-layer mean, pose_enc, every refinement step of it and
+    the four dense maps <= 1e-4 against the REAL reference."""
+    full_model.set_compute_dtype(L.F32X if mode == "f32x" else torch.float32)
+    try:
+        got = _tiny_forward(full_model, name)
+    finally:
+        full_model.set_compute_dtype(torch.float32)
+    gold = common.load_golden(name)
+    errs = {k: common.max_rel(got[k], gold[k]) for k in gold}
+    print("%s full-depth %s: %s" % (mode, name, ", ".join("%s %.2e" % kv for kv in errs.items())))
+    assert all(got[k].shape == gold[k].shape for k in gold)
+    assert max(errs.values()) <= F32_TOL, errs
+
+
+def test_tiny_one_column_grid_low_precision_full_depth(full_model):
+    """t2_70x14_cam has no twin (the CPU autocast reference is not finite on one-column grids): bf16 / f16 at full depth are held to the
+    3e-2 / 5e-3 of the 16-bit modes outside the twin cases, on every stored tensor, against the f32 reference golden."""
+    name = "t2_70x14_cam"
+    gold = common.load_golden(name)
+    try:
+        for dtype, tag, tol in ((torch.bfloat16, "bf16", 3e-2), (torch.float16, "f16", 5e-3)):
+            full_model.set_compute_dtype(dtype)
+            got = _tiny_forward(full_model, name)
+            errs = {k: common.max_rel(got[k], gold[k]) for k in gold}
+            print("%s full-depth %s: %s" % (tag, name, ", ".join("%s %.2e" % kv for kv in errs.items())))
+            assert all(torch.isfinite(torch.as_tensor(got[k])).all() for k in gold)
+            assert max(errs.values()) <= tol, (tag, errs)
+    finally:
+        full_model.set_compute_dtype(torch.float32)
+
+
+def test_tiny_grids_take_the_early_dpt_levels_bit_identically(full_model):
+    """At the tiny / long grids the pyramid levels of layers 4 / 11 / 17 ARE started from the aggregator's layer hook (_begin_early_levels
+    hands out a hook and both heads want those layers), and the forward without them gives the same bytes -- 16-bit heads (bf16) and the
+    exact-f32 heads (f32 mode)."""
+    import small_grids as sg
+    try:
+        for dtype in (torch.bfloat16, torch.float32):
+            full_model.set_compute_dtype(dtype)
+            for name in common.TINY_CASES:
+                S, dgi, cgi, hw = common.case(name)
+                inp = common.inputs_for(S, DEV, hw=hw)
+                full_model.early_dpt_levels = True
+                early, hook = full_model._begin_early_levels(inp["images"])
+                assert hook is not None and set(early) == {"depth", "point"}, (dtype, name)
+                assert [l for l in range(24) if early["depth"].wants(l)] == [4, 11, 17]
+                res = {}
+                for on in (True, False):
+                    full_model.early_dpt_levels = on
+                    res[on] = sg.to_host(sg.forward(full_model, inp, dgi, cgi))
+                    assert full_model.aggregator.layer_hook is None
+                assert sg.same_bytes(res[True], res[False]) == [], (dtype, name)
+    finally:
+        full_model.early_dpt_levels = True
+        full_model.set_compute_dtype(torch.float32)
