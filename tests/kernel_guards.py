@@ -6,6 +6,7 @@ guarded()            an output view inside a larger byte buffer pre-filled with 
 poison_*()           large finite values of alternating sign in the padding a kernel must not depend on
 elementwise_budget() |got - ref| <= u_out |ref| + c u_acc mag for EVERY element (gpu_selftest.report gates the tensor-global maximum only)
 *_budget()           the constants c, each derived from the rounding points of its kernel (never fitted to a kernel's output)
+conv_ref()           ovg_conv's float64 reference and magnitude (test_gpu_edges.py, test_gpu_head_edges.py, dpt_stages.py)
 upsample_window()    the 16-bit roundings a bilinear kernel may hold per element; dpt_tail_budget() carries them through the fused output stage
                      (test_dpt_tail_budget_host.py); camera_tables_budget() for ovg_camera_tables (test_camera_tables_budget_host.py)
 camera_*()           ovg_camera_head stage by stage from the buffers it leaves in its workspace: camera_ws_views() (the layout), camera_ksplit()
@@ -291,6 +292,32 @@ def qk_norm_rope_error(z, ez, w, b, eps, pos, cos, sin, scale=1.0):
     return scale * (rope_abs(ey) + MARGIN * 3 * U_ACC * rope_abs(y.abs()))
 
 
+# ---- ovg_conv (NHWC implicit GEMM) ---------------------------------------------------------------
+def conv_ref(x, w, bias, cout, k, stride, up, relu, a1, a2, pos):
+    """x [n, H, W, cin], w [rows, k k cin] taps-major, bias [cout] / a1 / a2 [n, OH, OW, cout] / pos = (pos_x [OW, cout/2], pos_y [OH, cout/2])
+    or None, all float64 (the values of the stored operands) -> (ref, mag): the convolution (up > 1: ConvTranspose with kernel = stride = up,
+    rows ordered (dy, dx, co)) + bias + adds + tables, ReLU'd if asked, and the magnitude sum |x||w| + |bias| + |adds| + |table| that the
+    accumulation's budget scales with."""
+    n, H, W, cin = x.shape
+    if up > 1:
+        y = (x.reshape(-1, cin) @ w.t()).reshape(n, H, W, up, up, cout).permute(0, 1, 3, 2, 4, 5).reshape(n, H * up, W * up, cout)
+        m = (x.abs().reshape(-1, cin) @ w.abs().t()).reshape(n, H, W, up, up, cout).permute(0, 1, 3, 2, 4, 5).reshape(n, H * up, W * up, cout)
+    else:
+        wt = w[:cout].reshape(cout, k, k, cin).permute(0, 3, 1, 2)
+        y = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), wt, None, stride=stride, padding=k // 2).permute(0, 2, 3, 1)
+        m = torch.nn.functional.conv2d(x.abs().permute(0, 3, 1, 2), wt.abs(), None, stride=stride, padding=k // 2).permute(0, 2, 3, 1)
+    y, m = y.contiguous(), m.contiguous()
+    for t in (bias, a1, a2):
+        if t is not None:
+            y, m = y + t, m + t.abs()
+    if pos is not None:
+        half = cout // 2
+        for arr, f in ((y, lambda t: t), (m, torch.abs)):
+            arr[..., :half] += f(pos[0])[None, None]
+            arr[..., half:] += f(pos[1])[None, :, None]
+    return (torch.relu(y) if relu else y), m
+
+
 # ---- bilinear resize (align_corners = True) ---------------------------------------------------
 # The specification both kernels document (csrc/ovg_head.hip upsample_kernel, csrc/ovg_dpt_tail.h xgeo / ygeo) and ATen implements:
 #   s = (in - 1) / (out - 1) an f32 quotient, f = s o an f32 product, i0 = min(int(f), in - 1), i1 = i0 + (i0 < in - 1), l = f - i0 (exact:
@@ -302,8 +329,13 @@ def qk_norm_rope_error(z, ez, w, b, eps, pos, cos, sin, scale=1.0):
 # < 2^24 are exact in float64). It moves l by up to half an ulp of f, and the window below is sharp enough to tell the two apart: the host
 # test uses it as a mutant, and on the MI355X ovg_upsample held the plain form on every one of 1.1e7 elements of a 148 -> 296 map while the
 # fused form left 0.3 % (bf16) / 1.8 % (f16) of them outside the window.
+# An output side of ONE pixel has no (out - 1) to divide by: the header of ovg_upsample documents s = 0 for it (source row / column 0 with
+# weight 1, what ATen's area_pixel_compute_scale gives for align_corners with an output size <= 1), whatever the input side.
 def _axis_spec(n_in, n_out, fused):
-    s = torch.tensor(float(n_in - 1), dtype=torch.float32) / torch.tensor(float(n_out - 1), dtype=torch.float32)
+    if n_out > 1:
+        s = torch.tensor(float(n_in - 1), dtype=torch.float32) / torch.tensor(float(n_out - 1), dtype=torch.float32)
+    else:
+        s = torch.zeros((), dtype=torch.float32)
     o = torch.arange(n_out, dtype=torch.float32)
     f = s * o
     i0 = f.to(torch.int64).clamp_max(n_in - 1)

@@ -798,25 +798,7 @@ def test_attn_merge_and_heads_to_tokens_short_rows_strided(mode):
 # =============================================================================================
 # head kernels
 # =============================================================================================
-def _conv_ref(x, w, bias, cout, k, stride, up, relu, a1, a2, pos):
-    n, H, W, cin = x.shape
-    if up > 1:
-        y = (x.reshape(-1, cin) @ w.t()).reshape(n, H, W, up, up, cout).permute(0, 1, 3, 2, 4, 5).reshape(n, H * up, W * up, cout)
-        m = (x.abs().reshape(-1, cin) @ w.abs().t()).reshape(n, H, W, up, up, cout).permute(0, 1, 3, 2, 4, 5).reshape(n, H * up, W * up, cout)
-    else:
-        wt = w[:cout].reshape(cout, k, k, cin).permute(0, 3, 1, 2)
-        y = F.conv2d(x.permute(0, 3, 1, 2), wt, None, stride=stride, padding=k // 2).permute(0, 2, 3, 1)
-        m = F.conv2d(x.abs().permute(0, 3, 1, 2), wt.abs(), None, stride=stride, padding=k // 2).permute(0, 2, 3, 1)
-    y, m = y.contiguous(), m.contiguous()
-    for t in (bias, a1, a2):
-        if t is not None:
-            y, m = y + t, m + t.abs()
-    if pos is not None:
-        half = cout // 2
-        for arr, f in ((y, lambda t: t), (m, torch.abs)):
-            arr[..., :half] += f(pos[0])[None, None]
-            arr[..., half:] += f(pos[1])[None, :, None]
-    return (F.relu(y) if relu else y), m
+_conv_ref = kg.conv_ref          # the float64 reference and magnitude of ovg_conv (shared with dpt_stages.py)
 
 
 @pytest.mark.parametrize("mode", ["bf16", "f16", "f32"])
@@ -866,7 +848,7 @@ def test_conv_small_maps_guarded(mode):
 def test_upsample_edges_guarded(mode):
     g = torch.Generator().manual_seed(119)
     dt = MODES[mode]
-    for (H, W, OH, OW) in ((1, 1, 5, 7), (2, 3, 2, 3), (37, 28, 74, 56), (8, 8, 5, 5)):
+    for (H, W, OH, OW) in ((1, 1, 5, 7), (2, 3, 2, 3), (37, 28, 74, 56), (8, 8, 5, 5), (1, 3, 1, 5), (3, 1, 5, 1), (2, 3, 1, 1)):
         x = torch.randn(2, H, W, 64, generator=g).to(dt)
         slot = Slot.get((2, OH, OW, 64), dt, 72, tag="up")
         try:
