@@ -4,6 +4,7 @@ They only marshal device pointers, shapes and the current HIP stream into the pa
 structs of include/omnivggt_hip.h; every byte of compute happens in libomnivggt_hip.so.
 """
 import collections
+import math
 
 import torch
 
@@ -575,6 +576,128 @@ def camera_tables(extrinsics, intrinsics, index, S, hw, pose_w, pose_b, adapt_w,
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# geometry wrappers (unproject .. mesh_smooth). Each reads as: what it checks, what it allocates, how it fills the struct; the
+# checks below are the one implementation of each kind. The older wrappers (.. knn_normals) test the device first, the newer ones
+# test shapes first and the device last.
+# ---------------------------------------------------------------------------------------------------------------------------------
+_F32, _F64, _U8, _I32, _I64 = torch.float32, torch.float64, torch.uint8, torch.int32, torch.int64
+_F32_MAX = 3.4028234663852886e38
+
+
+def _ws_query(symbol, **dims):
+    """A host-only `*_workspace_bytes` query of the library -> bytes. Every integer must fit its C argument type (int32 / int64,
+    from L.SYMBOLS) and the library must not answer with a negative value."""
+    ctypes_ = L.SYMBOLS[symbol][1]
+    if all(-(1 << 8 * L.C.sizeof(ct) - 1) <= int(v) < 1 << 8 * L.C.sizeof(ct) - 1 for ct, v in zip(ctypes_, dims.values())):
+        b = getattr(L.load(), symbol)(*(int(v) for v in dims.values()))
+        if b >= 0:
+            return int(b)
+    raise L.OvgError("%s: unsupported (%s)" % (symbol, ", ".join("%s=%d" % kv for kv in dims.items())))
+
+
+def _tensor(what, t, name, dtype, shape=None, numel=None, min_numel=None, optional=False):
+    """t must be a contiguous `dtype` tensor of exactly `shape`, or of any shape with exactly `numel` / at least `min_numel` elements
+    (none of the three: any size). None passes only when optional."""
+    if t is None and optional:
+        return
+    ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+    if ok and shape is not None:
+        ok = tuple(t.shape) == tuple(shape)
+    if ok and numel is not None:
+        ok = t.numel() == numel
+    if ok and min_numel is not None:
+        ok = t.numel() >= min_numel
+    if not ok:
+        size = " %r" % (list(shape),) if shape is not None else " of %s elements" % numel if numel is not None else \
+            " of at least %s elements" % min_numel if min_numel is not None else ""
+        raise L.OvgError("%s: %s must be a contiguous %s tensor%s" % (what, name, str(dtype).replace("torch.", ""), size))
+
+
+def _rows(what, t, name, dtype, width):
+    """t must be a contiguous `dtype` tensor of any shape that holds `width` values per row -> the number of rows."""
+    _tensor(what, t, name, dtype)
+    if t.numel() % width:
+        raise L.OvgError("%s: %s must be a contiguous %s tensor of %d values per row" % (what, name, str(dtype).replace("torch.", ""), width))
+    return t.numel() // width
+
+
+def _table(what, t, name, dtype, width, min_rows=0, max_rows=None):
+    """t must be a contiguous `dtype` tensor [n, width] with min_rows <= n (< max_rows) -> n."""
+    _tensor(what, t, name, dtype)
+    if t.dim() != 2 or t.shape[1] != width or t.shape[0] < min_rows or (max_rows is not None and t.shape[0] >= max_rows):
+        bound = (", %d <= n" % min_rows if min_rows else "") + (" < %d" % max_rows if max_rows is not None else "")
+        raise L.OvgError("%s: %s must be a contiguous %s tensor [n, %d]%s" % (what, name, str(dtype).replace("torch.", ""), width, bound))
+    return int(t.shape[0])
+
+
+def _points(what, t, name, min_rows=0, max_rows=None):
+    """t must be a contiguous f32 tensor [n, 3] with min_rows <= n (< max_rows) -> n."""
+    return _table(what, t, name, _F32, 3, min_rows, max_rows)
+
+
+def _query_reference(what, query, reference, query_valid, reference_valid, exclude_self, origin=None, out_stats=None):
+    """The arguments the nearest-neighbour and grid searches share -> (nq, nr)."""
+    nq, nr = _points(what, query, "query"), _points(what, reference, "reference")
+    _tensor(what, query_valid, "query_valid", _U8, (nq,), optional=True)
+    _tensor(what, reference_valid, "reference_valid", _U8, (nr,), optional=True)
+    _tensor(what, origin, "origin", _F32, numel=3, optional=True)
+    if exclude_self and nq != nr:
+        raise L.OvgError("%s: exclude_self needs nq == nr (got %d, %d)" % (what, nq, nr))
+    _tensor(what, out_stats, "out_stats", _I64, numel=4, optional=True)
+    return nq, nr
+
+
+def _out(what, t, name, dtype, shape, device, any_shape=False):
+    """An output: allocated when None, else checked (any_shape: only for the element count of `shape`)."""
+    if t is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if any_shape:
+        _tensor(what, t, name, dtype, numel=math.prod(shape))
+    else:
+        _tensor(what, t, name, dtype, shape)
+    return t
+
+
+def _workspace(ws, need, device):
+    """The caller's workspace when it holds `need` bytes, else a fresh one."""
+    return torch.empty(need, device=device, dtype=_U8) if ws is None or nbytes(ws) < need else ws
+
+
+def _number(what, name, value, lo=None, hi=None, strict=False, f32=True):
+    """A host number (not a bool, not NaN) with lo <= value <= hi (strict: lo < value) -> float(value). f32: it is passed on as a
+    float32 and must be finite there; otherwise +-inf and any magnitude pass."""
+    ok = not isinstance(value, bool) and isinstance(value, (int, float)) and value == value
+    if ok and lo is not None:
+        ok = value > lo if strict else value >= lo
+    if ok and hi is not None:
+        ok = value <= hi
+    if ok and f32:
+        ok = abs(value) <= _F32_MAX
+    if ok:
+        try:
+            return float(value)
+        except OverflowError:                                                # an integer beyond float64
+            pass
+    rule = ("" if lo is None else " %s %r" % (">" if strict else ">=", lo)) + ("" if hi is None else " <= %r" % (hi,))
+    raise L.OvgError("%s: %s must be a %s%s, got %r" % (what, name, "finite float32 number" if f32 else "number (not NaN)", rule, value))
+
+
+def _int_in(what, name, value, lo, hi):
+    """A host integer (not a bool) with lo <= value < hi."""
+    if isinstance(value, bool) or not isinstance(value, int) or not lo <= value < hi:
+        raise L.OvgError("%s: %s must be an integer in [%d, %d), got %r" % (what, name, lo, hi, value))
+    return value
+
+
+def _capacity_buffers(what, buffers):
+    """The outputs of a SCATTER stage, buffers = (tensor, name, dtype, elements it must hold, required): nothing is asked of the
+    buffers of a zero capacity, and a buffer that is not required may be None."""
+    for t, name, dtype, need, required in buffers:
+        if need:
+            _tensor(what, t, name, dtype, min_numel=need, optional=not required)
+
+
 def unproject(depth, cam):
     """depth f32 [S,H,W], cam f32 [S,16] (cam-to-world R row-major, t, fu, fv, cu, cv) -> world points [S,H,W,3] f32."""
     _chk_dev(depth, cam)
@@ -586,26 +709,23 @@ def unproject(depth, cam):
 
 
 def percentile_workspace_bytes(n, ncols):
-    b = L.load().ovg_percentile_workspace_bytes(int(n), int(ncols))
-    if b < 0:
-        raise L.OvgError("ovg_percentile_workspace_bytes: unsupported (n=%d, ncols=%d)" % (n, ncols))
-    return int(b)
+    return _ws_query("ovg_percentile_workspace_bytes", n=n, ncols=ncols)
 
 
 def percentile(x, n, stride, col_stride, ncols, qs, mask=None, norm=False, ws=None):
     """numpy-2 linear percentiles `qs` (<= 4, in [0, 100]) of `ncols` (<= 4) f32 columns of x: key i of column c at element
     c * col_stride + i * stride (element offsets from x's data pointer). mask: optional contiguous f32 [n] (key * (mask > 0.1)).
     -> out [ncols, len(qs)] f32 on the device (and, with norm=True and two percentiles, the 0-d f32 norm of out[:, 1] - out[:, 0])."""
+    what = "percentile"
     _chk_dev(x, mask, ws)
-    if x.dtype != torch.float32 or (mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous())):
-        raise L.OvgError("percentile: x must be f32 and mask a contiguous f32 tensor")
+    if x.dtype != torch.float32:
+        raise L.OvgError("%s: x must be f32" % what)
+    _tensor(what, mask, "mask", _F32, optional=True)
     last = (ncols - 1) * col_stride + (n - 1) * stride
     if n < 1 or stride < 1 or col_stride < 0 or x.storage_offset() + last >= x.untyped_storage().nbytes() // 4 or \
             (mask is not None and mask.numel() < n):
-        raise L.OvgError("percentile: the strided columns (or the mask) reach outside the tensor")
-    need = percentile_workspace_bytes(n, ncols)
-    if ws is None or nbytes(ws) < need:
-        ws = torch.empty(need, device=x.device, dtype=torch.uint8)
+        raise L.OvgError("%s: the strided columns (or the mask) reach outside the tensor" % what)
+    ws = _workspace(ws, percentile_workspace_bytes(n, ncols), x.device)
     out = torch.empty(ncols, len(qs), device=x.device, dtype=torch.float32)
     nrm = torch.empty((), device=x.device, dtype=torch.float32) if norm else None
     p = L.PercentileParams()
@@ -618,10 +738,7 @@ def percentile(x, n, stride, col_stride, ncols, qs, mask=None, norm=False, ws=No
 
 
 def point_filter_workspace_bytes(n):
-    b = L.load().ovg_point_filter_workspace_bytes(int(n))
-    if b < 0:
-        raise L.OvgError("ovg_point_filter_workspace_bytes: unsupported (n=%d)" % n)
-    return int(b)
+    return _ws_query("ovg_point_filter_workspace_bytes", n=n)
 
 
 def point_filter(stage, conf, images, points, hw, ws, threshold=None, mask=None, min_conf=1e-5, flags=0, index_base=0,
@@ -630,20 +747,22 @@ def point_filter(stage, conf, images, points, hw, ws, threshold=None, mask=None,
     0-d / 1-element f32 device tensor or None (0), mask f32 [n] or None. stage L.PF_COUNT writes the int64 cloud size to out_count;
     L.PF_SCATTER writes the first `capacity` kept pixels (in pixel order) to out_points / out_colors / out_index from what the COUNT
     stage left in ws."""
+    what = "point_filter"
     _chk_dev(conf, images, points, ws, threshold, mask, out_count, out_points, out_colors, out_index)
-    for t in (conf, images, points, threshold, mask):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise L.OvgError("point_filter: conf / images / points / threshold / mask must be contiguous f32 tensors")
+    _tensor(what, conf, "conf", _F32)
     n = conf.numel()
-    if images.numel() != 3 * n or points.numel() != 3 * n or (mask is not None and mask.numel() != n) or hw <= 0 or n % hw:
-        raise L.OvgError("point_filter: images / points must hold 3 values per pixel, mask one, and hw divide the pixel count")
+    _tensor(what, images, "images", _F32, numel=3 * n)
+    _tensor(what, points, "points", _F32, numel=3 * n)
+    _tensor(what, threshold, "threshold", _F32, optional=True)
+    _tensor(what, mask, "mask", _F32, numel=n, optional=True)
+    if hw <= 0 or n % hw:
+        raise L.OvgError("%s: hw must be positive and divide the pixel count" % what)
     if stage & L.PF_SCATTER:
-        outs = ((out_points, torch.float32, 3), (out_colors, torch.uint8, 3), (out_index, torch.int64, 1))
-        for t, dt, k in outs:
-            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < k * capacity):
-                raise L.OvgError("point_filter: output buffers must be contiguous and hold `capacity` entries")
+        _tensor(what, out_points, "out_points", _F32, min_numel=3 * capacity, optional=True)
+        _tensor(what, out_colors, "out_colors", _U8, min_numel=3 * capacity, optional=True)
+        _tensor(what, out_index, "out_index", _I64, min_numel=capacity, optional=True)
     if out_count is not None and (out_count.dtype != torch.int64 or out_count.numel() < 1):
-        raise L.OvgError("point_filter: out_count must be an int64 device tensor")
+        raise L.OvgError("%s: out_count must be an int64 device tensor" % what)
     p = L.PointFilterParams()
     p.conf, p.mask, p.threshold, p.min_conf, p.flags = L.ptr(conf), L.ptr(mask), L.ptr(threshold), float(min_conf), int(flags)
     p.images, p.hw, p.points, p.n, p.stage = L.ptr(images), int(hw), L.ptr(points), n, int(stage)
@@ -654,10 +773,7 @@ def point_filter(stage, conf, images, points, hw, ws, threshold=None, mask=None,
 
 
 def voxel_downsample_workspace_bytes(n):
-    b = L.load().ovg_voxel_downsample_workspace_bytes(int(n))
-    if b < 0:
-        raise L.OvgError("ovg_voxel_downsample_workspace_bytes: unsupported (n=%d)" % n)
-    return int(b)
+    return _ws_query("ovg_voxel_downsample_workspace_bytes", n=n)
 
 
 def voxel_downsample(stage, points, voxel, ws, conf=None, colors=None, out_count=None, capacity=0, out_points=None, out_colors=None,
@@ -665,21 +781,17 @@ def voxel_downsample(stage, points, voxel, ws, conf=None, colors=None, out_count
     """ovg_voxel_downsample on contiguous device tensors: points f32 [n, 3], voxel a 0-d / 1-element f32 device tensor, conf f32 [n] or
     None, colors u8 [n, 3] or None. stage L.VG_COUNT writes (M', flags) to the two int64 of out_count; L.VG_SCATTER writes the first
     `capacity` winners (in input order) to out_points / out_colors / out_index from what the COUNT stage left in ws."""
+    what = "voxel_downsample"
     _chk_dev(points, voxel, ws, conf, colors, out_count, out_points, out_colors, out_index)
-    for t in (points, voxel, conf):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise L.OvgError("voxel_downsample: points / voxel / conf must be contiguous f32 tensors")
-    n = points.numel() // 3
-    if points.numel() != 3 * n or voxel.numel() != 1 or (conf is not None and conf.numel() != n) or \
-            (colors is not None and (colors.dtype != torch.uint8 or not colors.is_contiguous() or colors.numel() != 3 * n)):
-        raise L.OvgError("voxel_downsample: points / colors must hold 3 values per point, conf one, voxel exactly one")
+    n = _rows(what, points, "points", _F32, 3)
+    _tensor(what, voxel, "voxel", _F32, numel=1)
+    _tensor(what, conf, "conf", _F32, numel=n, optional=True)
+    _tensor(what, colors, "colors", _U8, numel=3 * n, optional=True)
     if stage & L.VG_SCATTER:
-        outs = ((out_points, torch.float32, 3), (out_colors, torch.uint8, 3), (out_index, torch.int64, 1))
-        for t, dt, k in outs:
-            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < k * capacity):
-                raise L.OvgError("voxel_downsample: output buffers must be contiguous and hold `capacity` entries")
-    if out_count is not None and (out_count.dtype != torch.int64 or out_count.numel() < 2 or not out_count.is_contiguous()):
-        raise L.OvgError("voxel_downsample: out_count must be a contiguous int64 device tensor of two elements")
+        _tensor(what, out_points, "out_points", _F32, min_numel=3 * capacity, optional=True)
+        _tensor(what, out_colors, "out_colors", _U8, min_numel=3 * capacity, optional=True)
+        _tensor(what, out_index, "out_index", _I64, min_numel=capacity, optional=True)
+    _tensor(what, out_count, "out_count", _I64, min_numel=2, optional=True)
     p = L.VoxelDownsampleParams()
     p.points, p.conf, p.colors, p.voxel, p.n, p.stage = L.ptr(points), L.ptr(conf), L.ptr(colors), L.ptr(voxel), n, int(stage)
     p.capacity = int(capacity)
@@ -689,13 +801,7 @@ def voxel_downsample(stage, points, voxel, ws, conf=None, colors=None, out_count
 
 
 def render_workspace_bytes(V, H, W):
-    for v in (V, H, W):
-        if not -(1 << 31) <= int(v) < (1 << 31):
-            raise L.OvgError("ovg_render_workspace_bytes: unsupported (V=%d, H=%d, W=%d)" % (V, H, W))
-    b = L.load().ovg_render_workspace_bytes(int(V), int(H), int(W))
-    if b < 0:
-        raise L.OvgError("ovg_render_workspace_bytes: unsupported (V=%d, H=%d, W=%d)" % (V, H, W))
-    return int(b)
+    return _ws_query("ovg_render_workspace_bytes", V=V, H=H, W=W)
 
 
 def render_points(points, colors, cams, H, W, radius=1, near=1e-3, background=(255, 255, 255), depth=True, index=False, ws=None,
@@ -703,16 +809,11 @@ def render_points(points, colors, cams, H, W, radius=1, near=1e-3, background=(2
     """ovg_render_points on contiguous device tensors: points f32 [n, 3], colors u8 [n, 3], cams f32 [V, 16] (world-to-camera rotation
     row-major, translation, fx, fy, cx, cy). -> (rgb u8 [V, H, W, 3], depth f32 [V, H, W] or None, index int64 [V, H, W] or None),
     allocated here; ws: an optional uint8 device tensor of at least render_workspace_bytes(V, H, W) bytes. Nothing is read back."""
+    what = "render_points"
     _chk_dev(points, colors, cams, ws)
-    if points.dtype != torch.float32 or cams.dtype != torch.float32 or colors.dtype != torch.uint8 or \
-            not (points.is_contiguous() and colors.is_contiguous() and cams.is_contiguous()):
-        raise L.OvgError("render_points: points / cams must be contiguous f32 tensors, colors a contiguous u8 tensor")
-    n, V = points.numel() // 3, cams.numel() // 16
-    if points.numel() != 3 * n or colors.numel() != 3 * n or cams.numel() != 16 * V:
-        raise L.OvgError("render_points: points / colors must hold 3 values per point, cams 16 per view")
-    need = render_workspace_bytes(V, H, W)
-    if ws is None or nbytes(ws) < need:
-        ws = torch.empty(need, device=cams.device, dtype=torch.uint8)
+    n, V = _rows(what, points, "points", _F32, 3), _rows(what, cams, "cams", _F32, 16)
+    _tensor(what, colors, "colors", _U8, numel=3 * n)
+    ws = _workspace(ws, render_workspace_bytes(V, H, W), cams.device)
     rgb = torch.empty(V, H, W, 3, device=cams.device, dtype=torch.uint8)
     dep = torch.empty(V, H, W, device=cams.device, dtype=torch.float32) if depth else None
     idx = torch.empty(V, H, W, device=cams.device, dtype=torch.int64) if index else None
@@ -727,13 +828,7 @@ def render_points(points, colors, cams, H, W, radius=1, near=1e-3, background=(2
 
 
 def render_mesh_workspace_bytes(V, H, W):
-    for v in (V, H, W):
-        if not -(1 << 31) <= int(v) < (1 << 31):
-            raise L.OvgError("ovg_render_mesh_workspace_bytes: unsupported (V=%d, H=%d, W=%d)" % (V, H, W))
-    b = L.load().ovg_render_mesh_workspace_bytes(int(V), int(H), int(W))
-    if b < 0:
-        raise L.OvgError("ovg_render_mesh_workspace_bytes: unsupported (V=%d, H=%d, W=%d)" % (V, H, W))
-    return int(b)
+    return _ws_query("ovg_render_mesh_workspace_bytes", V=V, H=H, W=W)
 
 
 def render_mesh(vertices, faces, cams, H, W, normals=None, colors=None, shading=L.MESH_SHADE_HEADLIGHT, cull=L.MESH_CULL_NONE, near=1e-3,
@@ -742,20 +837,12 @@ def render_mesh(vertices, faces, cams, H, W, normals=None, colors=None, shading=
     [M, 3], cams f32 [V, 16] (as for render_points). -> (rgb u8 [V, H, W, 3], depth f32 [V, H, W] or None, index int64 [V, H, W] or
     None), allocated here unless out = (rgb, depth or None, index or None) gives them; ws: an optional uint8 device tensor of at
     least render_mesh_workspace_bytes(V, H, W) bytes. Nothing is read back."""
+    what = "render_mesh"
     _chk_dev(vertices, faces, cams, normals, colors, ws)
-    if vertices.dtype != torch.float32 or cams.dtype != torch.float32 or faces.dtype != torch.int32 or \
-            not (vertices.is_contiguous() and faces.is_contiguous() and cams.is_contiguous()):
-        raise L.OvgError("render_mesh: vertices / cams must be contiguous f32 tensors, faces a contiguous int32 tensor")
-    M, F, V = vertices.numel() // 3, faces.numel() // 3, cams.numel() // 16
-    if vertices.numel() != 3 * M or faces.numel() != 3 * F or cams.numel() != 16 * V:
-        raise L.OvgError("render_mesh: vertices / faces must hold 3 values per row, cams 16 per view")
-    if normals is not None and (normals.dtype != torch.float32 or not normals.is_contiguous() or normals.numel() != 3 * M):
-        raise L.OvgError("render_mesh: normals must be a contiguous f32 tensor of 3 values per vertex")
-    if colors is not None and (colors.dtype != torch.uint8 or not colors.is_contiguous() or colors.numel() != 3 * M):
-        raise L.OvgError("render_mesh: colors must be a contiguous u8 tensor of 3 values per vertex")
-    need = render_mesh_workspace_bytes(V, H, W)
-    if ws is None or nbytes(ws) < need:
-        ws = torch.empty(need, device=cams.device, dtype=torch.uint8)
+    M, F, V = _rows(what, vertices, "vertices", _F32, 3), _rows(what, faces, "faces", _I32, 3), _rows(what, cams, "cams", _F32, 16)
+    _tensor(what, normals, "normals", _F32, numel=3 * M, optional=True)
+    _tensor(what, colors, "colors", _U8, numel=3 * M, optional=True)
+    ws = _workspace(ws, render_mesh_workspace_bytes(V, H, W), cams.device)
     if out is not None:
         rgb, dep, idx = out
     else:
@@ -776,13 +863,7 @@ def render_mesh(vertices, faces, cams, H, W, normals=None, colors=None, shading=
 
 
 def consistency_workspace_bytes(S, H, W):
-    for v in (S, H, W):
-        if not -(1 << 31) <= int(v) < (1 << 31):
-            raise L.OvgError("ovg_consistency_workspace_bytes: unsupported (S=%d, H=%d, W=%d)" % (S, H, W))
-    b = L.load().ovg_consistency_workspace_bytes(int(S), int(H), int(W))
-    if b < 0:
-        raise L.OvgError("ovg_consistency_workspace_bytes: unsupported (S=%d, H=%d, W=%d)" % (S, H, W))
-    return int(b)
+    return _ws_query("ovg_consistency_workspace_bytes", S=S, H=H, W=W)
 
 
 def multiview_consistency(points, cams, tol, near=1e-3, valid=None, src_first=0, src_count=None, occluded=False, ws=None,
@@ -792,22 +873,21 @@ def multiview_consistency(points, cams, tol, near=1e-3, valid=None, src_first=0,
     src_first + src_count - 1 (all S by default), allocated here; ws: an optional uint8 device tensor of at least
     consistency_workspace_bytes(S, H, W) bytes (with L.MVC_KEEP_MAP in flags: the one an earlier call on the same inputs filled).
     Nothing is read back."""
+    what = "multiview_consistency"
     _chk_dev(points, cams, valid, ws)
-    if points.dtype != torch.float32 or cams.dtype != torch.float32 or not (points.is_contiguous() and cams.is_contiguous()):
-        raise L.OvgError("multiview_consistency: points / cams must be contiguous f32 tensors")
-    if points.dim() != 4 or points.shape[3] != 3 or cams.numel() != 16 * points.shape[0]:
-        raise L.OvgError("multiview_consistency: points must be [S, H, W, 3], cams hold 16 values per view")
+    _tensor(what, points, "points", _F32)
+    if points.dim() != 4 or points.shape[3] != 3:
+        raise L.OvgError("%s: points must be [S, H, W, 3]" % what)
     S, H, W = (int(v) for v in points.shape[:3])
-    if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or tuple(valid.shape) != (S, H, W)):
-        raise L.OvgError("multiview_consistency: valid must be a contiguous u8 tensor [S, H, W]")
+    _tensor(what, cams, "cams", _F32, numel=16 * S)
+    _tensor(what, valid, "valid", _U8, (S, H, W), optional=True)
     n = S - src_first if src_count is None else int(src_count)
     if not (0 <= src_first < S and 0 < n <= S - src_first):
-        raise L.OvgError("multiview_consistency: source views %d .. %d outside [0, %d)" % (src_first, src_first + n - 1, S))
+        raise L.OvgError("%s: source views %d .. %d outside [0, %d)" % (what, src_first, src_first + n - 1, S))
     need = consistency_workspace_bytes(S, H, W)
-    if ws is None or nbytes(ws) < need:
-        if flags & L.MVC_KEEP_MAP:
-            raise L.OvgError("multiview_consistency: MVC_KEEP_MAP needs the workspace of the call that computed the maps")
-        ws = torch.empty(need, device=points.device, dtype=torch.uint8)
+    if (ws is None or nbytes(ws) < need) and flags & L.MVC_KEEP_MAP:
+        raise L.OvgError("%s: MVC_KEEP_MAP needs the workspace of the call that computed the maps" % what)
+    ws = _workspace(ws, need, points.device)
     sup = torch.empty(n, H, W, device=points.device, dtype=torch.int16)
     vio = torch.empty(n, H, W, device=points.device, dtype=torch.int16)
     occ = torch.empty(n, H, W, device=points.device, dtype=torch.int16) if occluded else None
@@ -820,13 +900,7 @@ def multiview_consistency(points, cams, tol, near=1e-3, valid=None, src_first=0,
 
 
 def nn_workspace_bytes(nq, nr):
-    for v in (nq, nr):
-        if not -(1 << 63) <= int(v) < (1 << 63):
-            raise L.OvgError("ovg_nn_workspace_bytes: unsupported (nq=%d, nr=%d)" % (nq, nr))
-    b = L.load().ovg_nn_workspace_bytes(int(nq), int(nr))
-    if b < 0:
-        raise L.OvgError("ovg_nn_workspace_bytes: unsupported (nq=%d, nr=%d)" % (nq, nr))
-    return int(b)
+    return _ws_query("ovg_nn_workspace_bytes", nq=nq, nr=nr)
 
 
 def nearest_neighbours(query, reference, query_valid=None, reference_valid=None, exclude_self=False, splits=0, ws=None, index=None,
@@ -836,26 +910,12 @@ def nearest_neighbours(query, reference, query_valid=None, reference_valid=None,
     ties; with exclude_self, nq == nr and reference i is skipped for query i), -1 / +inf where there is none. splits: 0 lets the
     library choose, any other value gives the same bytes; ws: an optional uint8 device tensor of at least nn_workspace_bytes(nq, nr)
     bytes; index / sqdist: optional outputs to write into. Nothing is read back."""
+    what = "nearest_neighbours"
     _chk_dev(query, reference, query_valid, reference_valid, ws, index, sqdist)
-    for t, name in ((query, "query"), (reference, "reference")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
-            raise L.OvgError("nearest_neighbours: %s must be a contiguous f32 tensor [n, 3]" % name)
-    nq, nr = int(query.shape[0]), int(reference.shape[0])
-    for v, n, name in ((query_valid, nq, "query_valid"), (reference_valid, nr, "reference_valid")):
-        if v is not None and (v.dtype != torch.uint8 or not v.is_contiguous() or tuple(v.shape) != (n,)):
-            raise L.OvgError("nearest_neighbours: %s must be a contiguous u8 tensor [%d]" % (name, n))
-    if exclude_self and nq != nr:
-        raise L.OvgError("nearest_neighbours: exclude_self needs nq == nr (got %d, %d)" % (nq, nr))
-    need = nn_workspace_bytes(nq, nr)
-    if ws is None or nbytes(ws) < need:
-        ws = torch.empty(need, device=query.device, dtype=torch.uint8)
-    if index is None:
-        index = torch.empty(nq, device=query.device, dtype=torch.int32)
-    if sqdist is None:
-        sqdist = torch.empty(nq, device=query.device, dtype=torch.float32)
-    if index.dtype != torch.int32 or sqdist.dtype != torch.float32 or index.numel() != nq or sqdist.numel() != nq or \
-            not (index.is_contiguous() and sqdist.is_contiguous()):
-        raise L.OvgError("nearest_neighbours: index / sqdist must be contiguous int32 / f32 tensors [%d]" % nq)
+    nq, nr = _query_reference(what, query, reference, query_valid, reference_valid, exclude_self)
+    ws = _workspace(ws, nn_workspace_bytes(nq, nr), query.device)
+    index = _out(what, index, "index", _I32, (nq,), query.device, any_shape=True)
+    sqdist = _out(what, sqdist, "sqdist", _F32, (nq,), query.device, any_shape=True)
     p = L.NnParams()
     p.query, p.reference, p.query_valid, p.reference_valid = L.ptr(query), L.ptr(reference), L.ptr(query_valid), L.ptr(reference_valid)
     p.nq, p.nr, p.flags, p.splits = nq, nr, L.NN_EXCLUDE_SAME_INDEX if exclude_self else 0, int(splits)
@@ -865,13 +925,7 @@ def nearest_neighbours(query, reference, query_valid=None, reference_valid=None,
 
 
 def fps_workspace_bytes(batch, n, npoint):
-    for v in (batch, n, npoint):
-        if not -(1 << 63) <= int(v) < (1 << 63):
-            raise L.OvgError("ovg_fps_workspace_bytes: unsupported (batch=%d, n=%d, npoint=%d)" % (batch, n, npoint))
-    b = L.load().ovg_fps_workspace_bytes(int(batch), int(n), int(npoint))
-    if b < 0:
-        raise L.OvgError("ovg_fps_workspace_bytes: unsupported (batch=%d, n=%d, npoint=%d)" % (batch, n, npoint))
-    return int(b)
+    return _ws_query("ovg_fps_workspace_bytes", batch=batch, n=n, npoint=npoint)
 
 
 def farthest_point_sample(points, npoint, valid=None, first=0, include_last=False, path=0, ws=None, index=None, sqdist=None, distance=None):
@@ -882,28 +936,20 @@ def farthest_point_sample(points, npoint, valid=None, first=0, include_last=Fals
     force a form; all give the same bytes. ws: an optional uint8 device tensor of at least fps_workspace_bytes(B, N, npoint) bytes;
     index / sqdist: optional outputs to write into; distance: None, or True to allocate, or an f32 [B, N] tensor to fill with every
     point's squared distance to the nearest sample (returned as the third value, else None). Nothing is read back."""
+    what = "farthest_point_sample"
     _chk_dev(points, valid, ws, index, sqdist, None if isinstance(distance, bool) else distance)
-    if points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 3 or points.shape[2] != 3:
-        raise L.OvgError("farthest_point_sample: points must be a contiguous f32 tensor [B, N, 3]")
+    _tensor(what, points, "points", _F32)
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise L.OvgError("%s: points must be [B, N, 3]" % what)
     B, N, npoint = int(points.shape[0]), int(points.shape[1]), int(npoint)
-    if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or tuple(valid.shape) != (B, N)):
-        raise L.OvgError("farthest_point_sample: valid must be a contiguous u8 tensor [%d, %d]" % (B, N))
-    need = fps_workspace_bytes(B, N, npoint)
-    if ws is None or nbytes(ws) < need:
-        ws = torch.empty(need, device=points.device, dtype=torch.uint8)
-    if index is None:
-        index = torch.empty(B, npoint, device=points.device, dtype=torch.int32)
-    if sqdist is None:
-        sqdist = torch.empty(B, npoint, device=points.device, dtype=torch.float32)
-    if index.dtype != torch.int32 or sqdist.dtype != torch.float32 or index.numel() != B * npoint or sqdist.numel() != B * npoint or \
-            not (index.is_contiguous() and sqdist.is_contiguous()):
-        raise L.OvgError("farthest_point_sample: index / sqdist must be contiguous int32 / f32 tensors [%d, %d]" % (B, npoint))
-    if distance is True:
-        distance = torch.empty(B, N, device=points.device, dtype=torch.float32)
-    elif distance is False:
+    _tensor(what, valid, "valid", _U8, (B, N), optional=True)
+    ws = _workspace(ws, fps_workspace_bytes(B, N, npoint), points.device)
+    index = _out(what, index, "index", _I32, (B, npoint), points.device, any_shape=True)
+    sqdist = _out(what, sqdist, "sqdist", _F32, (B, npoint), points.device, any_shape=True)
+    if distance is None or distance is False:
         distance = None
-    if distance is not None and (distance.dtype != torch.float32 or distance.numel() != B * N or not distance.is_contiguous()):
-        raise L.OvgError("farthest_point_sample: distance must be a contiguous f32 tensor [%d, %d]" % (B, N))
+    else:
+        distance = _out(what, None if distance is True else distance, "distance", _F32, (B, N), points.device, any_shape=True)
     p = L.FpsParams()
     p.points, p.valid, p.batch, p.n, p.npoint, p.first = L.ptr(points), L.ptr(valid), B, N, npoint, int(first)
     p.flags, p.path = L.FPS_INCLUDE_LAST if include_last else 0, int(path)
@@ -915,7 +961,6 @@ def farthest_point_sample(points, npoint, valid=None, first=0, include_last=Fals
 def radius_reach(radius_sq):
     """REACH of include/omnivggt_hip.h for a float32 radius_sq: the float32 just above sqrt((double)radius_sq) (1 + 2^-20). The box of
     cells a query scans spans +-REACH per axis, and REACH is the smallest cell edge ovg_radius_search accepts."""
-    import math
     import struct
     r2 = struct.unpack("f", struct.pack("f", float(radius_sq)))[0]
     v = math.sqrt(r2) * (1.0 + 2.0 ** -20)
@@ -926,13 +971,7 @@ def radius_reach(radius_sq):
 
 
 def radius_workspace_bytes(nq, nr):
-    for v in (nq, nr):
-        if not -(1 << 63) <= int(v) < (1 << 63):
-            raise L.OvgError("ovg_radius_workspace_bytes: unsupported (nq=%d, nr=%d)" % (nq, nr))
-    b = L.load().ovg_radius_workspace_bytes(int(nq), int(nr))
-    if b < 0:
-        raise L.OvgError("ovg_radius_workspace_bytes: unsupported (nq=%d, nr=%d)" % (nq, nr))
-    return int(b)
+    return _ws_query("ovg_radius_workspace_bytes", nq=nq, nr=nr)
 
 
 def radius_search(stage, query, reference, radius_sq, cell, ws, query_valid=None, reference_valid=None, origin=None, exclude_self=False,
@@ -944,30 +983,16 @@ def radius_search(stage, query, reference, radius_sq, cell, ws, query_valid=None
     allocated when None); L.RS_SEARCH writes count int32 [nq], index int32 [nq] and sqdist f32 [nq] (allocated when None) -- or nothing
     at all when the candidate pairs exceed max_pairs, which out_stats (if given) then reports as L.RS_OVER_BUDGET.
     -> (out_stats, count, index, sqdist), None for what the stage does not write. Nothing is read back."""
+    what = "radius_search"
     _chk_dev(query, reference, ws, query_valid, reference_valid, origin, out_stats, count, index, sqdist)
-    for t, name in ((query, "query"), (reference, "reference")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
-            raise L.OvgError("radius_search: %s must be a contiguous f32 tensor [n, 3]" % name)
-    nq, nr = int(query.shape[0]), int(reference.shape[0])
-    for v, n, name in ((query_valid, nq, "query_valid"), (reference_valid, nr, "reference_valid")):
-        if v is not None and (v.dtype != torch.uint8 or not v.is_contiguous() or tuple(v.shape) != (n,)):
-            raise L.OvgError("radius_search: %s must be a contiguous u8 tensor [%d]" % (name, n))
-    if origin is not None and (origin.dtype != torch.float32 or not origin.is_contiguous() or origin.numel() != 3):
-        raise L.OvgError("radius_search: origin must be a contiguous f32 tensor of three elements")
-    if exclude_self and nq != nr:
-        raise L.OvgError("radius_search: exclude_self needs nq == nr (got %d, %d)" % (nq, nr))
+    nq, nr = _query_reference(what, query, reference, query_valid, reference_valid, exclude_self, origin, out_stats)
     stage = int(stage)
     if stage & L.RS_BUILD and out_stats is None:
         out_stats = torch.empty(4, device=query.device, dtype=torch.int64)
-    if out_stats is not None and (out_stats.dtype != torch.int64 or out_stats.numel() != 4 or not out_stats.is_contiguous()):
-        raise L.OvgError("radius_search: out_stats must be a contiguous int64 tensor of four elements")
     if stage & L.RS_SEARCH:
-        count = torch.empty(nq, device=query.device, dtype=torch.int32) if count is None else count
-        index = torch.empty(nq, device=query.device, dtype=torch.int32) if index is None else index
-        sqdist = torch.empty(nq, device=query.device, dtype=torch.float32) if sqdist is None else sqdist
-        for t, dt in ((count, torch.int32), (index, torch.int32), (sqdist, torch.float32)):
-            if t.dtype != dt or t.numel() != nq or not t.is_contiguous():
-                raise L.OvgError("radius_search: count / index / sqdist must be contiguous int32 / int32 / f32 tensors [%d]" % nq)
+        count = _out(what, count, "count", _I32, (nq,), query.device, any_shape=True)
+        index = _out(what, index, "index", _I32, (nq,), query.device, any_shape=True)
+        sqdist = _out(what, sqdist, "sqdist", _F32, (nq,), query.device, any_shape=True)
     else:
         count = index = sqdist = None
     p = L.RadiusParams()
@@ -988,29 +1013,15 @@ def knn_search(query, reference, radius_sq, cell, ws, k, query_valid=None, refer
     first, equal distances in ascending index, -1 / +inf from rank min(k, count) on -- or nothing at all when the candidate pairs
     exceed max_pairs or ws holds no grid, which out_stats (int64 [4], if given) then reports as L.RS_OVER_BUDGET / L.RS_NOT_BUILT.
     -> (out_stats, count, index, sqdist). Nothing is read back."""
+    what = "knn_search"
     _chk_dev(query, reference, ws, query_valid, reference_valid, origin, out_stats, count, index, sqdist)
-    for t, name in ((query, "query"), (reference, "reference")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
-            raise L.OvgError("knn_search: %s must be a contiguous f32 tensor [n, 3]" % name)
-    nq, nr, k = int(query.shape[0]), int(reference.shape[0]), int(k)
+    nq, nr = _query_reference(what, query, reference, query_valid, reference_valid, exclude_self, origin, out_stats)
+    k = int(k)
     if not 1 <= k <= L.KNN_MAX_K:
-        raise L.OvgError("knn_search: k must be in [1, %d], got %d" % (L.KNN_MAX_K, k))
-    for v, n, name in ((query_valid, nq, "query_valid"), (reference_valid, nr, "reference_valid")):
-        if v is not None and (v.dtype != torch.uint8 or not v.is_contiguous() or tuple(v.shape) != (n,)):
-            raise L.OvgError("knn_search: %s must be a contiguous u8 tensor [%d]" % (name, n))
-    if origin is not None and (origin.dtype != torch.float32 or not origin.is_contiguous() or origin.numel() != 3):
-        raise L.OvgError("knn_search: origin must be a contiguous f32 tensor of three elements")
-    if exclude_self and nq != nr:
-        raise L.OvgError("knn_search: exclude_self needs nq == nr (got %d, %d)" % (nq, nr))
-    if out_stats is not None and (out_stats.dtype != torch.int64 or out_stats.numel() != 4 or not out_stats.is_contiguous()):
-        raise L.OvgError("knn_search: out_stats must be a contiguous int64 tensor of four elements")
-    count = torch.empty(nq, device=query.device, dtype=torch.int32) if count is None else count
-    index = torch.empty(nq, k, device=query.device, dtype=torch.int32) if index is None else index
-    sqdist = torch.empty(nq, k, device=query.device, dtype=torch.float32) if sqdist is None else sqdist
-    for t, dt, n in ((count, torch.int32, nq), (index, torch.int32, nq * k), (sqdist, torch.float32, nq * k)):
-        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
-            raise L.OvgError("knn_search: count / index / sqdist must be contiguous int32 [%d] / int32 [%d, %d] / f32 [%d, %d] tensors"
-                             % (nq, nq, k, nq, k))
+        raise L.OvgError("%s: k must be in [1, %d], got %d" % (what, L.KNN_MAX_K, k))
+    count = _out(what, count, "count", _I32, (nq,), query.device, any_shape=True)
+    index = _out(what, index, "index", _I32, (nq, k), query.device, any_shape=True)
+    sqdist = _out(what, sqdist, "sqdist", _F32, (nq, k), query.device, any_shape=True)
     p = L.KnnParams()
     p.query, p.reference, p.query_valid, p.reference_valid = L.ptr(query), L.ptr(reference), L.ptr(query_valid), L.ptr(reference_valid)
     p.origin, p.nq, p.nr, p.radius_sq, p.cell = L.ptr(origin), nq, nr, float(radius_sq), float(cell)
@@ -1031,26 +1042,16 @@ def cluster(points, radius_sq, cell, ws, min_neighbours, valid=None, origin=None
     at all when the candidate pairs exceed max_pairs or ws holds no grid, which out_stats (int64 [4], if given) then reports as
     L.RS_OVER_BUDGET / L.RS_NOT_BUILT; L.CL_INTERNAL there means the union-find broke its own bounds (a bug: no result).
     -> (out_stats, root, kind, degree). Nothing is read back."""
-    deg = None if isinstance(degree, bool) else degree
-    _chk_dev(points, ws, valid, origin, out_stats, root, kind, deg)
-    if points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3:
-        raise L.OvgError("cluster: points must be a contiguous f32 tensor [n, 3]")
-    n = int(points.shape[0])
-    if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, int) or not 0 <= min_neighbours < 1 << 31:
-        raise L.OvgError("cluster: min_neighbours must be an integer in [0, 2^31), got %r" % (min_neighbours,))
-    if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or tuple(valid.shape) != (n,)):
-        raise L.OvgError("cluster: valid must be a contiguous u8 tensor [%d]" % n)
-    if origin is not None and (origin.dtype != torch.float32 or not origin.is_contiguous() or origin.numel() != 3):
-        raise L.OvgError("cluster: origin must be a contiguous f32 tensor of three elements")
-    if out_stats is not None and (out_stats.dtype != torch.int64 or out_stats.numel() != 4 or not out_stats.is_contiguous()):
-        raise L.OvgError("cluster: out_stats must be a contiguous int64 tensor of four elements")
-    root = torch.empty(n, device=points.device, dtype=torch.int32) if root is None else root
-    kind = torch.empty(n, device=points.device, dtype=torch.uint8) if kind is None else kind
-    if degree is None or degree is True:
-        deg = torch.empty(n, device=points.device, dtype=torch.int32)
-    for t, dt in ((root, torch.int32), (kind, torch.uint8), (deg, torch.int32)):
-        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
-            raise L.OvgError("cluster: root / kind / degree must be contiguous int32 / u8 / int32 tensors [%d]" % n)
+    what = "cluster"
+    _chk_dev(points, ws, valid, origin, out_stats, root, kind, None if isinstance(degree, bool) else degree)
+    n = _points(what, points, "points")
+    _int_in(what, "min_neighbours", min_neighbours, 0, 1 << 31)
+    _tensor(what, valid, "valid", _U8, (n,), optional=True)
+    _tensor(what, origin, "origin", _F32, numel=3, optional=True)
+    _tensor(what, out_stats, "out_stats", _I64, numel=4, optional=True)
+    root = _out(what, root, "root", _I32, (n,), points.device, any_shape=True)
+    kind = _out(what, kind, "kind", _U8, (n,), points.device, any_shape=True)
+    deg = None if degree is False else _out(what, None if degree is True else degree, "degree", _I32, (n,), points.device, any_shape=True)
     p = L.ClusterParams()
     p.points, p.valid, p.origin, p.n, p.radius_sq, p.cell = L.ptr(points), L.ptr(valid), L.ptr(origin), n, float(radius_sq), float(cell)
     p.min_neighbours, p.flags, p.max_pairs = min_neighbours, 0, int(max_pairs)
@@ -1066,30 +1067,20 @@ def knn_normals(query, reference, index, viewpoint=None, normal=None, curvature=
     covariance, used): the unit normal of the plane through every row's neighbours (zeros where fewer than three), towards the
     viewpoint. curvature (f32 [nq]), covariance (f64 [nq, 6]: xx xy xz yy yz zz) and used (int32 [nq]: neighbours per row) are
     written when given as tensors or True (allocated), else returned as None. Nothing is read back."""
+    what = "knn_normals"
     opt = lambda t: None if isinstance(t, bool) else t
     _chk_dev(query, reference, index, viewpoint, normal, opt(curvature), opt(covariance), opt(used))
-    for t, name in ((query, "query"), (reference, "reference")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
-            raise L.OvgError("knn_normals: %s must be a contiguous f32 tensor [n, 3]" % name)
-    nq, nr = int(query.shape[0]), int(reference.shape[0])
-    if index.dtype != torch.int32 or not index.is_contiguous() or index.dim() != 2 or index.shape[0] != nq or index.shape[1] < 1:
-        raise L.OvgError("knn_normals: index must be a contiguous int32 tensor [%d, k]" % nq)
+    nq, nr = _points(what, query, "query"), _points(what, reference, "reference")
+    _tensor(what, index, "index", _I32)
+    if index.dim() != 2 or index.shape[0] != nq or index.shape[1] < 1:
+        raise L.OvgError("%s: index must be [%d, k], k >= 1" % (what, nq))
     k = int(index.shape[1])
-    stride = 0
     if viewpoint is not None:
-        if viewpoint.dtype != torch.float32 or not viewpoint.is_contiguous() or tuple(viewpoint.shape) not in ((3,), (nq, 3)):
-            raise L.OvgError("knn_normals: viewpoint must be a contiguous f32 tensor [3] or [%d, 3]" % nq)
-        stride = 3 if viewpoint.dim() == 2 else 0
-    outs = []
-    for t, shape, dt, name in ((normal, (nq, 3), torch.float32, "normal"), (curvature, (nq,), torch.float32, "curvature"),
-                               (covariance, (nq, 6), torch.float64, "covariance"), (used, (nq,), torch.int32, "used")):
-        if t is True or (t is None and name == "normal"):
-            t = torch.empty(shape, device=query.device, dtype=dt)
-        elif t is False:
-            t = None
-        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
-            raise L.OvgError("knn_normals: %s must be a contiguous %s tensor %r" % (name, dt, shape))
-        outs.append(t)
+        _tensor(what, viewpoint, "viewpoint", _F32, (nq, 3) if isinstance(viewpoint, torch.Tensor) and viewpoint.dim() == 2 else (3,))
+    stride = 3 if viewpoint is not None and viewpoint.dim() == 2 else 0
+    outs = [_out(what, normal, "normal", _F32, (nq, 3), query.device)]
+    for t, name, dt, shape in ((curvature, "curvature", _F32, (nq,)), (covariance, "covariance", _F64, (nq, 6)), (used, "used", _I32, (nq,))):
+        outs.append(None if t is None or t is False else _out(what, opt(t), name, dt, shape, query.device))
     p = L.KnnNormalsParams()
     p.query, p.reference, p.index, p.viewpoint = L.ptr(query), L.ptr(reference), L.ptr(index), L.ptr(viewpoint)
     p.nq, p.nr, p.k, p.viewpoint_stride = nq, nr, k, stride
@@ -1099,19 +1090,7 @@ def knn_normals(query, reference, index, viewpoint=None, normal=None, curvature=
 
 
 def align_workspace_bytes(n):
-    if not -(1 << 63) <= int(n) < (1 << 63):
-        raise L.OvgError("ovg_align_workspace_bytes: unsupported (n=%d)" % n)
-    b = L.load().ovg_align_workspace_bytes(int(n))
-    if b < 0:
-        raise L.OvgError("ovg_align_workspace_bytes: unsupported (n=%d)" % n)
-    return int(b)
-
-
-def _align_tensor(what, t, name, dtype, shape, optional=False):
-    if t is None and optional:
-        return
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise L.OvgError("%s: %s must be a contiguous %s tensor %r" % (what, name, dtype, tuple(shape)))
+    return _ws_query("ovg_align_workspace_bytes", n=n)
 
 
 def align_moments(source, target, index=None, source_valid=None, target_valid=None, sqdist=None, max_sqdist=None, centre=None, ws=None,
@@ -1122,31 +1101,25 @@ def align_moments(source, target, index=None, source_valid=None, target_valid=No
     sums of a, b, a b^T, |a|^2, |b|^2 and |q - p|^2 over them in the fixed order of include/omnivggt_hip.h, so two calls give identical
     bytes. ws: an optional uint8 device tensor of at least align_workspace_bytes(n) bytes. Nothing is read back."""
     what = "align_moments"
-    for t, name in ((source, "source"), (target, "target")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
-            raise L.OvgError("%s: %s must be a contiguous f32 tensor [n, 3], n >= 1" % (what, name))
-    n, m = int(source.shape[0]), int(target.shape[0])
-    _align_tensor(what, index, "index", torch.int32, (n,), True)
+    n, m = _points(what, source, "source", 1), _points(what, target, "target", 1)
+    _tensor(what, index, "index", _I32, (n,), optional=True)
     if index is None and n != m:
         raise L.OvgError("%s: without an index the pairs are i <-> i and need n == m (got %d, %d)" % (what, n, m))
-    _align_tensor(what, source_valid, "source_valid", torch.uint8, (n,), True)
-    _align_tensor(what, target_valid, "target_valid", torch.uint8, (m,), True)
-    _align_tensor(what, sqdist, "sqdist", torch.float32, (n,), True)
+    _tensor(what, source_valid, "source_valid", _U8, (n,), optional=True)
+    _tensor(what, target_valid, "target_valid", _U8, (m,), optional=True)
+    _tensor(what, sqdist, "sqdist", _F32, (n,), optional=True)
     if (sqdist is None) != (max_sqdist is None):
         raise L.OvgError("%s: the gate needs both sqdist and max_sqdist" % what)
     if max_sqdist is not None and not float(max_sqdist) == float(max_sqdist):
         raise L.OvgError("%s: max_sqdist must be a number, not NaN" % what)
-    _align_tensor(what, centre, "centre", torch.float64, (6,), True)
-    _align_tensor(what, count, "count", torch.int64, (1,), True)
-    _align_tensor(what, sums, "sums", torch.float64, (L.ALIGN_SUMS,), True)
-    if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous()):
-        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    _tensor(what, centre, "centre", _F64, (6,), optional=True)
+    _tensor(what, count, "count", _I64, (1,), optional=True)
+    _tensor(what, sums, "sums", _F64, (L.ALIGN_SUMS,), optional=True)
+    _tensor(what, ws, "ws", _U8, optional=True)
     _chk_dev(source, target, index, source_valid, target_valid, sqdist, centre, ws, count, sums)
-    need = align_workspace_bytes(n)
-    if ws is None or nbytes(ws) < need:
-        ws = torch.empty(need, device=source.device, dtype=torch.uint8)
-    count = torch.empty(1, device=source.device, dtype=torch.int64) if count is None else count
-    sums = torch.empty(L.ALIGN_SUMS, device=source.device, dtype=torch.float64) if sums is None else sums
+    ws = _workspace(ws, align_workspace_bytes(n), source.device)
+    count = _out(what, count, "count", _I64, (1,), source.device)
+    sums = _out(what, sums, "sums", _F64, (L.ALIGN_SUMS,), source.device)
     p = L.AlignMomentsParams()
     p.source, p.target, p.index, p.source_valid, p.target_valid = L.ptr(source), L.ptr(target), L.ptr(index), L.ptr(source_valid), L.ptr(target_valid)
     p.sqdist, p.centre, p.n, p.m = L.ptr(sqdist), L.ptr(centre), n, m
@@ -1163,14 +1136,14 @@ def align_solve(count, sums, transform, centre=None, with_scale=True, compose=Fa
     int32 [1] (L.ALIGN_FEW_PAIRS | L.ALIGN_NO_SPREAD | L.ALIGN_NOT_FINITE: the step is then the identity) are written when given.
     -> transform. Nothing is read back."""
     what = "align_solve"
-    _align_tensor(what, count, "count", torch.int64, (1,))
-    _align_tensor(what, sums, "sums", torch.float64, (L.ALIGN_SUMS,))
-    _align_tensor(what, transform, "transform", torch.float64, (4, 4))
-    _align_tensor(what, centre, "centre", torch.float64, (6,), True)
-    _align_tensor(what, scale, "scale", torch.float64, (1,), True)
-    _align_tensor(what, rms, "rms", torch.float64, (1,), True)
-    _align_tensor(what, out_count, "out_count", torch.int64, (1,), True)
-    _align_tensor(what, status, "status", torch.int32, (1,), True)
+    _tensor(what, count, "count", _I64, (1,))
+    _tensor(what, sums, "sums", _F64, (L.ALIGN_SUMS,))
+    _tensor(what, transform, "transform", _F64, (4, 4))
+    _tensor(what, centre, "centre", _F64, (6,), optional=True)
+    _tensor(what, scale, "scale", _F64, (1,), optional=True)
+    _tensor(what, rms, "rms", _F64, (1,), optional=True)
+    _tensor(what, out_count, "out_count", _I64, (1,), optional=True)
+    _tensor(what, status, "status", _I32, (1,), optional=True)
     _chk_dev(count, sums, transform, centre, scale, rms, out_count, status)
     p = L.AlignSolveParams()
     p.count, p.sums, p.centre, p.transform = L.ptr(count), L.ptr(sums), L.ptr(centre), L.ptr(transform)
@@ -1184,35 +1157,23 @@ def align_apply(points, transform, out=None):
     """ovg_align_apply on contiguous device tensors: points f32 [n, 3], transform f64 [4, 4] -> out f32 [n, 3] (allocated when None; may
     be `points` itself): out[i] = f32(T p[i]) with every coordinate ((T0 x + T1 y) + T2 z) + T3 in float64. Nothing is read back."""
     what = "align_apply"
-    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or \
-            points.shape[1] != 3 or points.shape[0] < 1:
-        raise L.OvgError("%s: points must be a contiguous f32 tensor [n, 3], n >= 1" % what)
-    n = int(points.shape[0])
-    _align_tensor(what, transform, "transform", torch.float64, (4, 4))
-    _align_tensor(what, out, "out", torch.float32, (n, 3), True)
+    n = _points(what, points, "points", 1)
+    _tensor(what, transform, "transform", _F64, (4, 4))
+    _tensor(what, out, "out", _F32, (n, 3), optional=True)
     _chk_dev(points, transform, out)
-    out = torch.empty(n, 3, device=points.device, dtype=torch.float32) if out is None else out
+    out = _out(what, out, "out", _F32, (n, 3), points.device)
     p = L.AlignApplyParams()
     p.points, p.transform, p.n, p.out = L.ptr(points), L.ptr(transform), n, L.ptr(out)
     L.call("ovg_align_apply", p, _stream())
     return out
 
 
-def _deptheval_ws_bytes(name, groups, n):
-    if not all(-(1 << 63) <= int(v) < (1 << 63) for v in (groups, n)):
-        raise L.OvgError("%s: unsupported (groups=%d, n=%d)" % (name, groups, n))
-    b = getattr(L.load(), name)(int(groups), int(n))
-    if b < 0:
-        raise L.OvgError("%s: unsupported (groups=%d, n=%d)" % (name, groups, n))
-    return int(b)
-
-
 def deptheval_median_workspace_bytes(groups, n):
-    return _deptheval_ws_bytes("ovg_deptheval_median_workspace_bytes", groups, n)
+    return _ws_query("ovg_deptheval_median_workspace_bytes", groups=groups, n=n)
 
 
 def deptheval_sums_workspace_bytes(groups, n):
-    return _deptheval_ws_bytes("ovg_deptheval_sums_workspace_bytes", groups, n)
+    return _ws_query("ovg_deptheval_sums_workspace_bytes", groups=groups, n=n)
 
 
 def _deptheval_maps(what, pred, gt, valid, min_depth, max_depth):
@@ -1229,21 +1190,9 @@ def _deptheval_maps(what, pred, gt, valid, min_depth, max_depth):
             raise L.OvgError("%s: %s must be shaped %r with the row stride of pred (%d)" % (what, name, (G, n), stride))
     if G > L.DEPTHEVAL_MAX_GROUPS or G * n >= (1 << 31) or stride < n:
         raise L.OvgError("%s: the maps must be at most %d groups, fewer than 2^31 pixels, row stride >= n" % (what, L.DEPTHEVAL_MAX_GROUPS))
-    for v, name in ((min_depth, "min_depth"), (max_depth, "max_depth")):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
-            raise L.OvgError("%s: %s must be a number, not NaN" % (what, name))
-    if min_depth < 0:
-        raise L.OvgError("%s: min_depth must be >= 0" % what)
+    _number(what, "min_depth", min_depth, lo=0, f32=False)
+    _number(what, "max_depth", max_depth, f32=False)
     return G, n, stride
-
-
-def _deptheval_check_ws(what, ws):
-    if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous()):
-        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
-
-
-def _deptheval_ws(ws, need, device):
-    return torch.empty(need, device=device, dtype=torch.uint8) if ws is None or nbytes(ws) < need else ws
 
 
 def deptheval_median(pred, gt, valid=None, min_depth=0.0, max_depth=float("inf"), ws=None, count=None, median=None):
@@ -1253,13 +1202,13 @@ def deptheval_median(pred, gt, valid=None, min_depth=0.0, max_depth=float("inf")
     optional uint8 device tensor of at least deptheval_median_workspace_bytes(G, n) bytes (the call zeroes it). Nothing is read back."""
     what = "deptheval_median"
     G, n, stride = _deptheval_maps(what, pred, gt, valid, min_depth, max_depth)
-    _align_tensor(what, count, "count", torch.int64, (G,), True)
-    _align_tensor(what, median, "median", torch.float32, (G, 2, 2), True)
-    _deptheval_check_ws(what, ws)
+    _tensor(what, count, "count", _I64, (G,), optional=True)
+    _tensor(what, median, "median", _F32, (G, 2, 2), optional=True)
+    _tensor(what, ws, "ws", _U8, optional=True)
     _chk_dev(pred, gt, valid, ws, count, median)
-    ws = _deptheval_ws(ws, deptheval_median_workspace_bytes(G, n), pred.device)
-    count = torch.empty(G, device=pred.device, dtype=torch.int64) if count is None else count
-    median = torch.empty(G, 2, 2, device=pred.device, dtype=torch.float32) if median is None else median
+    ws = _workspace(ws, deptheval_median_workspace_bytes(G, n), pred.device)
+    count = _out(what, count, "count", _I64, (G,), pred.device)
+    median = _out(what, median, "median", _F32, (G, 2, 2), pred.device)
     p = L.DepthEvalMedianParams()
     p.pred, p.gt, p.valid, p.groups, p.n, p.stride = L.ptr(pred), L.ptr(gt), L.ptr(valid), G, n, stride
     p.min_depth, p.max_depth = float(min_depth), float(max_depth)
@@ -1277,20 +1226,19 @@ def deptheval_sums(pred, gt, valid=None, min_depth=0.0, max_depth=float("inf"), 
     calls give identical bytes. ws: optional, at least deptheval_sums_workspace_bytes(G, n) bytes. Nothing is read back."""
     what = "deptheval_sums"
     G, n, stride = _deptheval_maps(what, pred, gt, valid, min_depth, max_depth)
-    _align_tensor(what, coeff, "coeff", torch.float64, (G, 2), True)
-    _align_tensor(what, counts, "counts", torch.int64, (G, L.DEPTHEVAL_COUNTS), True)
-    _align_tensor(what, sums, "sums", torch.float64, (G, L.DEPTHEVAL_SUMS), True)
+    _tensor(what, coeff, "coeff", _F64, (G, 2), optional=True)
+    _tensor(what, counts, "counts", _I64, (G, L.DEPTHEVAL_COUNTS), optional=True)
+    _tensor(what, sums, "sums", _F64, (G, L.DEPTHEVAL_SUMS), optional=True)
     if coeff is not None:
-        for v, name in ((clip_min, "clip_min"), (clip_max, "clip_max")):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
-                raise L.OvgError("%s: %s must be a number, not NaN" % (what, name))
+        _number(what, "clip_min", clip_min, f32=False)
+        _number(what, "clip_max", clip_max, f32=False)
         if not 0 < clip_min < float("inf") or clip_max < clip_min:
             raise L.OvgError("%s: clip_min must be positive and finite, clip_max >= clip_min" % what)
-    _deptheval_check_ws(what, ws)
+    _tensor(what, ws, "ws", _U8, optional=True)
     _chk_dev(pred, gt, valid, coeff, ws, counts, sums)
-    ws = _deptheval_ws(ws, deptheval_sums_workspace_bytes(G, n), pred.device)
-    counts = torch.empty(G, L.DEPTHEVAL_COUNTS, device=pred.device, dtype=torch.int64) if counts is None else counts
-    sums = torch.empty(G, L.DEPTHEVAL_SUMS, device=pred.device, dtype=torch.float64) if sums is None else sums
+    ws = _workspace(ws, deptheval_sums_workspace_bytes(G, n), pred.device)
+    counts = _out(what, counts, "counts", _I64, (G, L.DEPTHEVAL_COUNTS), pred.device)
+    sums = _out(what, sums, "sums", _F64, (G, L.DEPTHEVAL_SUMS), pred.device)
     p = L.DepthEvalSumsParams()
     p.pred, p.gt, p.valid, p.groups, p.n, p.stride = L.ptr(pred), L.ptr(gt), L.ptr(valid), G, n, stride
     p.min_depth, p.max_depth = float(min_depth), float(max_depth)
@@ -1309,42 +1257,22 @@ def deptheval_solve(mode, count, sums=None, median=None, coeff=None, status=None
     what = "deptheval_solve"
     if isinstance(mode, bool) or mode not in (L.DEPTHEVAL_NONE, L.DEPTHEVAL_MEDIAN, L.DEPTHEVAL_SCALE, L.DEPTHEVAL_SCALE_SHIFT):
         raise L.OvgError("%s: mode must be one of L.DEPTHEVAL_NONE / MEDIAN / SCALE / SCALE_SHIFT, got %r" % (what, mode))
-    if not isinstance(count, torch.Tensor) or count.dtype != torch.int64 or not count.is_contiguous() or count.dim() not in (1, 2) or \
-            count.shape[0] < 1 or count.shape[0] > L.DEPTHEVAL_MAX_GROUPS or (count.dim() == 2 and count.shape[1] != L.DEPTHEVAL_COUNTS):
-        raise L.OvgError("%s: count must be a contiguous int64 tensor [G] or [G, %d], 1 <= G <= %d" % (what, L.DEPTHEVAL_COUNTS, L.DEPTHEVAL_MAX_GROUPS))
+    _tensor(what, count, "count", _I64)
+    if count.dim() not in (1, 2) or not 1 <= count.shape[0] <= L.DEPTHEVAL_MAX_GROUPS or (count.dim() == 2 and count.shape[1] != L.DEPTHEVAL_COUNTS):
+        raise L.OvgError("%s: count must be [G] or [G, %d], 1 <= G <= %d" % (what, L.DEPTHEVAL_COUNTS, L.DEPTHEVAL_MAX_GROUPS))
     G = int(count.shape[0])
-    _align_tensor(what, sums, "sums", torch.float64, (G, L.DEPTHEVAL_SUMS), mode not in (L.DEPTHEVAL_SCALE, L.DEPTHEVAL_SCALE_SHIFT))
-    _align_tensor(what, median, "median", torch.float32, (G, 2, 2), mode != L.DEPTHEVAL_MEDIAN)
-    _align_tensor(what, coeff, "coeff", torch.float64, (G, 2), True)
-    _align_tensor(what, status, "status", torch.int32, (G,), True)
+    _tensor(what, sums, "sums", _F64, (G, L.DEPTHEVAL_SUMS), optional=mode not in (L.DEPTHEVAL_SCALE, L.DEPTHEVAL_SCALE_SHIFT))
+    _tensor(what, median, "median", _F32, (G, 2, 2), optional=mode != L.DEPTHEVAL_MEDIAN)
+    _tensor(what, coeff, "coeff", _F64, (G, 2), optional=True)
+    _tensor(what, status, "status", _I32, (G,), optional=True)
     _chk_dev(count, sums, median, coeff, status)
-    coeff = torch.empty(G, 2, device=count.device, dtype=torch.float64) if coeff is None else coeff
-    status = torch.empty(G, device=count.device, dtype=torch.int32) if status is None else status
+    coeff = _out(what, coeff, "coeff", _F64, (G, 2), count.device)
+    status = _out(what, status, "status", _I32, (G,), count.device)
     p = L.DepthEvalSolveParams()
     p.count, p.count_stride, p.sums, p.median = L.ptr(count), 1 if count.dim() == 1 else L.DEPTHEVAL_COUNTS, L.ptr(sums), L.ptr(median)
     p.groups, p.mode, p.coeff, p.status = G, int(mode), L.ptr(coeff), L.ptr(status)
     L.call("ovg_deptheval_solve", p, _stream())
     return coeff, status
-
-
-def _plane_points(what, points):
-    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or \
-            points.shape[1] != 3 or not 1 <= points.shape[0] < 1 << 31:
-        raise L.OvgError("%s: points must be a contiguous f32 tensor [n, 3], 1 <= n < 2^31" % what)
-    return int(points.shape[0])
-
-
-def _plane_threshold(what, threshold):
-    import math
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not (threshold >= 0 and math.isfinite(threshold)) or \
-            threshold > 3.4028234663852886e38:
-        raise L.OvgError("%s: threshold must be a finite float32 number >= 0, got %r" % (what, threshold))
-    return float(threshold)
-
-
-def _plane_out(what, t, name, dtype, shape, device):
-    _align_tensor(what, t, name, dtype, shape, True)
-    return torch.empty(shape, device=device, dtype=dtype) if t is None else t
 
 
 def plane_hypotheses(points, hypotheses, seed=0, valid=None, candidates=None, axis=None, min_abs_cos=0.0, planes=None, index=None):
@@ -1353,23 +1281,20 @@ def plane_hypotheses(points, hypotheses, seed=0, valid=None, candidates=None, ax
     [0, 2^64). -> (planes f32 [H, 4], index int32 [H, 3]) (allocated when None): hypothesis h through the three points its seeded
     draws name, four NaNs where the rule of include/omnivggt_hip.h voids it; index holds the draws either way. Nothing is read back."""
     what = "plane_hypotheses"
-    n = _plane_points(what, points)
-    if isinstance(hypotheses, bool) or not isinstance(hypotheses, int) or not 1 <= hypotheses < 1 << 31:
-        raise L.OvgError("%s: hypotheses must be an integer in [1, 2^31), got %r" % (what, hypotheses))
-    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
-        raise L.OvgError("%s: seed must be an integer in [0, 2^64), got %r" % (what, seed))
-    _align_tensor(what, valid, "valid", torch.uint8, (n,), True)
-    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int32 or candidates.dim() != 1 or
-                                   not candidates.is_contiguous() or not 1 <= candidates.shape[0] < 1 << 31):
-        raise L.OvgError("%s: candidates must be a contiguous int32 tensor [m], 1 <= m < 2^31" % what)
-    _align_tensor(what, axis, "axis", torch.float32, (3,), True)
-    if isinstance(min_abs_cos, bool) or not isinstance(min_abs_cos, (int, float)) or not 0.0 <= min_abs_cos <= 1.0:
-        raise L.OvgError("%s: min_abs_cos must be a number in [0, 1], got %r" % (what, min_abs_cos))
+    n = _points(what, points, "points", 1, 1 << 31)
+    _int_in(what, "hypotheses", hypotheses, 1, 1 << 31)
+    _int_in(what, "seed", seed, 0, 1 << 64)
+    _tensor(what, valid, "valid", _U8, (n,), optional=True)
+    _tensor(what, candidates, "candidates", _I32, optional=True)
+    if candidates is not None and (candidates.dim() != 1 or not 1 <= candidates.shape[0] < 1 << 31):
+        raise L.OvgError("%s: candidates must be [m], 1 <= m < 2^31" % what)
+    _tensor(what, axis, "axis", _F32, (3,), optional=True)
+    _number(what, "min_abs_cos", min_abs_cos, lo=0.0, hi=1.0)
     if axis is None and min_abs_cos != 0:
         raise L.OvgError("%s: min_abs_cos needs an axis" % what)
     _chk_dev(points, valid, candidates, axis, planes, index)
-    planes = _plane_out(what, planes, "planes", torch.float32, (hypotheses, 4), points.device)
-    index = _plane_out(what, index, "index", torch.int32, (hypotheses, 3), points.device)
+    planes = _out(what, planes, "planes", _F32, (hypotheses, 4), points.device)
+    index = _out(what, index, "index", _I32, (hypotheses, 3), points.device)
     p = L.PlaneHypothesesParams()
     p.points, p.valid, p.candidates, p.axis = L.ptr(points), L.ptr(valid), L.ptr(candidates), L.ptr(axis)
     p.n, p.m, p.H, p.seed = n, n if candidates is None else int(candidates.shape[0]), hypotheses, seed
@@ -1384,17 +1309,13 @@ def plane_score(points, planes, threshold, valid=None, splits=0, count=None):
     per plane, usable points only; a void (NaN) plane counts 0. splits: 0 lets the entry choose, otherwise the number of point splits
     of its grid -- the bytes are the same for every value. Nothing is read back."""
     what = "plane_score"
-    n = _plane_points(what, points)
-    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.float32 or not planes.is_contiguous() or planes.dim() != 2 or \
-            planes.shape[1] != 4 or not 1 <= planes.shape[0] < 1 << 31:
-        raise L.OvgError("%s: planes must be a contiguous f32 tensor [H, 4], 1 <= H < 2^31" % what)
-    H = int(planes.shape[0])
-    threshold = _plane_threshold(what, threshold)
-    _align_tensor(what, valid, "valid", torch.uint8, (n,), True)
-    if isinstance(splits, bool) or not isinstance(splits, int) or not 0 <= splits < 1 << 31:
-        raise L.OvgError("%s: splits must be an integer in [0, 2^31), got %r" % (what, splits))
+    n = _points(what, points, "points", 1, 1 << 31)
+    H = _table(what, planes, "planes", _F32, 4, 1, 1 << 31)
+    threshold = _number(what, "threshold", threshold, lo=0)
+    _tensor(what, valid, "valid", _U8, (n,), optional=True)
+    _int_in(what, "splits", splits, 0, 1 << 31)
     _chk_dev(points, planes, valid, count)
-    count = _plane_out(what, count, "count", torch.int32, (H,), points.device)
+    count = _out(what, count, "count", _I32, (H,), points.device)
     p = L.PlaneScoreParams()
     p.points, p.valid, p.planes, p.n, p.H = L.ptr(points), L.ptr(valid), L.ptr(planes), n, H
     p.threshold, p.splits, p.count = threshold, splits, L.ptr(count)
@@ -1407,19 +1328,18 @@ def plane_select(count, planes, min_inliers=3, best=None, plane=None, best_count
     status int32 [1]) (allocated when None): the hypothesis with the most inliers, ties to the lowest index, or -1 / four zeros /
     L.PLANE_NONE when that count is below min_inliers (>= 3). Nothing is read back."""
     what = "plane_select"
-    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.dim() != 1 or not count.is_contiguous() or \
-            not 1 <= count.shape[0] < 1 << 31:
-        raise L.OvgError("%s: count must be a contiguous int32 tensor [H], 1 <= H < 2^31" % what)
+    _tensor(what, count, "count", _I32)
+    if count.dim() != 1 or not 1 <= count.shape[0] < 1 << 31:
+        raise L.OvgError("%s: count must be [H], 1 <= H < 2^31" % what)
     H = int(count.shape[0])
-    _align_tensor(what, planes, "planes", torch.float32, (H, 4))
-    if isinstance(min_inliers, bool) or not isinstance(min_inliers, int) or not 3 <= min_inliers < 1 << 31:
-        raise L.OvgError("%s: min_inliers must be an integer in [3, 2^31), got %r" % (what, min_inliers))
+    _tensor(what, planes, "planes", _F32, (H, 4))
+    _int_in(what, "min_inliers", min_inliers, 3, 1 << 31)
     _chk_dev(count, planes, best, plane, best_count, status)
     dev = count.device
-    best = _plane_out(what, best, "best", torch.int32, (1,), dev)
-    plane = _plane_out(what, plane, "plane", torch.float32, (4,), dev)
-    best_count = _plane_out(what, best_count, "best_count", torch.int32, (1,), dev)
-    status = _plane_out(what, status, "status", torch.int32, (1,), dev)
+    best = _out(what, best, "best", _I32, (1,), dev)
+    plane = _out(what, plane, "plane", _F32, (4,), dev)
+    best_count = _out(what, best_count, "best_count", _I32, (1,), dev)
+    status = _out(what, status, "status", _I32, (1,), dev)
     p = L.PlaneSelectParams()
     p.count, p.planes, p.H, p.min_inliers, p.pad = L.ptr(count), L.ptr(planes), H, min_inliers, 0
     p.best, p.plane, p.best_count, p.status = L.ptr(best), L.ptr(plane), L.ptr(best_count), L.ptr(status)
@@ -1433,18 +1353,16 @@ def plane_mask(points, plane, threshold, valid=None, gate=None, inlier=None, dis
     the inlier mask of the plane at the threshold, the signed residual f32 [n] (NaN for unusable points) when distance is a tensor or
     True (allocated), else None, and the number of inliers. Nothing is read back."""
     what = "plane_mask"
-    n = _plane_points(what, points)
-    _align_tensor(what, plane, "plane", torch.float32, (4,))
-    threshold = _plane_threshold(what, threshold)
-    _align_tensor(what, valid, "valid", torch.uint8, (n,), True)
-    _align_tensor(what, gate, "gate", torch.int32, (1,), True)
-    dist = None if isinstance(distance, bool) else distance
-    _chk_dev(points, plane, valid, gate, inlier, dist, out_count)
-    inlier = _plane_out(what, inlier, "inlier", torch.uint8, (n,), points.device)
-    if distance is True:
-        dist = torch.empty(n, device=points.device, dtype=torch.float32)
-    _align_tensor(what, dist, "distance", torch.float32, (n,), True)
-    out_count = _plane_out(what, out_count, "out_count", torch.int64, (1,), points.device)
+    n = _points(what, points, "points", 1, 1 << 31)
+    _tensor(what, plane, "plane", _F32, (4,))
+    threshold = _number(what, "threshold", threshold, lo=0)
+    _tensor(what, valid, "valid", _U8, (n,), optional=True)
+    _tensor(what, gate, "gate", _I32, (1,), optional=True)
+    _chk_dev(points, plane, valid, gate, inlier, None if isinstance(distance, bool) else distance, out_count)
+    inlier = _out(what, inlier, "inlier", _U8, (n,), points.device)
+    dist = None if distance is None or distance is False else \
+        _out(what, None if distance is True else distance, "distance", _F32, (n,), points.device)
+    out_count = _out(what, out_count, "out_count", _I64, (1,), points.device)
     p = L.PlaneMaskParams()
     p.points, p.valid, p.plane, p.gate, p.n = L.ptr(points), L.ptr(valid), L.ptr(plane), L.ptr(gate), n
     p.threshold, p.pad, p.inlier, p.distance, p.out_count = threshold, 0, L.ptr(inlier), L.ptr(dist), L.ptr(out_count)
@@ -1459,14 +1377,14 @@ def plane_fit(count, sums, plane, centre=None, axis=None, rms=None, eigen=None, 
     inliers, collinear inliers, non-finite sums) leaves the plane as it was. rms f64 [1], eigen f64 [3] (ascending) and status int32 [1]
     (L.PLANE_FEW | L.PLANE_NO_SPREAD | L.PLANE_NOT_FINITE) are written when given. -> plane. Nothing is read back."""
     what = "plane_fit"
-    _align_tensor(what, count, "count", torch.int64, (1,))
-    _align_tensor(what, sums, "sums", torch.float64, (L.ALIGN_SUMS,))
-    _align_tensor(what, plane, "plane", torch.float32, (4,))
-    _align_tensor(what, centre, "centre", torch.float64, (6,), True)
-    _align_tensor(what, axis, "axis", torch.float32, (3,), True)
-    _align_tensor(what, rms, "rms", torch.float64, (1,), True)
-    _align_tensor(what, eigen, "eigen", torch.float64, (3,), True)
-    _align_tensor(what, status, "status", torch.int32, (1,), True)
+    _tensor(what, count, "count", _I64, (1,))
+    _tensor(what, sums, "sums", _F64, (L.ALIGN_SUMS,))
+    _tensor(what, plane, "plane", _F32, (4,))
+    _tensor(what, centre, "centre", _F64, (6,), optional=True)
+    _tensor(what, axis, "axis", _F32, (3,), optional=True)
+    _tensor(what, rms, "rms", _F64, (1,), optional=True)
+    _tensor(what, eigen, "eigen", _F64, (3,), optional=True)
+    _tensor(what, status, "status", _I32, (1,), optional=True)
     _chk_dev(count, sums, plane, centre, axis, rms, eigen, status)
     p = L.PlaneFitParams()
     p.count, p.sums, p.centre, p.axis, p.plane = L.ptr(count), L.ptr(sums), L.ptr(centre), L.ptr(axis), L.ptr(plane)
@@ -1475,26 +1393,26 @@ def plane_fit(count, sums, plane, centre=None, axis=None, rms=None, eigen=None, 
     return plane
 
 
-def _tsdf_scalar(what, name, value):
-    import math
-    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (value > 0 and math.isfinite(value)) or value > 3.4028234663852886e38:
-        raise L.OvgError("%s: %s must be a positive finite float32 number, got %r" % (what, name, value))
-    return float(value)
+def _map_shape(what, t, name, trailing=()):
+    """t must be a tensor [S, H, W] + trailing with 1 <= S H W < 2^31 -> (S, H, W)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 + len(trailing) or tuple(t.shape[3:]) != tuple(trailing) or 0 in t.shape or \
+            t.numel() // max(1, math.prod(trailing)) >= 1 << 31:
+        raise L.OvgError("%s: %s must be a tensor [S, H, W%s], 1 <= S H W < 2^31" % (what, name, "".join(", %d" % v for v in trailing)))
+    return tuple(int(v) for v in t.shape[:3])
 
 
 def _tsdf_volume(what, tsdf, weight, color, origin):
-    if not isinstance(tsdf, torch.Tensor) or tsdf.dtype != torch.float32 or tsdf.dim() != 3 or not tsdf.is_contiguous() or \
-            0 in tsdf.shape or tsdf.numel() >= 1 << 31:
-        raise L.OvgError("%s: tsdf must be a contiguous f32 tensor [nz, ny, nx], 1 <= nx ny nz < 2^31" % what)
-    _align_tensor(what, weight, "weight", torch.float32, tuple(tsdf.shape))
-    _align_tensor(what, color, "color", torch.float32, tuple(tsdf.shape) + (4,), True)
+    """The volume and its origin as the two TSDF entries take them -> (nx, ny, nz, origin as three floats)."""
+    nz, ny, nx = _map_shape(what, tsdf, "tsdf")
+    _tensor(what, tsdf, "tsdf", _F32, (nz, ny, nx))
+    _tensor(what, weight, "weight", _F32, (nz, ny, nx))
+    _tensor(what, color, "color", _F32, (nz, ny, nx, 4), optional=True)
     try:
         origin = [float(v) for v in origin]
     except (TypeError, ValueError):
         origin = []
-    if len(origin) != 3 or not all(abs(v) <= 3.4028234663852886e38 for v in origin):
+    if len(origin) != 3 or not all(abs(v) <= _F32_MAX for v in origin):
         raise L.OvgError("%s: origin must be three finite float32 numbers" % what)
-    nz, ny, nx = (int(v) for v in tsdf.shape)
     return nx, ny, nz, origin
 
 
@@ -1508,24 +1426,19 @@ def tsdf_integrate(tsdf, weight, depth, cams, origin, voxel, trunc, max_weight=6
     bytes of one call. tile: L.TSDF_TILE_*, speed only. -> (tsdf, weight, color). Nothing is read back."""
     what = "tsdf_integrate"
     nx, ny, nz, origin = _tsdf_volume(what, tsdf, weight, color, origin)
-    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 3 or not depth.is_contiguous() or \
-            0 in depth.shape or depth.numel() >= 1 << 31:
-        raise L.OvgError("%s: depth must be a contiguous f32 tensor [S, H, W], 1 <= S H W < 2^31" % what)
-    S, H, W = (int(v) for v in depth.shape)
-    _align_tensor(what, cams, "cams", torch.float32, (S, 16))
-    _align_tensor(what, valid, "valid", torch.uint8, (S, H, W), True)
-    _align_tensor(what, obs_weight, "obs_weight", torch.float32, (S, H, W), True)
-    _align_tensor(what, colors, "colors", torch.uint8, (S, H, W, 3), True)
+    S, H, W = _map_shape(what, depth, "depth")
+    _tensor(what, depth, "depth", _F32, (S, H, W))
+    _tensor(what, cams, "cams", _F32, (S, 16))
+    _tensor(what, valid, "valid", _U8, (S, H, W), optional=True)
+    _tensor(what, obs_weight, "obs_weight", _F32, (S, H, W), optional=True)
+    _tensor(what, colors, "colors", _U8, (S, H, W, 3), optional=True)
     if colors is not None and color is None:
         raise L.OvgError("%s: colors need a colour volume" % what)
-    voxel, trunc = _tsdf_scalar(what, "voxel", voxel), _tsdf_scalar(what, "trunc", trunc)
-    max_weight, near = _tsdf_scalar(what, "max_weight", max_weight), _tsdf_scalar(what, "near", near)
-    n = S - view_first if view_count is None else view_count
-    if isinstance(view_first, bool) or isinstance(n, bool) or not isinstance(view_first, int) or not isinstance(n, int) or \
-            not (0 <= view_first < S and 0 < n <= S - view_first):
-        raise L.OvgError("%s: views %r .. outside [0, %d)" % (what, view_first, S))
-    if isinstance(tile, bool) or not isinstance(tile, int) or not L.TSDF_TILE_DEFAULT <= tile <= L.TSDF_TILE_32x8x1:
-        raise L.OvgError("%s: unknown tile %r" % (what, tile))
+    voxel, trunc = _number(what, "voxel", voxel, lo=0, strict=True), _number(what, "trunc", trunc, lo=0, strict=True)
+    max_weight, near = _number(what, "max_weight", max_weight, lo=0, strict=True), _number(what, "near", near, lo=0, strict=True)
+    _int_in(what, "view_first", view_first, 0, S)
+    n = _int_in(what, "view_count", S - view_first if view_count is None else view_count, 1, S - view_first + 1)
+    _int_in(what, "tile", tile, L.TSDF_TILE_DEFAULT, L.TSDF_TILE_32x8x1 + 1)
     _chk_dev(tsdf, weight, color, depth, cams, valid, obs_weight, colors)
     p = L.TsdfIntegrateParams()
     p.tsdf, p.weight, p.color, p.nx, p.ny, p.nz = L.ptr(tsdf), L.ptr(weight), L.ptr(color), nx, ny, nz
@@ -1539,13 +1452,7 @@ def tsdf_integrate(tsdf, weight, depth, cams, origin, voxel, trunc, max_weight=6
 
 
 def tsdf_extract_workspace_bytes(nx, ny, nz):
-    for v in (nx, ny, nz):
-        if not -(1 << 31) <= int(v) < (1 << 31):
-            raise L.OvgError("ovg_tsdf_extract_workspace_bytes: unsupported (nx=%d, ny=%d, nz=%d)" % (nx, ny, nz))
-    b = L.load().ovg_tsdf_extract_workspace_bytes(int(nx), int(ny), int(nz))
-    if b < 0:
-        raise L.OvgError("ovg_tsdf_extract_workspace_bytes: unsupported (nx=%d, ny=%d, nz=%d)" % (nx, ny, nz))
-    return int(b)
+    return _ws_query("ovg_tsdf_extract_workspace_bytes", nx=nx, ny=ny, nz=nz)
 
 
 def tsdf_extract(stage, tsdf, weight, origin, voxel, ws, min_weight=1.0, color=None, out_count=None, vertex_capacity=0, quad_capacity=0,
@@ -1556,22 +1463,16 @@ def tsdf_extract(stage, tsdf, weight, origin, voxel, ws, min_weight=1.0, color=N
     quad_capacity quads to faces int32 [2 ., 3] (two triangles each) from what the COUNT stage left in ws."""
     what = "tsdf_extract"
     nx, ny, nz, origin = _tsdf_volume(what, tsdf, weight, color, origin)
-    voxel, min_weight = _tsdf_scalar(what, "voxel", voxel), _tsdf_scalar(what, "min_weight", min_weight)
+    voxel, min_weight = _number(what, "voxel", voxel, lo=0, strict=True), _number(what, "min_weight", min_weight, lo=0, strict=True)
     if stage not in (L.TSDF_COUNT, L.TSDF_SCATTER, L.TSDF_COUNT | L.TSDF_SCATTER):
         raise L.OvgError("%s: unknown stage %r" % (what, stage))
-    for name, v in (("vertex_capacity", vertex_capacity), ("quad_capacity", quad_capacity)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 62:
-            raise L.OvgError("%s: %s must be a non-negative integer, got %r" % (what, name, v))
-    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    _int_in(what, "vertex_capacity", vertex_capacity, 0, 1 << 62)
+    _int_in(what, "quad_capacity", quad_capacity, 0, 1 << 62)
+    _tensor(what, ws, "ws", _U8)
     if stage & L.TSDF_SCATTER:
-        outs = ((vertices, torch.float32, 3 * vertex_capacity), (normals, torch.float32, 3 * vertex_capacity),
-                (colors, torch.uint8, 3 * vertex_capacity), (faces, torch.int32, 6 * quad_capacity))
-        for t, dt, need in outs:
-            if need and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < need):
-                raise L.OvgError("%s: output buffers must be contiguous and hold the capacities" % what)
-    if not isinstance(out_count, torch.Tensor) or out_count.dtype != torch.int64 or out_count.numel() < 2 or not out_count.is_contiguous():
-        raise L.OvgError("%s: out_count must be a contiguous int64 device tensor of two elements" % what)
+        _capacity_buffers(what, ((vertices, "vertices", _F32, 3 * vertex_capacity, True), (normals, "normals", _F32, 3 * vertex_capacity, True),
+                                 (colors, "colors", _U8, 3 * vertex_capacity, True), (faces, "faces", _I32, 6 * quad_capacity, True)))
+    _tensor(what, out_count, "out_count", _I64, min_numel=2)
     _chk_dev(tsdf, weight, color, ws, out_count, vertices, normals, colors, faces)
     p = L.TsdfExtractParams()
     p.tsdf, p.weight, p.color, p.nx, p.ny, p.nz = L.ptr(tsdf), L.ptr(weight), L.ptr(color), nx, ny, nz
@@ -1587,34 +1488,6 @@ def tsdf_extract(stage, tsdf, weight, origin, voxel, ws, min_weight=1.0, color=N
 # ---------------------------------------------------------------------------------------------------------------------------------
 # image-space map geometry (ovg_map_depth, ovg_map_normals, ovg_map_edges, ovg_map_triangulate)
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _map_tensor(what, t, name, dtype, shape, optional=False):
-    if t is None and optional:
-        return
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise L.OvgError("%s: %s must be a contiguous %s tensor %r" % (what, name, str(dtype).replace("torch.", ""), list(shape)))
-
-
-def _map_shape(what, t, name, trailing=()):
-    if not isinstance(t, torch.Tensor) or t.dim() != 3 + len(trailing) or tuple(t.shape[3:]) != tuple(trailing) or 0 in t.shape or \
-            t.numel() // max(1, int(torch.Size(trailing).numel())) >= 1 << 31:
-        raise L.OvgError("%s: %s must be a tensor [S, H, W%s], 1 <= S H W < 2^31" % (what, name, "".join(", %d" % v for v in trailing)))
-    return tuple(int(v) for v in t.shape[:3])
-
-
-def _map_tol(what, name, value, allow_inf=True):
-    import math
-    if isinstance(value, bool) or not isinstance(value, (int, float)) or not value >= 0 or (not allow_inf and math.isinf(value)):
-        raise L.OvgError("%s: %s must be a non-negative number%s, got %r" % (what, name, " (+inf switches the test off)" if allow_inf else "", value))
-    return float(value)
-
-
-def _map_out(what, t, name, dtype, shape, device):
-    if t is None:
-        return torch.empty(shape, device=device, dtype=dtype)
-    _map_tensor(what, t, name, dtype, shape)
-    return t
-
-
 def map_depth(points=None, cams=None, depth=None, valid=None, near=1e-3, out=None):
     """ovg_map_depth on contiguous device tensors: exactly one of points f32 [S, H, W, 3] with cams f32 [S, 16] (packed as for
     render_points) or depth f32 [S, H, W]; valid u8 [S, H, W] or None. -> z f32 [S, H, W] (`out`, or allocated here): the camera depth
@@ -1624,15 +1497,15 @@ def map_depth(points=None, cams=None, depth=None, valid=None, near=1e-3, out=Non
         raise L.OvgError("%s: exactly one of points / depth" % what)
     if points is not None:
         S, H, W = _map_shape(what, points, "points", (3,))
-        _map_tensor(what, points, "points", torch.float32, (S, H, W, 3))
-        _map_tensor(what, cams, "cams", torch.float32, (S, 16))
+        _tensor(what, points, "points", _F32, (S, H, W, 3))
+        _tensor(what, cams, "cams", _F32, (S, 16))
     else:
         S, H, W = _map_shape(what, depth, "depth")
-        _map_tensor(what, depth, "depth", torch.float32, (S, H, W))
-    _map_tensor(what, valid, "valid", torch.uint8, (S, H, W), True)
-    near = _tsdf_scalar(what, "near", near)
+        _tensor(what, depth, "depth", _F32, (S, H, W))
+    _tensor(what, valid, "valid", _U8, (S, H, W), optional=True)
+    near = _number(what, "near", near, lo=0, strict=True)
     src = points if points is not None else depth
-    out = _map_out(what, out, "out", torch.float32, (S, H, W), src.device)
+    out = _out(what, out, "out", _F32, (S, H, W), src.device)
     _chk_dev(points, cams, depth, valid, out)
     p = L.MapDepthParams()
     p.points, p.cams, p.depth, p.valid = L.ptr(points), L.ptr(cams) if points is not None else None, L.ptr(depth), L.ptr(valid)
@@ -1646,10 +1519,10 @@ def map_normals(points, z, rel_tol=0.03, out=None):
     [S, H, W, 3] (`out`, or allocated here), unit vectors towards the camera, (0, 0, 0) where the rule gives none."""
     what = "map_normals"
     S, H, W = _map_shape(what, points, "points", (3,))
-    _map_tensor(what, points, "points", torch.float32, (S, H, W, 3))
-    _map_tensor(what, z, "z", torch.float32, (S, H, W))
-    rel_tol = _map_tol(what, "rel_tol", rel_tol)
-    out = _map_out(what, out, "out", torch.float32, (S, H, W, 3), points.device)
+    _tensor(what, points, "points", _F32, (S, H, W, 3))
+    _tensor(what, z, "z", _F32, (S, H, W))
+    rel_tol = _number(what, "rel_tol", rel_tol, lo=0, f32=False)             # +inf switches the test off
+    out = _out(what, out, "out", _F32, (S, H, W, 3), points.device)
     _chk_dev(points, z, out)
     p = L.MapNormalsParams()
     p.points, p.z, p.S, p.H, p.W, p.rel_tol, p.normals = L.ptr(points), L.ptr(z), S, H, W, rel_tol, L.ptr(out)
@@ -1663,32 +1536,23 @@ def map_edges(z, normals=None, radius=1, rel_tol=0.03, min_cos=float("-inf"), ti
     MAP_NORMAL_EDGE / MAP_NO_NORMAL. tile: L.MAP_TILE_*, speed only."""
     what = "map_edges"
     S, H, W = _map_shape(what, z, "z")
-    _map_tensor(what, z, "z", torch.float32, (S, H, W))
-    _map_tensor(what, normals, "normals", torch.float32, (S, H, W, 3), True)
-    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= L.MAP_MAX_RADIUS:
-        raise L.OvgError("%s: radius must be 1 .. %d, got %r" % (what, L.MAP_MAX_RADIUS, radius))
-    rel_tol = _map_tol(what, "rel_tol", rel_tol)
-    if isinstance(min_cos, bool) or not isinstance(min_cos, (int, float)) or min_cos != min_cos:
-        raise L.OvgError("%s: min_cos must be a number, got %r" % (what, min_cos))
-    if isinstance(tile, bool) or not isinstance(tile, int) or not L.MAP_TILE_DEFAULT <= tile <= L.MAP_TILE_64x4:
-        raise L.OvgError("%s: unknown tile %r" % (what, tile))
-    out = _map_out(what, out, "out", torch.uint8, (S, H, W), z.device)
+    _tensor(what, z, "z", _F32, (S, H, W))
+    _tensor(what, normals, "normals", _F32, (S, H, W, 3), optional=True)
+    _int_in(what, "radius", radius, 1, L.MAP_MAX_RADIUS + 1)
+    rel_tol = _number(what, "rel_tol", rel_tol, lo=0, f32=False)             # +inf switches the test off
+    min_cos = _number(what, "min_cos", min_cos, f32=False)
+    _int_in(what, "tile", tile, L.MAP_TILE_DEFAULT, L.MAP_TILE_64x4 + 1)
+    out = _out(what, out, "out", _U8, (S, H, W), z.device)
     _chk_dev(z, normals, out)
     p = L.MapEdgesParams()
     p.z, p.normals, p.S, p.H, p.W, p.radius = L.ptr(z), L.ptr(normals), S, H, W, radius
-    p.rel_tol, p.min_cos, p.tile, p.pad, p.flags = rel_tol, float(min_cos), tile, 0, L.ptr(out)
+    p.rel_tol, p.min_cos, p.tile, p.pad, p.flags = rel_tol, min_cos, tile, 0, L.ptr(out)
     L.call("ovg_map_edges", p, _stream())
     return out
 
 
 def map_triangulate_workspace_bytes(S, H, W):
-    for v in (S, H, W):
-        if not -(1 << 31) <= int(v) < (1 << 31):
-            raise L.OvgError("ovg_map_triangulate_workspace_bytes: unsupported (S=%d, H=%d, W=%d)" % (S, H, W))
-    b = L.load().ovg_map_triangulate_workspace_bytes(int(S), int(H), int(W))
-    if b < 0:
-        raise L.OvgError("ovg_map_triangulate_workspace_bytes: unsupported (S=%d, H=%d, W=%d)" % (S, H, W))
-    return int(b)
+    return _ws_query("ovg_map_triangulate_workspace_bytes", S=S, H=H, W=W)
 
 
 def map_triangulate(stage, z, points, ws, rel_tol=0.03, keep=None, normals=None, colors=None, out_count=None, vertex_capacity=0,
@@ -1700,27 +1564,22 @@ def map_triangulate(stage, z, points, ws, rel_tol=0.03, keep=None, normals=None,
     faces int32 [., 3] from what the COUNT stage left in ws."""
     what = "map_triangulate"
     S, H, W = _map_shape(what, z, "z")
-    _map_tensor(what, z, "z", torch.float32, (S, H, W))
-    _map_tensor(what, points, "points", torch.float32, (S, H, W, 3))
-    _map_tensor(what, keep, "keep", torch.uint8, (S, H, W), True)
-    _map_tensor(what, normals, "normals", torch.float32, (S, H, W, 3), True)
-    _map_tensor(what, colors, "colors", torch.uint8, (S, H, W, 3), True)
-    rel_tol = _map_tol(what, "rel_tol", rel_tol)
+    _tensor(what, z, "z", _F32, (S, H, W))
+    _tensor(what, points, "points", _F32, (S, H, W, 3))
+    _tensor(what, keep, "keep", _U8, (S, H, W), optional=True)
+    _tensor(what, normals, "normals", _F32, (S, H, W, 3), optional=True)
+    _tensor(what, colors, "colors", _U8, (S, H, W, 3), optional=True)
+    rel_tol = _number(what, "rel_tol", rel_tol, lo=0, f32=False)             # +inf switches the test off
     if stage not in (L.MAP_COUNT, L.MAP_SCATTER, L.MAP_COUNT | L.MAP_SCATTER):
         raise L.OvgError("%s: unknown stage %r" % (what, stage))
-    for name, v in (("vertex_capacity", vertex_capacity), ("face_capacity", face_capacity)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 62:
-            raise L.OvgError("%s: %s must be a non-negative integer, got %r" % (what, name, v))
-    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    _int_in(what, "vertex_capacity", vertex_capacity, 0, 1 << 62)
+    _int_in(what, "face_capacity", face_capacity, 0, 1 << 62)
+    _tensor(what, ws, "ws", _U8)
     if stage & L.MAP_SCATTER:
-        outs = ((vertices, torch.float32, 3 * vertex_capacity), (out_normals, torch.float32, 3 * vertex_capacity),
-                (out_colors, torch.uint8, 3 * vertex_capacity), (pixel_index, torch.int64, vertex_capacity), (faces, torch.int32, 3 * face_capacity))
-        for t, dt, need in outs:
-            if need and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < need):
-                raise L.OvgError("%s: output buffers must be contiguous and hold the capacities" % what)
-    if not isinstance(out_count, torch.Tensor) or out_count.dtype != torch.int64 or out_count.numel() < 2 or not out_count.is_contiguous():
-        raise L.OvgError("%s: out_count must be a contiguous int64 device tensor of two elements" % what)
+        _capacity_buffers(what, ((vertices, "vertices", _F32, 3 * vertex_capacity, True), (out_normals, "out_normals", _F32, 3 * vertex_capacity, True),
+                                 (out_colors, "out_colors", _U8, 3 * vertex_capacity, True), (pixel_index, "pixel_index", _I64, vertex_capacity, True),
+                                 (faces, "faces", _I32, 3 * face_capacity, True)))
+    _tensor(what, out_count, "out_count", _I64, min_numel=2)
     _chk_dev(z, points, keep, normals, colors, ws, out_count, vertices, out_normals, out_colors, pixel_index, faces)
     p = L.MapTriangulateParams()
     p.z, p.points, p.keep, p.normals, p.colors = L.ptr(z), L.ptr(points), L.ptr(keep), L.ptr(normals), L.ptr(colors)
@@ -1733,16 +1592,19 @@ def map_triangulate(stage, z, points, ws, rel_tol=0.03, keep=None, normals=None,
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# mesh simplification by vertex clustering (ovg_mesh_simplify)
+# meshes: simplification by vertex clustering (ovg_mesh_simplify); cleaning: components and edge statistics, ordered sub-meshes,
+# Laplacian / Taubin smoothing (ovg_mesh_topology / _select / _smooth)
 # ---------------------------------------------------------------------------------------------------------------------------------
+def _meshops_mesh(what, vertices, faces, ws, max_faces=1 << 31):
+    """The checks the mesh entries share -> (M, F)."""
+    M = _points(what, vertices, "vertices", 1, 1 << 31)
+    F = _table(what, faces, "faces", _I32, 3, 1, max_faces)
+    _tensor(what, ws, "ws", _U8)
+    return M, F
+
+
 def mesh_simplify_workspace_bytes(vertices, faces):
-    for v in (vertices, faces):
-        if not -(1 << 63) <= int(v) < (1 << 63):
-            raise L.OvgError("ovg_mesh_simplify_workspace_bytes: unsupported (vertices=%d, faces=%d)" % (vertices, faces))
-    b = L.load().ovg_mesh_simplify_workspace_bytes(int(vertices), int(faces))
-    if b < 0:
-        raise L.OvgError("ovg_mesh_simplify_workspace_bytes: unsupported (vertices=%d, faces=%d)" % (vertices, faces))
-    return int(b)
+    return _ws_query("ovg_mesh_simplify_workspace_bytes", vertices=vertices, faces=faces)
 
 
 def mesh_simplify(stage, vertices, faces, voxel, ws, normals=None, colors=None, position=L.MS_POS_MEAN, out_count=None, vertex_capacity=0,
@@ -1754,39 +1616,23 @@ def mesh_simplify(stage, vertices, faces, voxel, ws, normals=None, colors=None, 
     colors are given; source_index int64 [.] and vertex_count int32 [.] optional) and the first face_capacity faces to out_faces int32
     [., 3] from what the COUNT stage left in ws. position: L.MS_POS_MEAN or L.MS_POS_FIRST."""
     what = "mesh_simplify"
-    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or not 1 <= vertices.shape[0] < 1 << 31:
-        raise L.OvgError("%s: vertices must be a tensor [M, 3], 1 <= M < 2^31" % what)
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or not 1 <= faces.shape[0] < (1 << 32) - 1:
-        raise L.OvgError("%s: faces must be a tensor [F, 3], 1 <= F < 2^32 - 1" % what)
-    M, F = int(vertices.shape[0]), int(faces.shape[0])
-    _map_tensor(what, vertices, "vertices", torch.float32, (M, 3))
-    _map_tensor(what, faces, "faces", torch.int32, (F, 3))
-    _map_tensor(what, normals, "normals", torch.float32, (M, 3), True)
-    _map_tensor(what, colors, "colors", torch.uint8, (M, 3), True)
-    if not isinstance(voxel, torch.Tensor) or voxel.dtype != torch.float32 or voxel.numel() != 1 or not voxel.is_contiguous():
-        raise L.OvgError("%s: voxel must be a contiguous f32 tensor of one element" % what)
+    M, F = _meshops_mesh(what, vertices, faces, ws, (1 << 32) - 1)
+    _tensor(what, normals, "normals", _F32, (M, 3), optional=True)
+    _tensor(what, colors, "colors", _U8, (M, 3), optional=True)
+    _tensor(what, voxel, "voxel", _F32, numel=1)
     if stage not in (L.MS_COUNT, L.MS_SCATTER, L.MS_COUNT | L.MS_SCATTER):
         raise L.OvgError("%s: unknown stage %r" % (what, stage))
     if position not in (L.MS_POS_MEAN, L.MS_POS_FIRST):
         raise L.OvgError("%s: unknown position %r" % (what, position))
-    for name, v in (("vertex_capacity", vertex_capacity), ("face_capacity", face_capacity)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 62:
-            raise L.OvgError("%s: %s must be a non-negative integer, got %r" % (what, name, v))
-    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
+    _int_in(what, "vertex_capacity", vertex_capacity, 0, 1 << 62)
+    _int_in(what, "face_capacity", face_capacity, 0, 1 << 62)
     if stage & L.MS_SCATTER:
         if vertex_capacity and ((normals is None) != (out_normals is None) or (colors is None) != (out_colors is None)):
             raise L.OvgError("%s: out_normals / out_colors go with normals / colors" % what)
-        outs = ((out_vertices, torch.float32, 3 * vertex_capacity, True), (out_normals, torch.float32, 3 * vertex_capacity, False),
-                (out_colors, torch.uint8, 3 * vertex_capacity, False), (source_index, torch.int64, vertex_capacity, False),
-                (vertex_count, torch.int32, vertex_capacity, False), (out_faces, torch.int32, 3 * face_capacity, True))
-        for t, dt, need, required in outs:
-            if need and (t is not None or required) and \
-                    (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < need):
-                raise L.OvgError("%s: output buffers must be contiguous and hold the capacities" % what)
-    if (stage & L.MS_COUNT or out_count is not None) and \
-            (not isinstance(out_count, torch.Tensor) or out_count.dtype != torch.int64 or out_count.numel() < 6 or not out_count.is_contiguous()):
-        raise L.OvgError("%s: out_count must be a contiguous int64 device tensor of six elements" % what)
+        _capacity_buffers(what, ((out_vertices, "out_vertices", _F32, 3 * vertex_capacity, True), (out_normals, "out_normals", _F32, 3 * vertex_capacity, False),
+                                 (out_colors, "out_colors", _U8, 3 * vertex_capacity, False), (source_index, "source_index", _I64, vertex_capacity, False),
+                                 (vertex_count, "vertex_count", _I32, vertex_capacity, False), (out_faces, "out_faces", _I32, 3 * face_capacity, True)))
+    _tensor(what, out_count, "out_count", _I64, min_numel=6, optional=not stage & L.MS_COUNT)
     _chk_dev(vertices, faces, voxel, ws, normals, colors, out_count, out_vertices, out_normals, out_colors, source_index, vertex_count, out_faces)
     p = L.MeshSimplifyParams()
     p.vertices, p.faces, p.normals, p.colors, p.voxel = L.ptr(vertices), L.ptr(faces), L.ptr(normals), L.ptr(colors), L.ptr(voxel)
@@ -1798,42 +1644,16 @@ def mesh_simplify(stage, vertices, faces, voxel, ws, normals=None, colors=None, 
     L.call("ovg_mesh_simplify", p, _stream())
 
 
-# ---------------------------------------------------------------------------------------------------------------------------------
-# mesh cleaning: components and edge statistics, ordered sub-meshes, Laplacian / Taubin smoothing (ovg_mesh_topology / _select / _smooth)
-# ---------------------------------------------------------------------------------------------------------------------------------
-def _meshops_workspace_bytes(name, vertices, faces):
-    if not all(-(1 << 63) <= int(v) < (1 << 63) for v in (vertices, faces)):
-        raise L.OvgError("%s: unsupported (vertices=%d, faces=%d)" % (name, vertices, faces))
-    b = getattr(L.load(), name)(int(vertices), int(faces))
-    if b < 0:
-        raise L.OvgError("%s: unsupported (vertices=%d, faces=%d)" % (name, vertices, faces))
-    return int(b)
-
-
 def mesh_topology_workspace_bytes(vertices, faces):
-    return _meshops_workspace_bytes("ovg_mesh_topology_workspace_bytes", vertices, faces)
+    return _ws_query("ovg_mesh_topology_workspace_bytes", vertices=vertices, faces=faces)
 
 
 def mesh_select_workspace_bytes(vertices, faces):
-    return _meshops_workspace_bytes("ovg_mesh_select_workspace_bytes", vertices, faces)
+    return _ws_query("ovg_mesh_select_workspace_bytes", vertices=vertices, faces=faces)
 
 
 def mesh_smooth_workspace_bytes(vertices, faces):
-    return _meshops_workspace_bytes("ovg_mesh_smooth_workspace_bytes", vertices, faces)
-
-
-def _meshops_mesh(what, vertices, faces, ws):
-    """The checks the three entries share -> (M, F)."""
-    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or not 1 <= vertices.shape[0] < 1 << 31:
-        raise L.OvgError("%s: vertices must be a tensor [M, 3], 1 <= M < 2^31" % what)
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or not 1 <= faces.shape[0] < 1 << 31:
-        raise L.OvgError("%s: faces must be a tensor [F, 3], 1 <= F < 2^31" % what)
-    M, F = int(vertices.shape[0]), int(faces.shape[0])
-    _map_tensor(what, vertices, "vertices", torch.float32, (M, 3))
-    _map_tensor(what, faces, "faces", torch.int32, (F, 3))
-    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise L.OvgError("%s: ws must be a contiguous uint8 tensor" % what)
-    return M, F
+    return _ws_query("ovg_mesh_smooth_workspace_bytes", vertices=vertices, faces=faces)
 
 
 def mesh_topology(vertices, faces, ws, vertex_root, face_root, vertex_flags, out_count):
@@ -1843,10 +1663,10 @@ def mesh_topology(vertices, faces, ws, vertex_root, face_root, vertex_flags, out
     non-manifold vertices, status flags (L.MT_INTERNAL)."""
     what = "mesh_topology"
     M, F = _meshops_mesh(what, vertices, faces, ws)
-    _map_tensor(what, vertex_root, "vertex_root", torch.int32, (M,))
-    _map_tensor(what, face_root, "face_root", torch.int32, (F,))
-    _map_tensor(what, vertex_flags, "vertex_flags", torch.uint8, (M,))
-    _map_tensor(what, out_count, "out_count", torch.int64, (8,))
+    _tensor(what, vertex_root, "vertex_root", _I32, (M,))
+    _tensor(what, face_root, "face_root", _I32, (F,))
+    _tensor(what, vertex_flags, "vertex_flags", _U8, (M,))
+    _tensor(what, out_count, "out_count", _I64, (8,))
     _chk_dev(vertices, faces, ws, vertex_root, face_root, vertex_flags, out_count)
     p = L.MeshTopologyParams()
     p.vertices, p.faces, p.num_vertices, p.num_faces = L.ptr(vertices), L.ptr(faces), M, F
@@ -1864,23 +1684,16 @@ def mesh_select(stage, vertices, faces, ws, face_keep=None, vertex_keep=None, ou
     left in ws."""
     what = "mesh_select"
     M, F = _meshops_mesh(what, vertices, faces, ws)
-    _map_tensor(what, face_keep, "face_keep", torch.uint8, (F,), True)
-    _map_tensor(what, vertex_keep, "vertex_keep", torch.uint8, (M,), True)
+    _tensor(what, face_keep, "face_keep", _U8, (F,), optional=True)
+    _tensor(what, vertex_keep, "vertex_keep", _U8, (M,), optional=True)
     if stage not in (L.MSEL_COUNT, L.MSEL_SCATTER, L.MSEL_COUNT | L.MSEL_SCATTER):
         raise L.OvgError("%s: unknown stage %r" % (what, stage))
-    for name, v in (("vertex_capacity", vertex_capacity), ("face_capacity", face_capacity)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 62:
-            raise L.OvgError("%s: %s must be a non-negative integer, got %r" % (what, name, v))
+    _int_in(what, "vertex_capacity", vertex_capacity, 0, 1 << 62)
+    _int_in(what, "face_capacity", face_capacity, 0, 1 << 62)
     if stage & L.MSEL_SCATTER:
-        outs = ((out_vertices, torch.float32, 3 * vertex_capacity, True), (source_index, torch.int64, vertex_capacity, False),
-                (out_faces, torch.int32, 3 * face_capacity, True), (face_index, torch.int64, face_capacity, False))
-        for t, dt, need, required in outs:
-            if need and (t is not None or required) and \
-                    (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous() or t.numel() < need):
-                raise L.OvgError("%s: output buffers must be contiguous and hold the capacities" % what)
-    if (stage & L.MSEL_COUNT or out_count is not None) and \
-            (not isinstance(out_count, torch.Tensor) or out_count.dtype != torch.int64 or out_count.numel() < 2 or not out_count.is_contiguous()):
-        raise L.OvgError("%s: out_count must be a contiguous int64 device tensor of two elements" % what)
+        _capacity_buffers(what, ((out_vertices, "out_vertices", _F32, 3 * vertex_capacity, True), (source_index, "source_index", _I64, vertex_capacity, False),
+                                 (out_faces, "out_faces", _I32, 3 * face_capacity, True), (face_index, "face_index", _I64, face_capacity, False)))
+    _tensor(what, out_count, "out_count", _I64, min_numel=2, optional=not stage & L.MSEL_COUNT)
     _chk_dev(vertices, faces, ws, face_keep, vertex_keep, out_count, out_vertices, source_index, out_faces, face_index)
     p = L.MeshSelectParams()
     p.vertices, p.faces, p.face_keep, p.vertex_keep = L.ptr(vertices), L.ptr(faces), L.ptr(face_keep), L.ptr(vertex_keep)
@@ -1898,15 +1711,12 @@ def mesh_smooth(vertices, faces, ws, iterations, lam, mu, out_vertices, out_stat
     one int64 of out_status."""
     what = "mesh_smooth"
     M, F = _meshops_mesh(what, vertices, faces, ws)
-    _map_tensor(what, fixed, "fixed", torch.uint8, (M,), True)
-    _map_tensor(what, out_vertices, "out_vertices", torch.float32, (M, 3))
-    _map_tensor(what, out_normals, "out_normals", torch.float32, (M, 3), True)
-    _map_tensor(what, out_status, "out_status", torch.int64, (1,))
-    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= 65536:
-        raise L.OvgError("%s: iterations must be an integer in [0, 65536], got %r" % (what, iterations))
-    for name, v in (("lam", lam), ("mu", mu)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not abs(float(v)) <= 3.4028234663852886e38:
-            raise L.OvgError("%s: %s must be a finite float32 value, got %r" % (what, name, v))
+    _tensor(what, fixed, "fixed", _U8, (M,), optional=True)
+    _tensor(what, out_vertices, "out_vertices", _F32, (M, 3))
+    _tensor(what, out_normals, "out_normals", _F32, (M, 3), optional=True)
+    _tensor(what, out_status, "out_status", _I64, (1,))
+    _int_in(what, "iterations", iterations, 0, 65537)
+    lam, mu = _number(what, "lam", lam), _number(what, "mu", mu)
     if not isinstance(fix_boundary, bool):
         raise L.OvgError("%s: fix_boundary must be True or False, got %r" % (what, fix_boundary))
     if out_vertices.data_ptr() == vertices.data_ptr():
@@ -1914,7 +1724,7 @@ def mesh_smooth(vertices, faces, ws, iterations, lam, mu, out_vertices, out_stat
     _chk_dev(vertices, faces, ws, fixed, out_vertices, out_normals, out_status)
     p = L.MeshSmoothParams()
     p.vertices, p.faces, p.fixed, p.num_vertices, p.num_faces = L.ptr(vertices), L.ptr(faces), L.ptr(fixed), M, F
-    p.iterations, p.fix_boundary, p.lam, p.mu = iterations, int(fix_boundary), float(lam), float(mu)
+    p.iterations, p.fix_boundary, p.lam, p.mu = iterations, int(fix_boundary), lam, mu
     p.out_vertices, p.out_normals, p.out_status = L.ptr(out_vertices), L.ptr(out_normals), L.ptr(out_status)
     p.ws, p.ws_bytes = L.ptr(ws), nbytes(ws)
     L.call("ovg_mesh_smooth", p, _stream())

@@ -5,13 +5,12 @@ checks."""
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import consistency_twin as twin
 from omnivggt_official_amd import lib as L
@@ -186,25 +185,11 @@ def test_synthetic_scene_exercises_every_class():
 
 
 def test_ctypes_struct_layout_matches_c_consistency():
-    fields = [n for n, _ in L.ConsistencyParams._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %zu\\n", sizeof(ovg_consistency_params));\n'
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(ovg_consistency_params, %s));\n' % (n, n)
-    src += ('printf("enums %d %d %d %d %d %d %d %d %d\\n", OVG_MVC_MAX_VIEWS, OVG_MVC_TILE_DEFAULT, OVG_MVC_TILE_256x1, OVG_MVC_TILE_16x16, '
-            'OVG_MVC_TILE_8x32, OVG_MVC_TILE_32x8, OVG_MVC_ROTATE_TARGETS, OVG_MVC_KEEP_MAP, OVG_ABI_VERSION);\nreturn 0;}\n')
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(L.ConsistencyParams)
-    for n in fields:
-        assert int(got[n][0]) == getattr(L.ConsistencyParams, n).offset, n
-    assert [int(v) for v in got["enums"]] == [L.MVC_MAX_VIEWS, L.MVC_TILE_DEFAULT, L.MVC_TILE_256x1, L.MVC_TILE_16x16, L.MVC_TILE_8x32,
-                                              L.MVC_TILE_32x8, L.MVC_ROTATE_TARGETS, L.MVC_KEEP_MAP, L.ABI_VERSION]
+    enums, _ = abi_layout.check({"ovg_consistency_params": L.ConsistencyParams},
+                                ["OVG_MVC_MAX_VIEWS", "OVG_MVC_TILE_DEFAULT", "OVG_MVC_TILE_256x1", "OVG_MVC_TILE_16x16", "OVG_MVC_TILE_8x32",
+                                 "OVG_MVC_TILE_32x8", "OVG_MVC_ROTATE_TARGETS", "OVG_MVC_KEEP_MAP", "OVG_ABI_VERSION"])
+    assert enums == [L.MVC_MAX_VIEWS, L.MVC_TILE_DEFAULT, L.MVC_TILE_256x1, L.MVC_TILE_16x16, L.MVC_TILE_8x32,
+                     L.MVC_TILE_32x8, L.MVC_ROTATE_TARGETS, L.MVC_KEEP_MAP, L.ABI_VERSION]
     assert L.ABI_VERSION == 13
     text = open(HEADER).read()
     assert re.search(r"int64_t\s+ovg_consistency_workspace_bytes\s*\(\s*int32_t\s+S,\s*int32_t\s+H,\s*int32_t\s+W\s*\)\s*;", text)

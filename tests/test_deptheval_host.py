@@ -5,13 +5,12 @@ layers' argument checks, the degenerate groups, and the pose figures on cases wo
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import deptheval_twin as twin
 from omnivggt_official_amd import lib as L
@@ -137,25 +136,9 @@ def test_twin_degenerate_groups_are_identity_with_the_right_bit():
 # the C ABI without a device
 # ---------------------------------------------------------------------------------------------
 def _layout(struct, cname, extra):
-    fields = [n for n, _ in struct._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %%zu\\n", sizeof(%s));\n' % cname
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(%s, %s));\n' % (n, cname, n)
-    src += 'printf("enums %s\\n", %s);\n' % (" ".join(["%d"] * len(extra)), ", ".join(extra))
-    src += 'printf("eps %.17g\\n", (double)OVG_DEPTHEVAL_SPREAD_EPS);\nreturn 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(struct)
-    for n in fields:
-        assert int(got[n][0]) == getattr(struct, n).offset, n
-    assert float(got["eps"][0]) == L.DEPTHEVAL_SPREAD_EPS == twin.SPREAD_EPS == 2.0 ** -40
-    return [int(v) for v in got["enums"]]
+    enums, (eps,) = abi_layout.check({cname: struct}, extra, ["OVG_DEPTHEVAL_SPREAD_EPS"])
+    assert eps == L.DEPTHEVAL_SPREAD_EPS == twin.SPREAD_EPS == 2.0 ** -40
+    return enums
 
 
 def test_ctypes_struct_layouts_and_enums_match_c_deptheval():

@@ -5,13 +5,12 @@ Python API's argument checks."""
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import fps_twin as twin
 from omnivggt_official_amd import lib as L
@@ -96,25 +95,10 @@ def test_twin_crafted_inputs():
 
 
 def test_ctypes_struct_layout_matches_c_fps():
-    fields = [n for n, _ in L.FpsParams._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %zu\\n", sizeof(ovg_fps_params));\n'
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(ovg_fps_params, %s));\n' % (n, n)
-    src += ('printf("enums %d %d %d %d %d %d %d\\n", OVG_FPS_SMALL_MAX, OVG_FPS_TILE, OVG_FPS_INCLUDE_LAST, OVG_FPS_PATH_AUTO, '
-            'OVG_FPS_PATH_ONE_WORKGROUP, OVG_FPS_PATH_PER_STEP, OVG_ABI_VERSION);\nreturn 0;}\n')
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(L.FpsParams)
-    for n in fields:
-        assert int(got[n][0]) == getattr(L.FpsParams, n).offset, n
-    assert [int(v) for v in got["enums"]] == [L.FPS_SMALL_MAX, L.FPS_TILE, L.FPS_INCLUDE_LAST, L.FPS_PATH_AUTO, L.FPS_PATH_ONE_WORKGROUP,
-                                               L.FPS_PATH_PER_STEP, L.ABI_VERSION]
+    enums, _ = abi_layout.check({"ovg_fps_params": L.FpsParams},
+                                ["OVG_FPS_SMALL_MAX", "OVG_FPS_TILE", "OVG_FPS_INCLUDE_LAST", "OVG_FPS_PATH_AUTO", "OVG_FPS_PATH_ONE_WORKGROUP",
+                                 "OVG_FPS_PATH_PER_STEP", "OVG_ABI_VERSION"])
+    assert enums == [L.FPS_SMALL_MAX, L.FPS_TILE, L.FPS_INCLUDE_LAST, L.FPS_PATH_AUTO, L.FPS_PATH_ONE_WORKGROUP, L.FPS_PATH_PER_STEP, L.ABI_VERSION]
     assert (L.FPS_INCLUDE_LAST, L.FPS_PATH_AUTO, L.FPS_PATH_ONE_WORKGROUP, L.FPS_PATH_PER_STEP) == (1, 0, 1, 2)
     text = open(HEADER).read()
     assert re.search(r"int64_t\s+ovg_fps_workspace_bytes\s*\(\s*int64_t\s+batch,\s*int64_t\s+n,\s*int64_t\s+npoint\s*\)\s*;", text)

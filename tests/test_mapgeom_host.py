@@ -6,13 +6,12 @@ conditions under which the GPU comparison of tests/test_gpu_mapgeom.py cannot pa
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import mapgeom_scenes as scenes
 import mapgeom_twin as twin
@@ -181,23 +180,7 @@ def test_the_gpu_scene_exercises_every_branch():
 # the C ABI without a device
 # ---------------------------------------------------------------------------------------------
 def _layout(struct, cname, extra):
-    fields = [n for n, _ in struct._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %%zu\\n", sizeof(%s));\n' % cname
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(%s, %s));\n' % (n, cname, n)
-    src += 'printf("enums %s\\n", %s);\nreturn 0;}\n' % (" ".join(["%d"] * len(extra)), ", ".join(extra))
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(struct)
-    for n in fields:
-        assert int(got[n][0]) == getattr(struct, n).offset, n
-    return [int(v) for v in got["enums"]]
+    return abi_layout.check({cname: struct}, extra)[0]
 
 
 def test_ctypes_struct_layouts_and_enums_match_c_mapgeom():

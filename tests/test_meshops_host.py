@@ -4,13 +4,12 @@ the workspace queries, the refusals that return before any HIP call) and the arg
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import meshops_twin as twin
 from omnivggt_official_amd import lib as L
@@ -188,25 +187,9 @@ STRUCTS = (("ovg_mesh_topology_params", "MeshTopologyParams"), ("ovg_mesh_select
 def test_ctypes_struct_layouts_and_enums_match_c():
     enums = ["OVG_MT_REFERENCED", "OVG_MT_BOUNDARY", "OVG_MT_NONMANIFOLD", "OVG_MT_INTERNAL", "OVG_MSEL_COUNT", "OVG_MSEL_SCATTER",
              "OVG_MSM_NONFINITE", "OVG_ABI_VERSION"]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    for cname, pyname in STRUCTS:
-        src += 'printf("%s.sizeof %%zu\\n", sizeof(%s));\n' % (cname, cname)
-        for n, _ in getattr(L, pyname)._fields_:
-            src += 'printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (cname, n, cname, "lambda" if n == "lam" else n)
-    src += 'printf("enums %s\\n", %s);\nreturn 0;}\n' % (" ".join(["%d"] * len(enums)), ", ".join(enums))
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        got = {k[0]: k[1:] for k in (line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines())}
-    for cname, pyname in STRUCTS:
-        cls = getattr(L, pyname)
-        assert int(got[cname + ".sizeof"][0]) == ctypes.sizeof(cls), cname
-        for n, _ in cls._fields_:
-            assert int(got["%s.%s" % (cname, n)][0]) == getattr(cls, n).offset, (cname, n)
-    assert [int(x) for x in got["enums"]] == [L.MT_REFERENCED, L.MT_BOUNDARY, L.MT_NONMANIFOLD, L.MT_INTERNAL, L.MSEL_COUNT, L.MSEL_SCATTER,
-                                               L.MSM_NONFINITE, L.ABI_VERSION] == [1, 2, 4, 1, 1, 2, 1, 13]
+    got, _ = abi_layout.check({cname: getattr(L, pyname) for cname, pyname in STRUCTS}, enums, rename={"lam": "lambda"})
+    assert got == [L.MT_REFERENCED, L.MT_BOUNDARY, L.MT_NONMANIFOLD, L.MT_INTERNAL, L.MSEL_COUNT, L.MSEL_SCATTER,
+                   L.MSM_NONFINITE, L.ABI_VERSION] == [1, 2, 4, 1, 1, 2, 1, 13]
     assert (twin.REFERENCED, twin.BOUNDARY, twin.NONMANIFOLD) == (L.MT_REFERENCED, L.MT_BOUNDARY, L.MT_NONMANIFOLD)
 
 

@@ -4,13 +4,12 @@ call) and the argument checks of postprocess.simplify_mesh that need no device."
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import meshsimp_twin as twin
 import voxelgrid_twin
@@ -145,25 +144,9 @@ def test_grid_is_the_grid_of_voxel_downsample_and_flags():
 # the C ABI without a device
 # ---------------------------------------------------------------------------------------------
 def test_ctypes_struct_layout_and_enums_match_c_meshsimp():
-    fields = [n for n, _ in L.MeshSimplifyParams._fields_]
     enums = ["OVG_MS_COUNT", "OVG_MS_SCATTER", "OVG_MS_OVERFLOW", "OVG_MS_BAD_VOXEL", "OVG_MS_POS_MEAN", "OVG_MS_POS_FIRST", "OVG_ABI_VERSION"]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %zu\\n", sizeof(ovg_mesh_simplify_params));\n'
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(ovg_mesh_simplify_params, %s));\n' % (n, n)
-    src += 'printf("enums %s\\n", %s);\nreturn 0;}\n' % (" ".join(["%d"] * len(enums)), ", ".join(enums))
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(L.MeshSimplifyParams)
-    for n in fields:
-        assert int(got[n][0]) == getattr(L.MeshSimplifyParams, n).offset, n
-    assert [int(x) for x in got["enums"]] == [L.MS_COUNT, L.MS_SCATTER, L.MS_OVERFLOW, L.MS_BAD_VOXEL, L.MS_POS_MEAN, L.MS_POS_FIRST, L.ABI_VERSION] == \
-        [1, 2, 1, 2, 0, 1, 13]
+    got, _ = abi_layout.check({"ovg_mesh_simplify_params": L.MeshSimplifyParams}, enums)
+    assert got == [L.MS_COUNT, L.MS_SCATTER, L.MS_OVERFLOW, L.MS_BAD_VOXEL, L.MS_POS_MEAN, L.MS_POS_FIRST, L.ABI_VERSION] == [1, 2, 1, 2, 0, 1, 13]
     assert postprocess.MESH_POSITIONS == {"mean": L.MS_POS_MEAN, "first": L.MS_POS_FIRST}
 
 

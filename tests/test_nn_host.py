@@ -4,13 +4,12 @@ the workspace query, argument checks that return before any HIP call) and the Py
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import nn_twin as twin
 from omnivggt_official_amd import lib as L
@@ -122,23 +121,9 @@ def test_twin_reciprocal_never_matches_a_missing_neighbour():
 
 
 def test_ctypes_struct_layout_matches_c_nn():
-    fields = [n for n, _ in L.NnParams._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %zu\\n", sizeof(ovg_nn_params));\n'
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(ovg_nn_params, %s));\n' % (n, n)
-    src += 'printf("enums %d %d %d %d\\n", OVG_NN_QUERY_TILE, OVG_NN_REFERENCE_TILE, OVG_NN_EXCLUDE_SAME_INDEX, OVG_ABI_VERSION);\nreturn 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(L.NnParams)
-    for n in fields:
-        assert int(got[n][0]) == getattr(L.NnParams, n).offset, n
-    assert [int(v) for v in got["enums"]] == [L.NN_QUERY_TILE, L.NN_REFERENCE_TILE, L.NN_EXCLUDE_SAME_INDEX, L.ABI_VERSION]
+    enums, _ = abi_layout.check({"ovg_nn_params": L.NnParams},
+                                ["OVG_NN_QUERY_TILE", "OVG_NN_REFERENCE_TILE", "OVG_NN_EXCLUDE_SAME_INDEX", "OVG_ABI_VERSION"])
+    assert enums == [L.NN_QUERY_TILE, L.NN_REFERENCE_TILE, L.NN_EXCLUDE_SAME_INDEX, L.ABI_VERSION]
     text = open(HEADER).read()
     assert re.search(r"int64_t\s+ovg_nn_workspace_bytes\s*\(\s*int64_t\s+nq,\s*int64_t\s+nr\s*\)\s*;", text)
     assert re.search(r"int\s+ovg_nearest_neighbours\s*\(\s*const\s+ovg_nn_params\s*\*\s*,\s*void\s*\*\s*stream\s*\)\s*;", text)

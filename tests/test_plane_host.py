@@ -5,14 +5,13 @@ argument checks that return before any HIP call) and the Python API's argument c
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import plane_twin as twin
 from omnivggt_official_amd import lib as L
@@ -191,23 +190,7 @@ def test_degenerate_refits_keep_the_plane():
 
 
 def _layout(struct, cname, extra):
-    fields = [n for n, _ in struct._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %%zu\\n", sizeof(%s));\n' % cname
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(%s, %s));\n' % (n, cname, n)
-    src += 'printf("enums %s\\n", %s);\nreturn 0;}\n' % (" ".join(["%d"] * len(extra)), ", ".join(extra))
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(struct)
-    for n in fields:
-        assert int(got[n][0]) == getattr(struct, n).offset, n
-    return [int(v) for v in got["enums"]]
+    return abi_layout.check({cname: struct}, extra)[0]
 
 
 def test_library_exports_the_entries_and_ctypes_layout_matches_c():

@@ -2,22 +2,18 @@
 fixed-point tables against the twin's, the loaders' geometry and camera code against oracle/loader_oracle.py, and the C ABI of the
 preprocessing entries without a device."""
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
 
-import common
+import abi_layout
 import loader_oracle as lo
 import resample_twin as twin
 from omnivggt_official_amd import lib as L
 from omnivggt_official_amd import preprocess
 
-HEADER = os.path.join(common.ROOT, "include", "omnivggt_hip.h")
 
 GEOMETRIES = twin.GEOMETRIES
 
@@ -102,25 +98,8 @@ def test_abi_version_and_struct_layout_match_c():
     assert L.ABI_VERSION == 13 and lib.ovg_abi_version() == 13
     pairs = {"ovg_resample_frame": L.ResampleFrame, "ovg_resample_params": L.ResampleParams, "ovg_depth_frame": L.DepthFrame,
              "ovg_depth_params": L.DepthParams}
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    for name in pairs:
-        src += 'printf("%s %%zu\\n", sizeof(%s));\n' % (name, name)
-    for name, cls in pairs.items():
-        for field, _ in cls._fields_:
-            src += 'printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (name, field, name, field)
-    src += 'printf("fmt %d %d\\n", OVG_RS_F32_CHW, OVG_RS_U8_HWC);\nreturn 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().strip().splitlines()
-    got = {line.split(" ", 1)[0]: line.split(" ", 1)[1] for line in out}
-    for name, cls in pairs.items():
-        assert int(got[name]) == ctypes.sizeof(cls), name
-        for field, _ in cls._fields_:
-            assert int(got["%s.%s" % (name, field)]) == getattr(cls, field).offset, (name, field)
-    assert got["fmt"] == "%d %d" % (L.RS_F32_CHW, L.RS_U8_HWC)
+    fmt, _ = abi_layout.check(pairs, ["OVG_RS_F32_CHW", "OVG_RS_U8_HWC"])
+    assert fmt == [L.RS_F32_CHW, L.RS_U8_HWC]
 
 
 def _valid_resample():

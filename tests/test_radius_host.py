@@ -5,13 +5,12 @@ API's argument checks."""
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import nn_twin
 import radius_twin as twin
@@ -169,25 +168,11 @@ def test_dictionary_grid_on_offset_clouds(offset):
 
 
 def test_ctypes_struct_layout_matches_c_radius():
-    fields = [n for n, _ in L.RadiusParams._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %zu\\n", sizeof(ovg_radius_params));\n'
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(ovg_radius_params, %s));\n' % (n, n)
-    src += ('printf("enums %d %d %d %d %d %d %d %d %d\\n", OVG_RS_BUILD, OVG_RS_SEARCH, OVG_RS_EXCLUDE_SAME_INDEX, OVG_RS_BAD_ORIGIN, '
-            'OVG_RS_OVER_BUDGET, OVG_RS_NOT_BUILT, OVG_RS_MIN_SLOTS, OVG_RS_QUERY_BLOCK, OVG_ABI_VERSION);\nreturn 0;}\n')
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(L.RadiusParams)
-    for n in fields:
-        assert int(got[n][0]) == getattr(L.RadiusParams, n).offset, n
-    assert [int(v) for v in got["enums"]] == [L.RS_BUILD, L.RS_SEARCH, L.RS_EXCLUDE_SAME_INDEX, L.RS_BAD_ORIGIN, L.RS_OVER_BUDGET,
-                                              L.RS_NOT_BUILT, L.RS_MIN_SLOTS, L.RS_QUERY_BLOCK, L.ABI_VERSION]
+    enums, _ = abi_layout.check({"ovg_radius_params": L.RadiusParams},
+                                ["OVG_RS_BUILD", "OVG_RS_SEARCH", "OVG_RS_EXCLUDE_SAME_INDEX", "OVG_RS_BAD_ORIGIN", "OVG_RS_OVER_BUDGET",
+                                 "OVG_RS_NOT_BUILT", "OVG_RS_MIN_SLOTS", "OVG_RS_QUERY_BLOCK", "OVG_ABI_VERSION"])
+    assert enums == [L.RS_BUILD, L.RS_SEARCH, L.RS_EXCLUDE_SAME_INDEX, L.RS_BAD_ORIGIN, L.RS_OVER_BUDGET,
+                     L.RS_NOT_BUILT, L.RS_MIN_SLOTS, L.RS_QUERY_BLOCK, L.ABI_VERSION]
     text = open(HEADER).read()
     assert re.search(r"int64_t\s+ovg_radius_workspace_bytes\s*\(\s*int64_t\s+nq,\s*int64_t\s+nr\s*\)\s*;", text)
     assert re.search(r"int\s+ovg_radius_search\s*\(\s*const\s+ovg_radius_params\s*\*\s*,\s*void\s*\*\s*stream\s*\)\s*;", text)

@@ -1,50 +1,27 @@
 """Mesh rasterisation without a device: the C layout of ovg_render_mesh_params against the ctypes mirror, every ValueError of
 postprocess.render_mesh, and self-checks of tests/raster_twin.py (the oracle of tests/test_gpu_raster.py) on the analytic sphere
 meshes of tsdf_twin and on hand-made quads."""
-import ctypes
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import raster_twin as twin
 import tsdf_twin
 from omnivggt_official_amd import lib as L
 from omnivggt_official_amd import postprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "omnivggt_hip.h")
 F = np.float32
 
 
 def test_params_layout_matches_c():
     """sizeof and every field offset of ovg_render_mesh_params as gcc sees the header == the ctypes mirror; the enums too."""
-    fields = [name for name, _ in L.RenderMeshParams._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %zu\\n", sizeof(ovg_render_mesh_params));\n'
-    for name in fields:
-        src += 'printf("%s %%zu\\n", offsetof(ovg_render_mesh_params, %s));\n' % (name, name)
-    for name in ("OVG_MESH_SHADE_COLOR", "OVG_MESH_SHADE_HEADLIGHT", "OVG_MESH_SHADE_NORMAL", "OVG_MESH_CULL_NONE", "OVG_MESH_CULL_BACK",
-                 "OVG_MESH_CULL_FRONT"):
-        src += 'printf("%s %%d\\n", (int)%s);\n' % (name, name)
-    src += "return 0;}\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        with open(c, "w") as fh:
-            fh.write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = dict(line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines())
-    assert int(out["sizeof"]) == ctypes.sizeof(L.RenderMeshParams)
-    for name in fields:
-        assert int(out[name]) == getattr(L.RenderMeshParams, name).offset, name
-    assert [int(out["OVG_MESH_SHADE_" + k]) for k in ("COLOR", "HEADLIGHT", "NORMAL")] == \
-        [L.MESH_SHADE_COLOR, L.MESH_SHADE_HEADLIGHT, L.MESH_SHADE_NORMAL] == [twin.SHADE_COLOR, twin.SHADE_HEADLIGHT, twin.SHADE_NORMAL]
-    assert [int(out["OVG_MESH_CULL_" + k]) for k in ("NONE", "BACK", "FRONT")] == \
-        [L.MESH_CULL_NONE, L.MESH_CULL_BACK, L.MESH_CULL_FRONT] == [twin.CULL_NONE, twin.CULL_BACK, twin.CULL_FRONT]
+    enums, _ = abi_layout.check({"ovg_render_mesh_params": L.RenderMeshParams},
+                                ["OVG_MESH_SHADE_COLOR", "OVG_MESH_SHADE_HEADLIGHT", "OVG_MESH_SHADE_NORMAL", "OVG_MESH_CULL_NONE",
+                                 "OVG_MESH_CULL_BACK", "OVG_MESH_CULL_FRONT"])
+    assert enums[:3] == [L.MESH_SHADE_COLOR, L.MESH_SHADE_HEADLIGHT, L.MESH_SHADE_NORMAL] == [twin.SHADE_COLOR, twin.SHADE_HEADLIGHT, twin.SHADE_NORMAL]
+    assert enums[3:] == [L.MESH_CULL_NONE, L.MESH_CULL_BACK, L.MESH_CULL_FRONT] == [twin.CULL_NONE, twin.CULL_BACK, twin.CULL_FRONT]
     assert postprocess.MESH_SHADINGS == {"color": L.MESH_SHADE_COLOR, "headlight": L.MESH_SHADE_HEADLIGHT, "normal": L.MESH_SHADE_NORMAL}
     assert postprocess.MESH_CULLS == {None: L.MESH_CULL_NONE, "back": L.MESH_CULL_BACK, "front": L.MESH_CULL_FRONT}
     for name in ("ovg_render_mesh", "ovg_render_mesh_workspace_bytes"):

@@ -4,13 +4,12 @@ any HIP call), orbit_cameras, write_png and the Python API's argument checks."""
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_layout
 import common
 import render_twin as twin
 from omnivggt_official_amd import lib as L
@@ -123,23 +122,8 @@ def test_twin_views_are_independent_and_radius_grows_the_splat():
 
 
 def test_ctypes_struct_layout_matches_c_render():
-    fields = [n for n, _ in L.RenderParams._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %zu\\n", sizeof(ovg_render_params));\n'
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(ovg_render_params, %s));\n' % (n, n)
-    src += 'printf("enums %d %d %d\\n", OVG_RENDER_MAX_RADIUS, OVG_RENDER_NO_PREREAD, OVG_ABI_VERSION);\nreturn 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(L.RenderParams)
-    for n in fields:
-        assert int(got[n][0]) == getattr(L.RenderParams, n).offset, n
-    assert [int(v) for v in got["enums"]] == [L.RENDER_MAX_RADIUS, L.RENDER_NO_PREREAD, L.ABI_VERSION]
+    enums, _ = abi_layout.check({"ovg_render_params": L.RenderParams}, ["OVG_RENDER_MAX_RADIUS", "OVG_RENDER_NO_PREREAD", "OVG_ABI_VERSION"])
+    assert enums == [L.RENDER_MAX_RADIUS, L.RENDER_NO_PREREAD, L.ABI_VERSION]
     assert L.ABI_VERSION == 13
     text = open(HEADER).read()
     assert re.search(r"int64_t\s+ovg_render_workspace_bytes\s*\(\s*int32_t\s+V,\s*int32_t\s+H,\s*int32_t\s+W\s*\)\s*;", text)

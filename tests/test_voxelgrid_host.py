@@ -2,21 +2,17 @@
 layout, argument checks that return before any HIP call), the Python API's argument checks, and the camera frusta of write_glb."""
 import ctypes
 import json
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
-import common
+import abi_layout
 import voxelgrid_twin as twin
 from omnivggt_official_amd import lib as L
 from omnivggt_official_amd import postprocess
 
-HEADER = os.path.join(common.ROOT, "include", "omnivggt_hip.h")
 F = np.float32
 
 
@@ -93,23 +89,9 @@ def test_twin_properties_on_a_random_cloud():
 
 
 def test_ctypes_struct_layout_matches_c_voxelgrid():
-    fields = [n for n, _ in L.VoxelDownsampleParams._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){\n' % HEADER
-    src += 'printf("sizeof %zu\\n", sizeof(ovg_voxel_downsample_params));\n'
-    for n in fields:
-        src += 'printf("%s %%zu\\n", offsetof(ovg_voxel_downsample_params, %s));\n' % (n, n)
-    src += 'printf("enums %d %d %d %d %d\\n", OVG_VG_COUNT, OVG_VG_SCATTER, OVG_VG_OVERFLOW, OVG_VG_BAD_VOXEL, OVG_ABI_VERSION);\nreturn 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-std=c99", c, "-o", exe])
-        out = [line.split() for line in subprocess.check_output([exe]).decode().strip().splitlines()]
-    got = {k[0]: k[1:] for k in out}
-    assert int(got["sizeof"][0]) == ctypes.sizeof(L.VoxelDownsampleParams)
-    for n in fields:
-        assert int(got[n][0]) == getattr(L.VoxelDownsampleParams, n).offset, n
-    assert [int(v) for v in got["enums"]] == [L.VG_COUNT, L.VG_SCATTER, L.VG_OVERFLOW, L.VG_BAD_VOXEL, L.ABI_VERSION]
+    enums, _ = abi_layout.check({"ovg_voxel_downsample_params": L.VoxelDownsampleParams},
+                                ["OVG_VG_COUNT", "OVG_VG_SCATTER", "OVG_VG_OVERFLOW", "OVG_VG_BAD_VOXEL", "OVG_ABI_VERSION"])
+    assert enums == [L.VG_COUNT, L.VG_SCATTER, L.VG_OVERFLOW, L.VG_BAD_VOXEL, L.ABI_VERSION]
 
 
 def test_voxelgrid_argument_validation_without_gpu():
