@@ -116,6 +116,14 @@ const char* ovg_build_info(void);
  * vision_transformer.py:264 final DINO norm).  x is the f32 residual
  * stream with row stride ldx (elements); y is [rows,1024] in `dtype`
  * (out_f32 != 0: y is f32 regardless of dtype).
+ *
+ * Size limits of the model-path entries (this one to ovg_unproject, and ovg_camera_head): every byte offset a kernel forms from a row,
+ * pixel, head or image index and a stride is 64-bit unless the entry's "Size limits" paragraph says otherwise, and what it says otherwise
+ * is checked on the host: a call beyond it is refused (or, where stated, served by another kernel), never wrapped. Counts are int64_t in
+ * the structs; a kernel that holds one as an int says so below. The limits that remain are memory, not arithmetic
+ * (tests/test_gpu_address_range.py runs every strided operand 16 MiB per row apart and the dense ones past 4 GiB / 2^31 elements).
+ * Size limits: none beyond rows > 0 (ldx, ldy multiples of 4 elements, 16-byte aligned pointers); the grid is capped at 8192 blocks of
+ * four rows and strides over the rest.
  * ------------------------------------------------------------------ */
 typedef struct {
   const float* x; int64_t ldx;
@@ -138,6 +146,12 @@ int ovg_layernorm(const ovg_layernorm_params*, void* stream);
  *                    omnivggt_aggregator.py:284-301 camera injection)
  *   OVG_EPI_PATCH : y_f32[(m/p0)*p1 + off + m%p0, n] = acc + bias + table[(m%p0)+1, n]
  *                   (patch_embed.py:75-77 + vision_transformer.py:220-224)
+ * Size limits (each a host check; OVG_E_ARG unless noted): 0 < M <= 2^30 rows; N a multiple of 128, K of 64; ldx, ldw multiples of 16
+ * bytes, ldy / ldres of 4 elements. The epilogues divide the row index by p0 (PATCH) and inj_period (RES with inject) with a corrected
+ * float estimate that is exact while the quotient stays below 2^22: (M - 1) / p0 and (M - 1) / inj_period must, and both periods must
+ * be below 2^31. The 256 x 256 tile addresses the rows of a tile as 32-bit byte offsets from the tile's first row: it needs
+ * 0 <= ldx, ldw <= 8 421 504 elements (255 ld 2 + 64 <= 2^32; 16.06 MiB per row). Beyond that OVG_TILE_AUTO runs the 128 x 128 tile
+ * (64-bit row pointers, any stride) and a forced OVG_TILE_256 is OVG_E_UNSUPPORTED. y, res and the 128 x 128 tile's x / w take any stride.
  * ------------------------------------------------------------------ */
 enum { OVG_EPI_STORE = 0, OVG_EPI_GELU = 1, OVG_EPI_RES = 2, OVG_EPI_PATCH = 3 };
 /* workgroup tile of the GEMM kernels: 128 x 128 (4 waves, register-staged, up to 3 workgroups per CU) or 256 x 256 (8 waves, 4-slot LDS-DMA
@@ -181,6 +195,11 @@ int ovg_linear(const ovg_linear_params*, void* stream);
  * of one lane group of the PV MFMA, so the attention kernels move K / V^T tiles global -> LDS by LDS-DMA (no register pass)
  * and read a fragment with one ds_read_b128. ovg_qkv writes this order and ovg_flash_attn expects it; the permutation is
  * local to 32-key blocks, so slicing / exchanging vt buffers at 64-key granularity (segments, ranks, heads) is unaffected.
+ * Size limits (host checks, OVG_E_ARG unless noted): 0 < M <= 2^30 rows, M % seq == 0; (M - 1) / seq and, with rope,
+ * (M - 1) / tokens_per_view below 2^22 and tokens_per_view below 2^31 (the epilogue's row-index divisions, as in ovg_linear);
+ * nq_pad, nk_pad >= seq, nk_pad % 64 == 0; max_pos <= 128. x takes a row stride: the 128 x 128 tile any, the 256 x 256 tile
+ * 0 <= ldx <= 8 421 504 elements (AUTO falls back to 128 beyond, a forced OVG_TILE_256 is OVG_E_UNSUPPORTED); w, q, k, vt are dense,
+ * their offsets 64-bit (BH n_pad 64 elements may pass 2^31).
  * ------------------------------------------------------------------ */
 typedef struct {
   const void* x; int64_t ldx;       /* [M,1024] dtype */
@@ -209,6 +228,10 @@ int ovg_qkv(const ovg_qkv_params*, void* stream);
  *   q   [BH, nq_pad, 64]
  *   seg[i].k [BH, nk_pad_i, 64], seg[i].vt [BH, 64, nk_pad_i] (16-bit: columns in the ovg_qkv order above), nk_i valid keys
  *   out [B*nq, H*64] token-major (row = (bh/H)*nq + n, col = (bh%H)*64 + d), ld = ldo
+ * Size limits (host checks, OVG_E_ARG): the kernels hold query rows, keys and key tiles as ints and decode (entry, q tile, key range)
+ * from an int block index: 0 < nq < 2^27, every 0 < nk < 2^27, BH <= 2^27 and BH * ceil(nq / 64) <= 2^27 (a launch cut into
+ * OVG_MAX_SEG key ranges then has at most 2^30 workgroups); nk_pad % 64 == 0, ldo % 4 == 0. Every byte offset into q, k, vt, out, lse
+ * and the split workspace is 64-bit: BH nq_pad 128 B and ldo may pass 4 GiB.
  * ------------------------------------------------------------------ */
 typedef struct { const void* k; const void* vt; int64_t nk; int64_t nk_pad;
                  const void* k_lo; const void* vt_lo;   /* OVG_F16X2: lo planes of k / vt (same shapes) */
@@ -291,7 +314,9 @@ int ovg_attn_plan(const ovg_attn_params*, ovg_attn_plan_out* out);
 /* Combine two attention results over disjoint key sets (same queries):
  *   w_a = 2^(lse_a - m), w_b = 2^(lse_b - m), m = max(lse_a, lse_b);  out = (w_a * a + w_b * b) / (w_a + w_b)
  * a, b, out: [rows, 1024] `dtype` token-major (row strides lda / ldb / ldo; out may alias a or b);
- * lse_a, lse_b: f32 [16, n_pad] head-major as written by ovg_flash_attn (row = token n, B = 1). */
+ * lse_a, lse_b: f32 [16, n_pad] head-major as written by ovg_flash_attn (row = token n, B = 1).
+ * Size limits: 0 < rows <= n_pad; lda, ldb, ldo >= 1024 and multiples of 4 elements, otherwise any (64-bit offsets; the grid is capped
+ * at 2^16 blocks and strides over the rest). */
 typedef struct {
   const void* a; int64_t lda; const float* lse_a;
   const void* b; int64_t ldb; const float* lse_b;
@@ -307,6 +332,11 @@ int ovg_attn_merge(const ovg_attn_merge_params*, void* stream);
  * run as LN -> QKV -> flash-attn -> proj(RES) -> LN -> fc1(GELU) -> fc2(RES [+inject]).
  * x_in/x_out are f32 with row strides (x_out may alias x_in; they may also be
  * the two halves of a (.., 2C) concat buffer, omnivggt_aggregator.py:250).
+ * Size limits: those of the entries it sequences, all checked before the first launch (OVG_E_ARG): 0 < M <= 2^30, M % seq == 0,
+ * BH == (M / seq) 16, (M - 1) / seq < 2^22 (with rope also (M - 1) / tokens_per_view, and 0 < tokens_per_view < 2^31), seq < 2^27,
+ * every extra segment's nk < 2^27, BH * ceil(seq / 64) <= 2^27, nq_pad / nk_pad as ovg_qkv. ld_in and ld_out take
+ * any multiple of 4 elements; the workspace tensors are dense and may pass 2 GiB / 2^31 elements (ws_hid does from 262 145 tokens in
+ * the 16-bit modes, 131 073 in f32).
  * ------------------------------------------------------------------ */
 typedef struct {
   const void* n1_w; const void* n1_b;     /* f32 [1024] */
@@ -370,7 +400,8 @@ int ovg_block_workspace_bytes(const ovg_block_params*, ovg_block_workspace* out)
 
 /* Weight pre-pack (inference.py:321-325 loads f32 checkpoints): dst[r, :k] = convert(src[r, :k]) to `dtype`,
  * dst[r, k:k_pad] = 0.  src f32 [rows, k] (ld lds), dst `dtype` [rows, k_pad] (ld ldd, k_pad % 8 == 0).
- * nn.Linear weights pack with k_pad = k; the Conv2d(k=14,s=14) patch weights with k = C_in*196, k_pad = 640 / 448. */
+ * nn.Linear weights pack with k_pad = k; the Conv2d(k=14,s=14) patch weights with k = C_in*196, k_pad = 640 / 448.
+ * Size limits: rows, k > 0, k <= k_pad < 2^34 (k_pad / 8 is held as an int), lds >= k, ldd >= k_pad; offsets 64-bit, any stride. */
 typedef struct {
   const float* src; int64_t lds; void* dst; int64_t ldd;
   int64_t rows; int64_t k; int64_t k_pad; int dtype;
@@ -384,6 +415,8 @@ int ovg_pack_weights(const ovg_pack_weights_params*, void* stream);
  * zero for k >= C*196.  mode 0: (img[c]-mean[c])/std[c]  (omnivggt_aggregator.py:143)
  * mode 1: depth/mask: c=0 -> depth/(mean_b+1e-8)*mask, c=1 -> mask
  *         (omnivggt_aggregator.py:107-128,197); depth_stats = {sum,count} per batch
+ * Size limits: V > 0, Hpx, Wpx multiples of 14 (ints: one image below 2^31 pixels), C * 196 <= k_pad < 2^34, k_pad % 64 == 0; img and
+ * out are dense, their offsets 64-bit (out passes 4 GiB from 3.4 million patches on); the grid is capped at 2^16 blocks.
  * ------------------------------------------------------------------ */
 typedef struct {
   const float* img; const float* img2;   /* mode1: img=depth [V,H,W], img2=mask [V,H,W] */
@@ -397,14 +430,17 @@ typedef struct {
 int ovg_im2col(const ovg_im2col_params*, void* stream);
 
 /* masked depth statistics (omnivggt_aggregator.py:118-123): stats[b] = {sum of
- * depth where mask>0, count}.  partial: workspace of 2*nblocks doubles. */
+ * depth where mask>0, count}.  partial: workspace of 2*nblocks doubles.
+ * Size limits: B, n_per_batch, nblocks > 0 (B and nblocks are grid extents); offsets 64-bit. */
 typedef struct {
   const float* depth; const float* mask; int64_t B; int64_t n_per_batch;
   double* stats; double* partial; int nblocks;
 } ovg_depth_stats_params;
 int ovg_depth_stats(const ovg_depth_stats_params*, void* stream);
 
-/* DINOv2 special rows (vision_transformer.py:220-224): x[v,0]=cls+pos[0], x[v,1..4]=reg */
+/* DINOv2 special rows (vision_transformer.py:220-224): x[v,0]=cls+pos[0], x[v,1..4]=reg
+ * Size limits: V > 0, n_reg >= 0, ldx a multiple of 4 elements, otherwise any (64-bit offsets); one block per special row with an int
+ * block index: V * (1 + n_reg) <= 2^31 - 1, else OVG_E_UNSUPPORTED (answered before the pointers are checked). */
 typedef struct {
   float* x; int64_t ldx; int64_t V; int64_t tokens_per_view;
   const float* cls; const float* pos0; const float* reg; int n_reg;
@@ -416,7 +452,10 @@ int ovg_dino_specials(const ovg_dino_specials_params*, void* stream);
  *   t == 0     : camera_token[slot] + cam_add[v]
  *   1 <= t < 5 : register_token[slot][t-1]
  *   t >= 5     : LayerNorm_eps(xd[v,t]) + (depth_row[v] >= 0 ? depth_tok[depth_row[v]*P0+t-5] : placeholder)
- * slot = ((view0 + v) % S == 0) ? 0 : 1   (aggregator.py:343-366). */
+ * slot = ((view0 + v) % S == 0) ? 0 : 1   (aggregator.py:343-366).
+ * Size limits: V, S > 0, tokens_per_view > n_special, ldxd / ldo multiples of 4 elements, otherwise any (64-bit offsets; the grid is
+ * capped at 8192 blocks of four rows); the kernel holds a token index as an int: tokens_per_view >= 2^31 is OVG_E_UNSUPPORTED
+ * (answered before the pointers are checked). */
 typedef struct {
   const float* xd; int64_t ldxd;        /* DINO residual stream [V*P,1024] */
   const float* norm_w; const float* norm_b; float eps;
@@ -432,7 +471,8 @@ typedef struct {
 } ovg_assemble_params;
 int ovg_assemble_tokens(const ovg_assemble_params*, void* stream);
 
-/* strided f32 row copy/add helper: y[r, :n] = x[r, :n] (+ add[r / period, :n] on rows r%period==0) */
+/* strided f32 row copy/add helper: y[r, :n] = x[r, :n] (+ add[r / period, :n] on rows r%period==0)
+ * Size limits: rows, n > 0, n, ldx, ldy multiples of 4 elements, otherwise any (64-bit offsets; 8192 blocks stride over the rows). */
 typedef struct {
   const float* x; int64_t ldx; float* y; int64_t ldy; int64_t rows; int64_t n;
 } ovg_copy_rows_params;
@@ -447,7 +487,9 @@ int ovg_copy_rows(const ovg_copy_rows_params*, void* stream);
 
 /* LayerNorm over rows of 2048 of the aggregator output list (dpt_head.py:219 `self.norm`):
  * input row of output row r is x + ((r / p0) * p1 + row_off + r % p0) * ldx  (p0 patch tokens kept
- * per view out of p1 tokens per view, skipping the row_off special tokens); y is [rows, 2048] dtype. */
+ * per view out of p1 tokens per view, skipping the row_off special tokens); y is [rows, 2048] dtype.
+ * Size limits: rows > 0, 0 < p0 <= p1, row_off >= 0, ldx / ldy multiples of 4 elements, otherwise any (64-bit offsets and row arithmetic;
+ * 2^16 blocks of four rows stride over the rest: a second trip from 262 145 rows on). */
 typedef struct {
   const float* x; int64_t ldx;
   void* y; int64_t ldy;
@@ -473,7 +515,12 @@ int ovg_head_layernorm(const ovg_head_layernorm_params*, void* stream);
  *         is stored at y[i, oy*s+dy, ox*s+dx, co].  pos / add are not supported together with upshuffle.
  *   out_f32 != 0: y is f32.
  * Constraints: Cin % 64 == 0 (OVG_F32: % 32); w holds w_rows rows (a multiple of 128, zero rows beyond the Cout_gemm real ones,
- * Cout_gemm = Cout, or s*s*Cout with upshuffle: then it must itself be the multiple of 128); Cout % 4 == 0. */
+ * Cout_gemm = Cout, or s*s*Cout with upshuffle: then it must itself be the multiple of 128); Cout % 4 == 0.
+ * Size limits: at most 2^30 output pixels (n_img OH OW; OVG_E_ARG beyond); ldx >= Cin, ldy >= Cout, ld1 / ld2 / ldy multiples of 4 elements
+ * (ldx of 8; OVG_F32: 4), otherwise any: the 128-pixel kernel forms every offset in 64 bits. The 256-pixel LDS-DMA kernels (16-bit dtypes,
+ * 16-bit output, >= 16384 output pixels) address the images of a tile through one buffer descriptor with 32-bit offsets; they are chosen
+ * only while (255 / (OH OW) + 2) H W ldx 2 bytes -- the images 256 consecutive output pixels can touch: two from 256-pixel maps on --
+ * stay below 2^32 - 65536 and the weight matrix below 2^32 bytes; any other call runs the 128-pixel kernel. y, add1, add2 are 64-bit in both. */
 typedef struct {
   const void* x; int64_t ldx;
   const void* w; const float* bias;
@@ -488,7 +535,9 @@ int ovg_conv(const ovg_conv_params*, void* stream);
 /* Bilinear resize, align_corners = True (F.interpolate at dpt_head.py:242-247, :466), NHWC, C % 8 == 0:
  * y[i, oy, ox, :] = lerp of x[i, :, :, :] at (oy*(H-1)/(OH-1), ox*(W-1)/(OW-1)), plus the optional UV
  * position embedding (pos_x [OW, C/2], pos_y [OH, C/2], dpt_head.py:249-250) -- both in `dtype`.
- * OH == 1 / OW == 1 (one-row / one-column patch grids) take source row / column 0, like ATen. */
+ * OH == 1 / OW == 1 (one-row / one-column patch grids) take source row / column 0, like ATen.
+ * Size limits: H, W, OH, OW are ints; ldx, ldy >= C and multiples of 8 elements, otherwise any. Every offset is 64-bit; 2^20 blocks of
+ * 256 (pixel, 8-channel) items stride over the rest (a second trip from 2^28 items on). */
 typedef struct {
   const void* x; int64_t ldx; void* y; int64_t ldy;
   const float* pos_x; const float* pos_y;
@@ -501,7 +550,8 @@ int ovg_upsample(const ovg_upsample_params*, void* stream);
  * ovg_conv (k = 3, Cout = 32, relu, out_f32) produced; f32 in, f32 out:
  *   activation 0 = "exp" (depth head, out_dim 2: val = exp(v0)), 1 = "inv_log" (point head, out_dim 4:
  *   val_j = sign(v_j) * expm1(|v_j|), j < 3); confidence = 1 + exp(v_last) ("expp1") in both.
- *   h [npix, 32] f32;  w2 [out_dim, 32] f32, b2 [out_dim] f32;  val [npix, out_dim-1] f32;  conf [npix] f32 */
+ *   h [npix, 32] f32;  w2 [out_dim, 32] f32, b2 [out_dim] f32;  val [npix, out_dim-1] f32;  conf [npix] f32
+ * Size limits: npix > 0 (int64, 64-bit offsets; 2^20 blocks of 256 pixels stride over the rest). */
 typedef struct {
   const float* h; const float* w2; const float* b2;
   float* val; float* conf;
@@ -516,7 +566,10 @@ int ovg_dpt_out(const ovg_dpt_out_params*, void* stream);
  *   both or neither), rounded to dtype as ovg_upsample does;  w1 [>= 32 rows, 9 * 128] dtype taps-major (row stride ldw1 elements: the
  *   zero-padded matrix ovg_conv takes is fine), b1 f32 [32] or NULL;  w2 f32 [out_dim, 32], b2 f32 [out_dim];
  *   val f32 [n, OH, OW, out_dim - 1], conf f32 [n, OH, OW]; activation as ovg_dpt_out_params.
- * Any other channel count / dtype is OVG_E_UNSUPPORTED (callers run the three-launch form). */
+ * Any other channel count / dtype is OVG_E_UNSUPPORTED (callers run the three-launch form).
+ * Size limits: the kernel indexes ONE source image with 32-bit element offsets: H W ldx < 2^31 elements, else OVG_E_UNSUPPORTED (the
+ * three-launch form takes it); the image index times H W ldx is 64-bit, so n images may pass 4 GiB. OH, OW >= 2; at most 2^30 output
+ * tiles of 16 x 14 pixels (OVG_E_ARG); ldx a multiple of 8 elements, ldw1 >= 1152. val / conf are dense, their offsets 64-bit. */
 typedef struct {
   const void* x; int64_t ldx;
   const float* pos_x; const float* pos_y;
@@ -537,6 +590,7 @@ int ovg_dpt_tail(const ovg_dpt_tail_params*, void* stream);
  *   x_cam = (u - cu) * d / fu, y_cam = (v - cv) * d / fv evaluated in double and rounded to f32 exactly like
  *   the numpy expression (int64 pixel grid promotes it to float64), then world = R * cam + t in double (the
  *   reference's inverse pose is float64) rounded to f32 on store (the reference returns float64).
+ * Size limits: S, H, W > 0 (H, W ints); the pixel index S H W and every offset are 64-bit; 2^20 blocks of 256 pixels stride over the rest.
  * ------------------------------------------------------------------ */
 typedef struct {
   const float* depth; const float* cam; float* out;
@@ -1812,6 +1866,8 @@ int ovg_heads_to_tokens(const ovg_heads_to_tokens_params*, void* stream);
  *   attn [S][2048]  dtype  attention output, token-major
  *   hid  [S][8192]  dtype  GELU(fc1) of the block
  * After the call the buffers hold the values of the last round's last block; nothing outside these ranges is written.
+ * Size limits: 0 < S <= 4096 (OVG_E_UNSUPPORTED beyond), iters > 0; ld_tokens >= 2048 and a multiple of 4 elements, otherwise any: the
+ * tokens are read once, by the token LayerNorm, through a 64-bit row offset. Every workspace offset is 64-bit (and below 2^31 at S = 4096).
  * ------------------------------------------------------------------ */
 #define OVG_CAMERA_MAX_TRUNK 4
 typedef struct {

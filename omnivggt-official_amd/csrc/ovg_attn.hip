@@ -628,10 +628,13 @@ int dispatch_x3(const ovg_attn_params& p, hipStream_t st) {
 extern "C" int ovg_flash_attn(const ovg_attn_params* p, void* stream) {
   if (!p || !p->q || !p->out) return OVG_E_ARG;
   if (p->nq <= 0 || p->nq_pad < p->nq || p->BH <= 0 || p->nseg < 1 || p->nseg > OVG_MAX_SEG) return OVG_E_ARG;
-  if (p->BH * ((p->nq + 63) / 64) > (int64_t)1 << 30) return OVG_E_ARG;
+  // the kernels hold q rows, keys and key tiles as ints and decode (entry, q tile, key range) from an int block id; byte offsets are 64-bit.
+  // nq and every nk below 2^27 (2^21 key tiles per segment, 2^24 over eight segments); at most 2^27 (entry, 64-row tile) units, so that a
+  // launch cut into OVG_MAX_SEG key ranges still has fewer than 2^31 workgroups (BH is then below 2^27 as well)
+  if (p->nq >= ((int64_t)1 << 27) || p->BH > ((int64_t)1 << 27) || p->BH * ((p->nq + 63) / 64) > (int64_t)1 << 27) return OVG_E_ARG;
   for (int i = 0; i < p->nseg; ++i) {
     const ovg_kv_segment& s = p->seg[i];
-    if (!s.k || !s.vt || s.nk <= 0 || s.nk_pad % BC != 0 || s.nk_pad < ((s.nk + BC - 1) / BC) * BC) return OVG_E_ARG;
+    if (!s.k || !s.vt || s.nk <= 0 || s.nk >= ((int64_t)1 << 27) || s.nk_pad % BC != 0 || s.nk_pad < ((s.nk + BC - 1) / BC) * BC) return OVG_E_ARG;
     if ((reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.vt)) & 15) return OVG_E_ARG;
   }
   if ((reinterpret_cast<uintptr_t>(p->q) | reinterpret_cast<uintptr_t>(p->out)) & 15) return OVG_E_ARG;

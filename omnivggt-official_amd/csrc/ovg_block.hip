@@ -10,8 +10,12 @@ namespace {
 // with_extra: the entry runs the attention step, so extra[0 .. nseg_extra) must be filled in (the prologue runs before the caller has them)
 int check_block(const ovg_block_params* p, bool with_extra) {
   if (!p || !p->x_in || !p->x_out || !p->ws_xn || !p->ws_q || !p->ws_k || !p->ws_vt || !p->ws_attn || !p->ws_hid) return OVG_E_ARG;
-  if (p->M <= 0 || p->seq <= 0 || p->M % p->seq || p->BH != (p->M / p->seq) * OVG_H) return OVG_E_ARG;
+  if (p->M <= 0 || p->M > (1 << 30) || p->seq <= 0 || p->M % p->seq || p->BH != (p->M / p->seq) * OVG_H) return OVG_E_ARG;
   // what ovg_block_workspace_bytes refuses, refused here: the inner entries check the same, but ovg_qkv only after LN1 has been launched
+  // (its row-count limits -- M <= 2^30, (M - 1) / seq and, with RoPE, (M - 1) / tokens_per_view below 2^22, tokens_per_view an int -- and
+  // ovg_flash_attn's -- seq < 2^27, at most 2^27 (entry, 64-row tile) units -- likewise)
+  if ((p->M - 1) / p->seq >= ((int64_t)1 << 22) || p->seq >= ((int64_t)1 << 27) || p->BH * ((p->seq + 63) / 64) > ((int64_t)1 << 27)) return OVG_E_ARG;
+  if (p->rope && (p->tokens_per_view <= 0 || p->tokens_per_view >= ((int64_t)1 << 31) || (p->M - 1) / p->tokens_per_view >= ((int64_t)1 << 22))) return OVG_E_ARG;
   if (p->nq_pad < p->seq || p->nk_pad < p->seq || p->nk_pad % OVG_KV_TILE) return OVG_E_ARG;
   if (p->dtype != OVG_BF16 && p->dtype != OVG_F16 && p->dtype != OVG_F32 && p->dtype != OVG_F16X2) return OVG_E_DTYPE;
   if (p->nseg_extra < 0 || p->nseg_extra >= OVG_MAX_SEG) return OVG_E_ARG;
@@ -23,7 +27,7 @@ int check_block(const ovg_block_params* p, bool with_extra) {
   if (with_extra && !p->skip_attention)      // ovg_flash_attn's segment checks, before the launches that precede it in ovg_block_forward
     for (int i = 0; i < p->nseg_extra; ++i) {
       const ovg_kv_segment& s = p->extra[i];
-      if (!s.k || !s.vt || s.nk <= 0 || s.nk_pad < s.nk || s.nk_pad % OVG_KV_TILE) return OVG_E_ARG;
+      if (!s.k || !s.vt || s.nk <= 0 || s.nk >= ((int64_t)1 << 27) || s.nk_pad < s.nk || s.nk_pad % OVG_KV_TILE) return OVG_E_ARG;
       if (p->dtype == OVG_F16X2 && (!s.k_lo || !s.vt_lo)) return OVG_E_ARG;
     }
   return OVG_OK;

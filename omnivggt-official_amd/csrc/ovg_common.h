@@ -116,7 +116,8 @@ OVG_DEV int vt_pos16(int n) {
   return (n & ~31) | ((k & 12) << 1) | ((k & 16) >> 2) | (k & 3);
 }
 
-// x / d and x % d for 0 <= x < 2^24, 1 <= d: one v_rcp_f32 per divisor (hoisted by the caller), then ~8 VALU per
+// x / d and x % d for 0 <= x < 2^31, 1 <= d, x / d < 2^22 (the float estimate is within (x / d) 2^-22 of the quotient, so one correction
+// step either way suffices; ovg_linear / ovg_qkv refuse calls beyond it: fastdiv_ok in ovg_gemm.hip): one v_rcp_f32 per divisor (hoisted by the caller), then ~8 VALU per
 // division instead of the ~30 of the generic 32-bit sequence hipcc expands (the epilogues divide token indices by the
 // sequence length / tokens per view / patch-grid width once per 16-row block: r02 profile of the QKV kernel showed
 // 790 v_mul_lo_u32 + 730 v_cndmask_b32 of division code against 256 MFMAs).

@@ -64,7 +64,8 @@ OVG_DEV void mainloop(const ovg_conv_params& p, const int M, const int OH, const
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
 
   // descriptors: weights (whole padded matrix); activations from the first image this tile touches to the end of the tensor (< 4 GB:
-  // the host sends a shape here only when two images fit 32-bit offsets -- a 256-pixel tile spans at most two)
+  // the host sends a shape here only when every image a 256-pixel tile can touch -- 255 / (OH OW) + 2 of them, two for maps of 256 pixels
+  // and more -- fits 32-bit offsets: ovg_conv in ovg_head.hip)
   const i32x4 srd_w = make_srd(p.w, (uint32_t)p.w_rows * (uint32_t)ktot_b);
   const int img0 = m0 / (OH * OW);
   const int64_t img_b = (int64_t)p.H * p.W * pix_b;

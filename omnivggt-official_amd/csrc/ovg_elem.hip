@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(ovg_pack_weights_para
 
 extern "C" int ovg_pack_weights(const ovg_pack_weights_params* p, void* stream) {
   if (!p || !p->src || !p->dst || p->rows <= 0 || p->k <= 0 || p->k_pad < p->k || (p->k_pad % 8) || p->lds < p->k || p->ldd < p->k_pad) return OVG_E_ARG;
-  if (!al16(p->dst) || (p->ldd % 8)) return OVG_E_ARG;
+  if (!al16(p->dst) || (p->ldd % 8) || p->k_pad >= ((int64_t)1 << 34)) return OVG_E_ARG;   // k_pad / 8 is an int in the kernel
   const int cpr = (int)(p->k_pad / 8);
   const int64_t total = p->rows * cpr;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -360,7 +360,7 @@ extern "C" int ovg_layernorm(const ovg_layernorm_params* p, void* stream) {
 
 extern "C" int ovg_im2col(const ovg_im2col_params* p, void* stream) {
   if (!p || !p->img || !p->out || p->V <= 0) return OVG_E_ARG;
-  if (p->Hpx % 14 || p->Wpx % 14 || p->k_pad % 64 || p->k_pad < p->C * 196) return OVG_E_ARG;
+  if (p->Hpx % 14 || p->Wpx % 14 || p->k_pad % 64 || p->k_pad < p->C * 196 || p->k_pad >= ((int64_t)1 << 34)) return OVG_E_ARG;   // k_pad / 8: an int in the kernel
   if (p->mode == 0 ? (p->C != 3) : (p->C != 2 || !p->img2 || !p->depth_stats || p->views_per_batch <= 0)) return OVG_E_ARG;
   if (!al16(p->out)) return OVG_E_ARG;
   const int gh = p->Hpx / 14, gw = p->Wpx / 14;
@@ -391,16 +391,22 @@ extern "C" int ovg_depth_stats(const ovg_depth_stats_params* p, void* stream) {
 }
 
 extern "C" int ovg_dino_specials(const ovg_dino_specials_params* p, void* stream) {
-  if (!p || !p->x || !p->cls || !p->pos0 || (p->n_reg > 0 && !p->reg) || p->V <= 0 || (p->ldx % 4)) return OVG_E_ARG;
+  if (!p || p->V <= 0 || p->n_reg < 0 || (p->ldx % 4)) return OVG_E_ARG;
+  // one block per special row, the block index an int: V (1 + n_reg) < 2^31, exactly (V <= floor((2^31 - 1) / (1 + n_reg))). A size the
+  // kernel cannot hold is OVG_E_UNSUPPORTED, answered before the pointers are looked at
+  if (p->V > (((int64_t)1 << 31) - 1) / (1 + (int64_t)p->n_reg)) return OVG_E_UNSUPPORTED;
+  if (!p->x || !p->cls || !p->pos0 || (p->n_reg > 0 && !p->reg)) return OVG_E_ARG;
   OVG_LAUNCH(dino_specials_kernel, dim3((unsigned)(p->V * (1 + p->n_reg))), dim3(256), 0, static_cast<hipStream_t>(stream), *p);
   OVG_CHECK_LAUNCH();
   return OVG_OK;
 }
 
 extern "C" int ovg_assemble_tokens(const ovg_assemble_params* p, void* stream) {
-  if (!p || !p->xd || !p->norm_w || !p->norm_b || !p->camera_token || !p->register_token || !p->cam_add || !p->placeholder || !p->out)
-    return OVG_E_ARG;
+  if (!p) return OVG_E_ARG;
   if (p->V <= 0 || p->S <= 0 || p->view0 < 0 || p->tokens_per_view <= p->n_special || (p->ldo % 4) || (p->ldxd % 4)) return OVG_E_ARG;
+  if (p->tokens_per_view >= ((int64_t)1 << 31)) return OVG_E_UNSUPPORTED;   // the kernel holds a token index as an int (answered before the pointers are looked at)
+  if (!p->xd || !p->norm_w || !p->norm_b || !p->camera_token || !p->register_token || !p->cam_add || !p->placeholder || !p->out)
+    return OVG_E_ARG;
   OVG_LAUNCH(assemble_kernel, dim3(grid_for(p->V * p->tokens_per_view, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), *p);
   OVG_CHECK_LAUNCH();
   return OVG_OK;

@@ -847,6 +847,12 @@ constexpr int TILE_GROUP = 8, TILE_GROUP256 = 4;
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The epilogues split a row index m by a period d (PATCH: p0; camera injection: inj_period; QKV: seq, tokens_per_view) with FastDiv
+// (ovg_common.h): a float estimate of m / d corrected by ONE step. The estimate is within (m / d) 2^-22 of the quotient (v_rcp_f32: 1 ulp,
+// the conversion of m and the product: half an ulp each), so the single step suffices while m / d < 2^22; the divisor is held as an int.
+// A call outside that range would address other rows: refused (OVG_E_ARG).
+bool fastdiv_ok(int64_t rows, int64_t d) { return d > 0 && d < ((int64_t)1 << 31) && (rows - 1) / d < ((int64_t)1 << 22); }
+
 // One linear launch: the 256 x 256 kernel (16-bit modes, `big`) or the 128 x 128 one
 template <typename T, int EPI, bool OUT_F32, bool X3>
 int launch_linear_one(const ovg_linear_params& p, hipStream_t st, bool big) {
@@ -888,7 +894,6 @@ int dispatch_linear(const ovg_linear_params& p, hipStream_t st, bool big) {
 // where they are worth +1 % (16 views) ... +2 % (64 views) on the forward. Re-checked in r03 with the staged-store epilogues
 // (profiles/r03_gemm_mlp256_insitu.txt): fc1 / fc2 alone on 256 x 256 below the threshold -- isolated +8 / +17 % at M = 10 992 -- still
 // LOSES in situ (4 / 8 / 12 views: -6.5 / -4 / -2.5 %; the global attention behind them 0.445 -> 0.482 ms): the threshold stays.
-// Returns 1 = use 256^2, 0 = use 128^2, -1 = the caller forced a tile this shape / dtype cannot run.
 // Short launches (round 6, profiles/r06_gemm_short_launch_tiles_insitu.txt). Below 20 000 rows the 128 x 128 kernels stay the default -- fc1 on
 // 256 x 256 tiles at 8 views is isolated +21 % and in the forward -4.8 % (the global attention behind it clocks 0.442 -> 0.480 ms) -- with two
 // exceptions where the 256 x 256 launch fits ONE round of the chip (tiles <= CUs):
@@ -905,12 +910,20 @@ int gemm_device_cus() {
   }();
   return n;
 }
-int choose_256(int tile, bool sixteen_bit, int64_t M, int64_t N, int64_t K, bool light_epilogue_or_long_k, int kind = 0) {
+// The 256 x 256 main loop (ovg_gemm256.h) addresses the rows of a tile as 32-BIT byte offsets from the tile's first row: row 255 and its last
+// 64-byte k chunk must lie below 2^32, i.e. 255 * ld * 2 + 64 <= 2^32 (ld <= 8 421 504 elements, 16.06 MiB per row). A longer (or negative)
+// leading dimension would wrap the lane offset and fetch other rows of the same tensor -- a wrong result, no fault: such calls run the
+// 128 x 128 kernels (64-bit row pointers), and a forced OVG_TILE_256 is refused.
+bool ld_fits_256(int64_t ld) { return ld >= 0 && ld <= ((((int64_t)1 << 32) - 64) / 255) / 2; }
+
+// Returns 1 = use 256^2, 0 = use 128^2, -1 = the caller forced a tile this shape / dtype cannot run (OVG_E_ARG), -2 = forced 256^2 with a
+// leading dimension beyond ld_fits_256 (OVG_E_UNSUPPORTED).
+int choose_256(int tile, bool sixteen_bit, int64_t M, int64_t N, int64_t K, bool light_epilogue_or_long_k, int kind = 0, bool ld_ok = true) {
   const bool legal = sixteen_bit && N % g256::BN2 == 0 && K % 64 == 0;
   if (tile == OVG_TILE_128) return 0;
-  if (tile == OVG_TILE_256) return legal ? 1 : -1;
+  if (tile == OVG_TILE_256) return !legal ? -1 : (ld_ok ? 1 : -2);
   if (tile != OVG_TILE_AUTO) return -1;
-  if (!legal) return 0;
+  if (!legal || !ld_ok) return 0;
   if (M >= 20000) return light_epilogue_or_long_k ? 1 : 0;
   const int64_t cus = gemm_device_cus();
   const int64_t t256 = ((M + 255) / 256) * (N / 256), t128 = ((M + 127) / 128) * (N / 128);
@@ -922,16 +935,17 @@ int choose_256(int tile, bool sixteen_bit, int64_t M, int64_t N, int64_t K, bool
 template <typename T>
 int launch_linear(const ovg_linear_params& p, hipStream_t st) {
   const int big = choose_256(p.tile, sizeof(T) == 2, p.M, p.N, p.K, p.epilogue != OVG_EPI_RES || p.K >= 2048,
-                             p.epilogue == OVG_EPI_GELU ? 1 : (p.epilogue == OVG_EPI_RES ? (p.K >= 2048 ? 2 : 3) : 0));
-  if (big < 0) return OVG_E_ARG;
+                             p.epilogue == OVG_EPI_GELU ? 1 : (p.epilogue == OVG_EPI_RES ? (p.K >= 2048 ? 2 : 3) : 0),
+                             ld_fits_256(p.ldx) && ld_fits_256(p.ldw));
+  if (big < 0) return big == -2 ? OVG_E_UNSUPPORTED : OVG_E_ARG;
   return dispatch_linear<T, false>(p, st, big != 0);
 }
 
 // split-f16 mode (OVG_F16X2): the same kernels with X3 = true on f16 planes; 256 x 256 tiles from M >= 20 000 rows on (three times the
 // main loop per epilogue: the ping-pong loop's advantage grows), register-form epilogues for the two-plane 16-bit outputs
 int launch_linear_x3(const ovg_linear_params& p, hipStream_t st) {
-  const int big = choose_256(p.tile, true, p.M, p.N, p.K, true);
-  if (big < 0) return OVG_E_ARG;
+  const int big = choose_256(p.tile, true, p.M, p.N, p.K, true, 0, ld_fits_256(p.ldx) && ld_fits_256(p.ldw));
+  if (big < 0) return big == -2 ? OVG_E_UNSUPPORTED : OVG_E_ARG;
   return dispatch_linear<f16_t, true>(p, st, big != 0);
 }
 
@@ -977,9 +991,9 @@ extern "C" int ovg_linear(const ovg_linear_params* p, void* stream) {
   if (p->bias && !aligned16(p->bias)) return OVG_E_ARG;
   if (p->epilogue == OVG_EPI_RES) {
     if (!p->res || !p->gamma || (p->ldres % 4) || (p->ldy % 4) || !aligned16(p->res) || !aligned16(p->gamma)) return OVG_E_ARG;
-    if (p->inject && (p->inj_period <= 0 || !aligned16(p->inject))) return OVG_E_ARG;
+    if (p->inject && (p->inj_period <= 0 || !aligned16(p->inject) || !fastdiv_ok(p->M, p->inj_period))) return OVG_E_ARG;
   } else if (p->epilogue == OVG_EPI_PATCH) {
-    if (!p->table || p->p0 <= 0 || p->p1 <= 0 || (p->ldy % 4) || !aligned16(p->table)) return OVG_E_ARG;
+    if (!p->table || p->p0 <= 0 || p->p1 <= 0 || (p->ldy % 4) || !aligned16(p->table) || !fastdiv_ok(p->M, p->p0)) return OVG_E_ARG;
   } else {
     const int64_t osz = p->out_f32 ? 4 : esz;
     if ((p->ldy * osz) % (4 * osz)) return OVG_E_ARG;
@@ -1002,7 +1016,7 @@ extern "C" int ovg_linear(const ovg_linear_params* p, void* stream) {
 
 extern "C" int ovg_qkv(const ovg_qkv_params* p, void* stream) {
   if (!p || !p->x || !p->w || !p->bias || !p->q || !p->k || !p->vt) return OVG_E_ARG;
-  if (p->M <= 0 || p->M > (1 << 30) || p->seq <= 0 || p->M % p->seq != 0) return OVG_E_ARG;
+  if (p->M <= 0 || p->M > (1 << 30) || p->seq <= 0 || p->M % p->seq != 0 || !fastdiv_ok(p->M, p->seq)) return OVG_E_ARG;
   if (p->nq_pad < p->seq || p->nk_pad < p->seq || p->nk_pad % OVG_KV_TILE != 0) return OVG_E_ARG;
   if (p->dtype != OVG_BF16 && p->dtype != OVG_F16 && p->dtype != OVG_F32 && p->dtype != OVG_F16X2) return OVG_E_DTYPE;
   const int64_t esz = p->dtype == OVG_F32 ? 4 : 2;
@@ -1013,7 +1027,7 @@ extern "C" int ovg_qkv(const ovg_qkv_params* p, void* stream) {
   }
   if (p->qk_norm && (!p->qn_w || !p->qn_b || !p->kn_w || !p->kn_b)) return OVG_E_ARG;
   if (p->rope) {
-    if (!p->rope_cos || !p->rope_sin || p->tokens_per_view <= 0 || p->grid_w <= 0) return OVG_E_ARG;
+    if (!p->rope_cos || !p->rope_sin || p->tokens_per_view <= 0 || p->grid_w <= 0 || !fastdiv_ok(p->M, p->tokens_per_view)) return OVG_E_ARG;
     const int64_t np = p->tokens_per_view - p->n_special;
     if (np <= 0 || (np - 1) / p->grid_w + 1 >= p->max_pos || p->grid_w >= p->max_pos) return OVG_E_ARG;
     if (p->max_pos > 128 || !aligned16(p->rope_cos) || !aligned16(p->rope_sin)) return OVG_E_ARG;   // the table is staged in 16 KB of LDS
@@ -1021,8 +1035,8 @@ extern "C" int ovg_qkv(const ovg_qkv_params* p, void* stream) {
   if (p->part < 0 || p->part > 2) return OVG_E_ARG;
   if (p->tile & OVG_TILE_R02_EPILOGUE) return OVG_E_UNSUPPORTED;   // retired A/B selectors (OVG_TILE_128X / OVG_TILE_256X)
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int big = choose_256(p->tile, p->dtype != OVG_F32, p->M, (p->part == 0 ? 3 : (p->part == 1 ? 2 : 1)) * OVG_C, OVG_C, true);
-  if (big < 0) return OVG_E_ARG;
+  const int big = choose_256(p->tile, p->dtype != OVG_F32, p->M, (p->part == 0 ? 3 : (p->part == 1 ? 2 : 1)) * OVG_C, OVG_C, true, 0, ld_fits_256(p->ldx));
+  if (big < 0) return big == -2 ? OVG_E_UNSUPPORTED : OVG_E_ARG;
   // part 0: all of q | k | v; 1: k | v; 2: q -- as a range of n tiles of the chosen width
   const int q_tiles = OVG_C / (big ? g256::BN2 : BN), all_tiles = 3 * q_tiles;
   const int nt_begin = p->part == 1 ? q_tiles : 0;

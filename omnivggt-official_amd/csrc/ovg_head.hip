@@ -390,12 +390,16 @@ extern "C" int ovg_conv(const ovg_conv_params* p, void* stream) {
   const dim3 grid((unsigned)(((M + 127) / 128) * nt)), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   // 256-pixel LDS-DMA forms (ovg_conv256.h): 16-bit, 16-bit output, every GEMM column real (w_rows == the GEMM's columns), 32-channel k-stages in
-  // pairs (the free-running loop walks two k-stages per iteration), enough pixels for at least one round of the chip, and two images within
-  // the 32-bit byte offsets of its descriptor. 256-column tiles where the columns allow, else 128-column tiles at two workgroups per CU.
-  const int64_t two_images = 2 * (int64_t)p->H * p->W * p->ldx * 2;
+  // pairs (the free-running loop walks two k-stages per iteration), enough pixels for at least one round of the chip, and every image a tile
+  // touches within the 32-bit byte offsets of its descriptor: 256 consecutive output pixels span at most 255 / (OH OW) + 2 images -- two for the
+  // model's maps (OH OW >= 256), more for tiny ones -- and tile_images H W ldx 2 bytes must stay below 2^32 - 65536 (evaluated by division: no
+  // product of caller values can overflow). 256-column tiles where the columns allow, else 128-column tiles at two workgroups per CU.
+  const int64_t tile_images = 255 / ((int64_t)OH * OW) + 2;
+  const int64_t span_elems = ((((int64_t)1 << 32) - 65536) / 2 - 1) / p->ldx / tile_images;   // H W <= this  <=>  tile_images H W ldx 2 < 2^32 - 65536
+  const bool x_fits = (int64_t)p->H * p->W <= span_elems;
   const int gemm_cols = s * s * p->Cout;
   if (p->dtype != OVG_F32 && !p->out_f32 && p->w_rows == gemm_cols && gemm_cols % 128 == 0 && p->Cin % 32 == 0 && (p->ksize * p->ksize * (p->Cin / 32)) % 2 == 0 &&
-      M >= 16384 && two_images < ((int64_t)1 << 32) - 65536 && (int64_t)p->w_rows * p->ksize * p->ksize * p->Cin * 2 < ((int64_t)1 << 32)) {
+      M >= 16384 && x_fits && (int64_t)p->w_rows * p->ksize * p->ksize * p->Cin * 2 < ((int64_t)1 << 32)) {
     // (round 6 lab, profiles/r06_heads_conv_choice_e2e_ab.txt: taking the 37^2 / 19^2 convolutions of short view counts on these kernels too -- from
     // 2048 pixels, with 128-column tiles below 200 workgroups -- changes the 8-view end-to-end time by < 0.5 %, inside the run-to-run spread)
     const bool wide = gemm_cols % 256 == 0;

@@ -76,6 +76,74 @@ def guarded(shape, dtype, device, ld=None, guard_bytes=1 << 16, fill=GUARD_BYTE,
     return view, check
 
 
+def guarded_chunked(shape, dtype, device, ld=None, guard_bytes=1 << 16, fill=GUARD_BYTE, spare_rows=0, chunk_bytes=1 << 28):
+    """guarded() for views that span several GiB (tests/test_gpu_address_range.py: a row stride of 16 MiB, 2^24 rows): the same layout, the
+    same view and the same report, but check() keeps no mask of the buffer and makes no full-size temporary -- it walks the front guard,
+    the gap behind each row (whole rows at a time, as a [rows, ld - cols] byte view) and the spare rows + back guard in steps of at most
+    `chunk_bytes` bytes each. tests/test_address_range_host.py holds it to guarded()'s report on small shapes. (The layout lines repeat
+    guarded()'s on purpose: guarded() itself is left as the existing tests pinned it.)"""
+    shape = tuple(int(s) for s in shape)
+    esz = torch.empty((), dtype=dtype).element_size()
+    cols = shape[-1]
+    ld = cols if ld is None else int(ld)
+    assert ld >= cols and guard_bytes % 16 == 0 and len(shape) >= 2 and chunk_bytes > 0
+    rows = 1
+    for s in shape[:-1]:
+        rows *= s
+    ldb, rowb = ld * esz, cols * esz
+    total = 2 * guard_bytes + (rows + spare_rows) * ldb
+    total = (total + 15) // 16 * 16
+    buf = torch.full((total,), fill, dtype=torch.uint8, device=device)
+    strides = [1, ld]
+    for s in reversed(shape[1:-1]):
+        strides.append(strides[-1] * s)
+    strides = tuple(reversed(strides[: len(shape)]))
+    typed = buf[guard_bytes:guard_bytes + (total - 2 * guard_bytes) // esz * esz].view(dtype)
+    view = typed.as_strided(shape, strides)
+    assert view.data_ptr() % 16 == 0, "the ABI wants 16-byte aligned tensors"
+
+    def pieces():
+        """(2-D byte view outside the tensor, buffer offset of its [0, 0], buffer bytes between its rows), each at most chunk_bytes."""
+        for a, b in ((0, guard_bytes), (guard_bytes + rows * ldb, total)):        # front guard; spare rows + back guard
+            for o in range(a, b, chunk_bytes):
+                yield buf[o:min(o + chunk_bytes, b)].view(1, -1), o, 0
+        gap = ldb - rowb
+        if gap > 0:
+            body = buf[guard_bytes:guard_bytes + rows * ldb].view(rows, ldb)
+            for c0 in range(rowb, ldb, chunk_bytes):                               # (one column block unless a single gap exceeds a step)
+                c1 = min(c0 + chunk_bytes, ldb)
+                step = max(1, chunk_bytes // (c1 - c0))
+                for r0 in range(0, rows, step):
+                    yield body[r0:r0 + step, c0:c1], guard_bytes + r0 * ldb + c0, ldb
+
+    fill64 = int.from_bytes(bytes([fill]) * 8, "little", signed=True)
+
+    def check(name="guard"):
+        count, first, last = 0, None, None
+        for piece, origin, pitch in pieces():
+            if piece.shape[1] % 8 == 0 and pitch % 8 == 0 and (piece.data_ptr() % 8) == 0:
+                if not bool((piece.view(torch.int64) != fill64).any()):      # eight bytes per comparison; the bytes are looked at only where a word differs
+                    continue
+            bad = piece != fill
+            n = int(bad.sum())
+            if n:
+                where = torch.nonzero(bad)
+                off = origin + where[:, 0] * pitch + where[:, 1]
+                lo, hi = int(off.min()), int(off.max())
+                count, first, last = count + n, lo if first is None else min(first, lo), hi if last is None else max(last, hi)
+        if count:
+            first, last = first - guard_bytes, last - guard_bytes
+
+            def rc(off):
+                return "byte %d (row %d, col %d)" % (off, off // (ld * esz) if off >= 0 else -1, (off % (ld * esz)) // esz if off >= 0 else -1)
+            raise GuardError("%s: %d bytes outside the %s view were written; first %s, last %s" % (name, count, shape, rc(first), rc(last)))
+        STATS["guarded_launches"] += 1
+
+    check.buffer = buf
+    check.guard_bytes = guard_bytes
+    return view, check
+
+
 # ---------------------------------------------------------------------------------------------
 # poisoned padding
 # ---------------------------------------------------------------------------------------------
@@ -158,6 +226,22 @@ def elementwise_budget(name, got, ref, mag, u_out, c, extra=None, u_acc=U_ACC, q
 
 
 MARGIN = 2.0     # over every derived constant: summation order, and the hardware exp2 / rcp / rsq approximations (about 1 ulp each, not pinned)
+
+
+# ---- ovg_unproject (csrc/ovg_head.hip unproject_kernel) ---------------------------------------------------------------------------
+# x_cam = (u - cu) d / fu and y_cam likewise are evaluated in double and rounded to f32 (one rounding each, as the numpy reference does);
+# world = R (x_cam, y_cam, d) + t is evaluated in double and rounded to f32 on store (elementwise_budget's u_out |ref|). The double
+# arithmetic contributes nothing at f32 scale, so an output is within u_out |ref| + 1 u_acc (|R| |cam|): C_UNPROJECT = MARGIN x 1 on
+# mag = |R| |cam| + |t|.
+C_UNPROJECT = 2.0 * 1
+
+
+def unproject_budget(depth, u, v, cam):
+    """depth [rows, W] float64, u [1, W] / v [rows, 1] pixel coordinates (float64), cam [16] float64 (R row-major, t, fu, fv, cu, cv), all
+    on one device -> (ref, mag) [rows, W, 3] float64 for elementwise_budget(..., U_OUT["f32"], C_UNPROJECT)."""
+    R, t = cam[:9].view(3, 3), cam[9:12]
+    pts = torch.stack([(u - cam[14]) * depth / cam[12], (v - cam[15]) * depth / cam[13], depth], -1)
+    return pts @ R.t() + t, pts.abs() @ R.abs().t() + t.abs()
 
 
 # ---- GEMM ----------------------------------------------------------------------------------

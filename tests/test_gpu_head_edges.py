@@ -100,14 +100,16 @@ def test_dpt_tail_every_form_against_the_per_element_budget(mode, case):
 # =============================================================================================
 def _expected_conv256(mode, n, H, W, cin, cout, k, stride, up, ldx):
     """ovg_conv's dispatch condition (csrc/ovg_head.hip), restated: None = the 128-pixel kernel, else the GEMM columns per tile (256 or 128)
-    of the 256-pixel form: a 16-bit output, every GEMM column real, an even number of 32-channel k-stages, at least 16384 output pixels, two
-    images and the weights within 32-bit byte offsets."""
+    of the 256-pixel form: a 16-bit output, every GEMM column real, an even number of 32-channel k-stages, at least 16384 output pixels, the
+    images a tile of 256 consecutive output pixels can touch (255 // (OH OW) + 2: two from 256-pixel maps on) and the weights within 32-bit
+    byte offsets."""
     s = up if up > 1 else 1
     pd = k // 2
-    M = n * ((H + 2 * pd - k) // stride + 1) * ((W + 2 * pd - k) // stride + 1)
+    opix = ((H + 2 * pd - k) // stride + 1) * ((W + 2 * pd - k) // stride + 1)
+    M = n * opix
     cols = s * s * cout
     ok = (mode in ("bf16", "f16") and cols % 128 == 0 and cin % 32 == 0 and (k * k * (cin // 32)) % 2 == 0 and M >= 16384
-          and 2 * H * W * ldx * 2 < (1 << 32) - 65536 and cols * k * k * cin * 2 < (1 << 32))
+          and (255 // opix + 2) * H * W * ldx * 2 < (1 << 32) - 65536 and cols * k * k * cin * 2 < (1 << 32))
     return (256 if cols % 256 == 0 else 128) if ok else None
 
 
