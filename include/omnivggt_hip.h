@@ -80,7 +80,10 @@ extern "C" {
  *     + mesh simplification by vertex clustering on the grid of ovg_voxel_downsample, duplicate faces merged (ovg_mesh_simplify,
  *       ovg_mesh_simplify_workspace_bytes): added the same way
  *     + mesh cleaning: connected components and edge statistics, ordered sub-meshes, Laplacian / Taubin smoothing (ovg_mesh_topology,
- *       ovg_mesh_select, ovg_mesh_smooth and their *_workspace_bytes queries): added the same way */
+ *       ovg_mesh_select, ovg_mesh_smooth and their *_workspace_bytes queries): added the same way
+ *     + weighted, robust registration and moving a prediction into another frame, for stitching chunks of a long sequence
+ *       (ovg_align_wmoments, ovg_align_wmoments_workspace_bytes, ovg_align_wsolve, ovg_align_move_maps, ovg_align_move_cameras):
+ *       added the same way */
 #define OVG_ABI_VERSION 13
 
 enum { OVG_BF16 = 0, OVG_F16 = 1, OVG_F32 = 2,
@@ -1188,6 +1191,112 @@ typedef struct {
   float* out;
 } ovg_align_apply_params;
 int ovg_align_apply(const ovg_align_apply_params*, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Weighted, robust registration and moving a prediction into another frame (added under ABI 13): what stitching overlapping chunks
+ * of a long sequence needs -- the moments of ovg_align_moments with a weight per pair, optionally reweighted by the pair's residual
+ * under a previous transform (iteratively reweighted least squares with the Cauchy weight), the solve with the weight sum in the
+ * place of the pair count, and the maps and cameras of a chunk carried over by the fitted transform. Four entries that never read
+ * anything back. tests/stitch_twin.py restates the moments and the two moves operation for operation (byte-identical) and the solve
+ * by numpy's eigh and, independently, a weighted Umeyama fit from the points. All arithmetic in float64, every operation rounded on
+ * its own (no fused multiply-add).
+ *
+ * ovg_align_wmoments: source p [n][3] f32, target q [n][3] f32, pair i is (p[i], q[i]). weight f32 [n] or NULL (1), source_valid /
+ *   target_valid u8 [n] or NULL, transform f64 [4][4] row-major or NULL (the identity; only rows 0..2 are read), delta f64 [1] on the
+ *   device or NULL (1), delta_scale a host double, centre f64 [6] (cp, cq) or NULL (zeros), flags: OVG_WALIGN_CAUCHY.
+ *   Pair i is USED when its six coordinates are finite, its valid bytes are non-zero, its weight (if given) is finite and > 0 and,
+ *   with a transform, the three moved coordinates are finite. For a used pair
+ *     w = (double)weight[i], or 1;
+ *     m[r] = ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3], (x, y, z) = p widened -- ovg_align_apply's expression, kept in float64
+ *            (m = p without a transform);
+ *     e = q - m, r2 = (e0 e0 + e1 e1) + e2 e2;
+ *     with OVG_WALIGN_CAUCHY: delta = delta_scale * (delta ? *delta : 1); if delta is finite and > 0 and delta delta > 0 (a square
+ *            that underflows reweights nothing), h = 1 / (1 + r2 / (delta delta)), else h = 1 -- a perfect previous fit (rms 0)
+ *            must not zero every weight; without the flag h = 1;
+ *     W = w h;
+ *     a = p - cp, b = q - cq from the UNMOVED source: the sums describe the fit source -> target, never a step onto a moved source.
+ *   The 20 TERMS of a pair (OVG_WALIGN_SUMS):
+ *     [0..2] W a   [3..5] W b   [6 + 3 r + c] (W a_r) b_c   [15] W ((a0 a0 + a1 a1) + a2 a2)   [16] the same of b   [17] W r2
+ *     [18] W   [19] W W.
+ *   out_count int64 [1]: the used pairs; out_sums f64 [20]: the sums of the terms over them in the order of ovg_align_moments, steps
+ *   1 .. 4 word for word (thread, wave tree, tile slot, one-workgroup fold; OVG_ALIGN_TILE pairs per tile, OVG_ALIGN_THREADS
+ *   threads), so two calls give identical bytes, and with weight == NULL and no flag sums [0..17] and the count are
+ *   ovg_align_moments' bytes (W = 1 multiplies exactly). No used pair: count 0 and every sum +0.0.
+ *   ws: >= ovg_align_wmoments_workspace_bytes(n) bytes, 16-byte aligned: OVG_WALIGN_PARTIAL_BYTES = 176 bytes (the count and 20 sums,
+ *   padded) per tile, rounded up to 256; the query returns -1 unless 1 <= n < 2^31.
+ *   OVG_E_ARG: NULL params / source / target / ws / out_count / out_sums, n outside [1, 2^31), unknown flags, a NaN delta_scale, a
+ *   pointer that is not 4-byte (transform, delta, centre, out_count, out_sums: 8-byte) aligned, a misaligned or undersized
+ *   workspace. Nothing is written then.
+ *
+ * ovg_align_wsolve: ovg_align_solve's rule (its steps 1 .. 5) on sums [0..17] with N replaced by W = sums[18]: the transform that
+ *   minimises the sum of W_i |q_i - (s R p_i + t)|^2. One workgroup, one thread; count int64 [1], sums f64 [20], centre as for the
+ *   moments. DEGENERATE when count < 3 or not W > 0 (OVG_ALIGN_FEW_PAIRS), when one of the 20 sums or a centre entry is not finite
+ *   (OVG_ALIGN_NOT_FINITE), when var = sums[15] - |sums[0..2]|^2 / W is not above OVG_ALIGN_SPREAD_EPS sums[15]
+ *   (OVG_ALIGN_NO_SPREAD), or when the step has a non-finite entry (OVG_ALIGN_NOT_FINITE).
+ *   flags: OVG_ALIGN_SCALE as for ovg_align_solve; OVG_WALIGN_KEEP: a degenerate solve leaves transform AND out_scale untouched
+ *   instead of writing the identity and 1 -- a refit loop keeps its last good transform. There is no compose: the moments always
+ *   describe source -> target. transform f64 [4][4] <- [s R, t; 0 0 0 1].
+ *   Optional outputs (NULL: not written): out_scale f64 [1] (s); out_rms f64 [1] = sqrt(sums[17] / W), the weighted root mean square
+ *   residual under the transform the weights came from (0 unless W > 0 and W, sums[17] are finite); out_fit_rms f64 [1] =
+ *   sqrt(max(E, 0) / W), the weighted root mean square residual AFTER this fit, from the moments alone: with tr = the sum of
+ *   R[r][c] S[c][r] and vb = sums[16] - |sums[3..5]|^2 / W, E = vb - (tr tr) / var with OVG_ALIGN_SCALE and E = (var + vb) - 2 tr
+ *   without (0 for a degenerate solve or an E that is not finite; E is a difference of sums of the size of vb, so its absolute
+ *   error is a few ulps of vb); out_weight f64 [1] (W); out_count int64 [1]; out_status int32 [1].
+ *   OVG_E_ARG: NULL params / count / sums / transform, unknown flags, a pointer that is not 8-byte (out_status: 4-byte) aligned.
+ *
+ * ovg_align_move_maps: one pass over the n pixels of a chunk's maps, one thread per pixel, each of four map pairs optional (NULL in,
+ *   NULL out): out_points[i] = ovg_align_apply's rule for points [n][3] f32 under transform f64 [4][4]; out_depth[i] =
+ *   f32((double)depth[i] * s) with s = *scale (f64 [1] on the device); out_points_conf / out_depth_conf [n] f32 are copies. An
+ *   output may be its own input.
+ *   OVG_E_ARG: NULL params, n outside [1, 2^31), no map at all, an input without its output or the reverse, points without
+ *   transform, depth without scale, a pointer that is not 4-byte (transform, scale: 8-byte) aligned.
+ *
+ * ovg_align_move_cameras: one thread per camera. extrinsic f32 [views][3][4] = [Rv | tv], world-to-camera in the chunk's frame; M =
+ *   transform f64 [4][4] = [s Rg, tM] the similarity that moved the chunk's points (x' = M x); s = *scale (f64 [1] on the device).
+ *     Rg[r][c] = M[r][c] / s;  A[i][j] = (Rv[i][0] Rg[j][0] + Rv[i][1] Rg[j][1]) + Rv[i][2] Rg[j][2];
+ *     t'[i] = s tv[i] - ((A[i][0] M[0][3] + A[i][1] M[1][3]) + A[i][2] M[2][3]);  out [views][3][4] = [A | t'] rounded to f32 once.
+ *   [A | t'] is the camera that sees the moved points at s times the old depth: x = Rg^T (x' - tM) / s, so s (Rv x + tv) =
+ *   Rv Rg^T (x' - tM) + s tv = A x' + t'. out == extrinsic is allowed.
+ *   OVG_E_ARG: NULL params / extrinsic / transform / scale / out, views outside [1, 2^31), a pointer that is not 4-byte (transform,
+ *   scale: 8-byte) aligned.
+ * ------------------------------------------------------------------ */
+enum { OVG_WALIGN_SUMS = 20, OVG_WALIGN_PARTIAL_BYTES = 176 };
+enum { OVG_WALIGN_CAUCHY = 1 };                                                      /* ovg_align_wmoments_params.flags */
+enum { OVG_WALIGN_KEEP = 4 };                                                        /* ovg_align_wsolve_params.flags, with OVG_ALIGN_SCALE */
+typedef struct {
+  const float* source; const float* target; const float* weight;
+  const uint8_t* source_valid; const uint8_t* target_valid;
+  const double* transform; const double* delta; const double* centre;
+  double delta_scale;
+  int64_t n; int64_t flags;
+  void* ws; int64_t ws_bytes;
+  int64_t* out_count; double* out_sums;
+} ovg_align_wmoments_params;
+int64_t ovg_align_wmoments_workspace_bytes(int64_t n);
+int ovg_align_wmoments(const ovg_align_wmoments_params*, void* stream);
+
+typedef struct {
+  const int64_t* count; const double* sums; const double* centre;
+  int64_t flags;
+  double* transform;
+  double* out_scale; double* out_rms; double* out_fit_rms; double* out_weight; int64_t* out_count; int32_t* out_status;
+} ovg_align_wsolve_params;
+int ovg_align_wsolve(const ovg_align_wsolve_params*, void* stream);
+
+typedef struct {
+  const float* points; const float* depth; const float* points_conf; const float* depth_conf;
+  const double* transform; const double* scale;
+  int64_t n;
+  float* out_points; float* out_depth; float* out_points_conf; float* out_depth_conf;
+} ovg_align_move_maps_params;
+int ovg_align_move_maps(const ovg_align_move_maps_params*, void* stream);
+
+typedef struct {
+  const float* extrinsic; const double* transform; const double* scale;
+  int64_t views;
+  float* out;
+} ovg_align_move_cameras_params;
+int ovg_align_move_cameras(const ovg_align_move_cameras_params*, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Depth evaluation (added under ABI 13): how good a predicted depth map is against ground truth -- AbsRel, delta < 1.25 and their

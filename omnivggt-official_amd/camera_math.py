@@ -49,7 +49,7 @@ def rotation_to_quaternion(R):
     cand = torch.stack(rows, dim=-2) / (2.0 * mag[..., None].clamp(min=0.1))
     pick = mag.argmax(dim=-1)
     q = torch.gather(cand, -2, pick[..., None, None].expand(pick.shape + (1, 4))).squeeze(-2)
-    q = q[..., [1, 2, 3, 0]]
+    q = torch.cat([q[..., 1:], q[..., :1]], dim=-1)          # wxyz -> xyzw, without an index tensor (on a device that is a host copy)
     return torch.where(q[..., 3:4] < 0, -q, q)
 
 

@@ -319,6 +319,31 @@ class AlignApplyParams(C.Structure):
     _fields_ = [("points", vp), ("transform", vp), ("n", i64), ("out", vp)]
 
 
+WALIGN_SUMS, WALIGN_PARTIAL_BYTES = 20, 176                  # ovg_align_wmoments: the 18 sums weighted, then W and W^2
+WALIGN_CAUCHY = 1                                            # ovg_align_wmoments_params.flags
+WALIGN_KEEP = 4                                              # ovg_align_wsolve_params.flags, next to ALIGN_SCALE
+
+
+class AlignWMomentsParams(C.Structure):
+    _fields_ = [("source", vp), ("target", vp), ("weight", vp), ("source_valid", vp), ("target_valid", vp), ("transform", vp),
+                ("delta", vp), ("centre", vp), ("delta_scale", C.c_double), ("n", i64), ("flags", i64), ("ws", vp), ("ws_bytes", i64),
+                ("out_count", vp), ("out_sums", vp)]
+
+
+class AlignWSolveParams(C.Structure):
+    _fields_ = [("count", vp), ("sums", vp), ("centre", vp), ("flags", i64), ("transform", vp), ("out_scale", vp), ("out_rms", vp),
+                ("out_fit_rms", vp), ("out_weight", vp), ("out_count", vp), ("out_status", vp)]
+
+
+class AlignMoveMapsParams(C.Structure):
+    _fields_ = [("points", vp), ("depth", vp), ("points_conf", vp), ("depth_conf", vp), ("transform", vp), ("scale", vp), ("n", i64),
+                ("out_points", vp), ("out_depth", vp), ("out_points_conf", vp), ("out_depth_conf", vp)]
+
+
+class AlignMoveCamerasParams(C.Structure):
+    _fields_ = [("extrinsic", vp), ("transform", vp), ("scale", vp), ("views", i64), ("out", vp)]
+
+
 DEPTHEVAL_THREADS, DEPTHEVAL_TILE, DEPTHEVAL_SUMS, DEPTHEVAL_COUNTS, DEPTHEVAL_PARTIAL_BYTES = 256, 1024, 5, 4, 80   # the order of ovg_deptheval_sums
 DEPTHEVAL_MAX_GROUPS, DEPTHEVAL_CHUNK, DEPTHEVAL_MEDIAN_GROUP_BYTES = 4096, 16384, 4128
 DEPTHEVAL_MOMENTS, DEPTHEVAL_METRICS = 0, 1                  # ovg_deptheval_sums_params.mode
@@ -533,6 +558,11 @@ SYMBOLS = {
     "ovg_align_workspace_bytes": (i64, [i64]),
     "ovg_align_solve": (i32, [C.POINTER(AlignSolveParams), vp]),
     "ovg_align_apply": (i32, [C.POINTER(AlignApplyParams), vp]),
+    "ovg_align_wmoments": (i32, [C.POINTER(AlignWMomentsParams), vp]),
+    "ovg_align_wmoments_workspace_bytes": (i64, [i64]),
+    "ovg_align_wsolve": (i32, [C.POINTER(AlignWSolveParams), vp]),
+    "ovg_align_move_maps": (i32, [C.POINTER(AlignMoveMapsParams), vp]),
+    "ovg_align_move_cameras": (i32, [C.POINTER(AlignMoveCamerasParams), vp]),
     "ovg_plane_hypotheses": (i32, [C.POINTER(PlaneHypothesesParams), vp]),
     "ovg_plane_score": (i32, [C.POINTER(PlaneScoreParams), vp]),
     "ovg_plane_select": (i32, [C.POINTER(PlaneSelectParams), vp]),

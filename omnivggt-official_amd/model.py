@@ -283,3 +283,36 @@ class OmniVGGT(nn.Module, _HubMixin):
                         out[key] = shard.gather_views(out[key].contiguous(), parts)
         out["images"] = images
         return out
+
+    def forward_chunked(self, images, extrinsics=None, intrinsics=None, depth=None, mask=None, depth_gt_index=None, camera_gt_index=None,
+                        chunk_size=32, overlap=4, **stitch_kw):
+        """`forward` for sequences too long for one call: the views run as overlapping chunks (postprocess.chunk_plan: chunk_size views,
+        consecutive chunks share `overlap`), each chunk under no_grad as a `forward` of its own on the slices of every per-view tensor
+        (dimension 1) with the two index lists mapped to the chunk's local indices, and the chunks' prediction dicts -- the tokens die
+        with each call -- are stitched into the first chunk's frame (postprocess.stitch_predictions, which takes **stitch_kw and whose
+        dict this returns: the familiar keys for all S views plus extrinsic, intrinsic, chunks, chunk_transforms). A sequence of at
+        most chunk_size views is one `forward`: its own dict, byte for byte.
+        One batch element only (B = 1, or 4-D images): ValueError otherwise. As in the reference, the FIRST selected camera of a call
+        defines the normalisation of the ground-truth cameras (the selected cameras are made relative to the first
+        of them and scaled by their mean distance), so every chunk normalises by its own first selected camera; a chunk whose local
+        view 0 has no ground-truth camera while other views do is passed through as given."""
+        from . import postprocess
+        if images.dim() == 4:
+            images = images.unsqueeze(0)
+        if images.dim() != 5 or images.shape[0] != 1:
+            raise ValueError("forward_chunked takes one sequence: images (S, 3, H, W) or (1, S, 3, H, W), got %r" % (tuple(images.shape),))
+        S = int(images.shape[1])
+        plan = postprocess.chunk_plan(S, chunk_size, overlap)
+        per_view = dict(extrinsics=extrinsics, intrinsics=intrinsics, depth=depth, mask=mask)
+        for name, t in per_view.items():
+            if t is not None and (t.dim() < 2 or t.shape[0] != 1 or t.shape[1] != S):
+                raise ValueError("forward_chunked: %s must be (1, %d, ...), got %r" % (name, S, tuple(t.shape)))
+        if len(plan) == 1:
+            return self.forward(images, extrinsics, intrinsics, depth, mask, depth_gt_index, camera_gt_index)
+        chunks = []
+        with torch.no_grad():
+            for a, b in plan:
+                part = {name: None if t is None else t[:, a:b] for name, t in per_view.items()}
+                chunks.append(self.forward(images[:, a:b], depth_gt_index=postprocess.chunk_indices(depth_gt_index, a, b),
+                                           camera_gt_index=postprocess.chunk_indices(camera_gt_index, a, b), **part))
+        return postprocess.stitch_predictions(chunks, plan, **stitch_kw)

@@ -1168,6 +1168,121 @@ def align_apply(points, transform, out=None):
     return out
 
 
+def align_wmoments_workspace_bytes(n):
+    return _ws_query("ovg_align_wmoments_workspace_bytes", n=n)
+
+
+def align_wmoments(source, target, weight=None, source_valid=None, target_valid=None, transform=None, delta=None, delta_scale=1.0,
+                   cauchy=False, centre=None, ws=None, count=None, sums=None):
+    """ovg_align_wmoments on contiguous device tensors: source, target f32 [n, 3] (pair i <-> i), weight f32 [n] or None, source_valid /
+    target_valid u8 [n] or None, transform f64 [4, 4] or None, centre f64 [6] or None. cauchy=True reweights every pair by
+    1 / (1 + r^2 / delta^2), r its residual under `transform`, delta = delta_scale (a host float, not NaN) times the device scalar
+    `delta` (f64 [1], or None: 1); a delta that is not finite and positive reweights nothing. -> (count int64 [1], sums f64 [20])
+    (allocated when None): the used pairs and the weighted sums of include/omnivggt_hip.h in its fixed order, so two calls give
+    identical bytes. ws: an optional uint8 device tensor of at least align_wmoments_workspace_bytes(n) bytes. Nothing is read back."""
+    what = "align_wmoments"
+    n = _points(what, source, "source", 1)
+    _tensor(what, target, "target", _F32, (n, 3))
+    _tensor(what, weight, "weight", _F32, (n,), optional=True)
+    _tensor(what, source_valid, "source_valid", _U8, (n,), optional=True)
+    _tensor(what, target_valid, "target_valid", _U8, (n,), optional=True)
+    _tensor(what, transform, "transform", _F64, (4, 4), optional=True)
+    _tensor(what, delta, "delta", _F64, (1,), optional=True)
+    delta_scale = _number(what, "delta_scale", delta_scale, f32=False)
+    _tensor(what, centre, "centre", _F64, (6,), optional=True)
+    _tensor(what, count, "count", _I64, (1,), optional=True)
+    _tensor(what, sums, "sums", _F64, (L.WALIGN_SUMS,), optional=True)
+    _tensor(what, ws, "ws", _U8, optional=True)
+    _chk_dev(source, target, weight, source_valid, target_valid, transform, delta, centre, ws, count, sums)
+    ws = _workspace(ws, align_wmoments_workspace_bytes(n), source.device)
+    count = _out(what, count, "count", _I64, (1,), source.device)
+    sums = _out(what, sums, "sums", _F64, (L.WALIGN_SUMS,), source.device)
+    p = L.AlignWMomentsParams()
+    p.source, p.target, p.weight, p.source_valid, p.target_valid = L.ptr(source), L.ptr(target), L.ptr(weight), L.ptr(source_valid), L.ptr(target_valid)
+    p.transform, p.delta, p.centre, p.delta_scale, p.n = L.ptr(transform), L.ptr(delta), L.ptr(centre), delta_scale, n
+    p.flags = L.WALIGN_CAUCHY if cauchy else 0
+    p.ws, p.ws_bytes, p.out_count, p.out_sums = L.ptr(ws), nbytes(ws), L.ptr(count), L.ptr(sums)
+    L.call("ovg_align_wmoments", p, _stream())
+    return count, sums
+
+
+def align_wsolve(count, sums, transform, centre=None, with_scale=True, keep=False, scale=None, rms=None, fit_rms=None, weight=None,
+                 out_count=None, status=None):
+    """ovg_align_wsolve on device tensors: the weighted moments (count int64 [1], sums f64 [20], and the centre f64 [6] they were computed
+    with, or None) -> the weighted least-squares similarity (with_scale) or rigid transform q ~ s R p + t, written to transform f64
+    [4, 4]. keep=True: a degenerate solve leaves transform and scale as they are instead of writing the identity and 1. scale, rms
+    (weighted, under the transform the weights came from), fit_rms (weighted, after this fit), weight (the weight sum), all f64 [1],
+    out_count int64 [1] and status int32 [1] (the L.ALIGN_* bits) are written when given. -> transform. Nothing is read back."""
+    what = "align_wsolve"
+    _tensor(what, count, "count", _I64, (1,))
+    _tensor(what, sums, "sums", _F64, (L.WALIGN_SUMS,))
+    _tensor(what, transform, "transform", _F64, (4, 4))
+    _tensor(what, centre, "centre", _F64, (6,), optional=True)
+    for t, name in ((scale, "scale"), (rms, "rms"), (fit_rms, "fit_rms"), (weight, "weight")):
+        _tensor(what, t, name, _F64, (1,), optional=True)
+    _tensor(what, out_count, "out_count", _I64, (1,), optional=True)
+    _tensor(what, status, "status", _I32, (1,), optional=True)
+    _chk_dev(count, sums, transform, centre, scale, rms, fit_rms, weight, out_count, status)
+    p = L.AlignWSolveParams()
+    p.count, p.sums, p.centre, p.transform = L.ptr(count), L.ptr(sums), L.ptr(centre), L.ptr(transform)
+    p.flags = (L.ALIGN_SCALE if with_scale else 0) | (L.WALIGN_KEEP if keep else 0)
+    p.out_scale, p.out_rms, p.out_fit_rms, p.out_weight = L.ptr(scale), L.ptr(rms), L.ptr(fit_rms), L.ptr(weight)
+    p.out_count, p.out_status = L.ptr(out_count), L.ptr(status)
+    L.call("ovg_align_wsolve", p, _stream())
+    return transform
+
+
+def align_move_maps(n, transform=None, scale=None, points=None, depth=None, points_conf=None, depth_conf=None, out_points=None,
+                    out_depth=None, out_points_conf=None, out_depth_conf=None):
+    """ovg_align_move_maps on contiguous device tensors of n pixels (any shape with that many elements: [n], [V, H, W], [V, H, W, 1];
+    points 3 n), every map optional (at least one): points f32 -> out_points = f32(transform p) as align_apply (transform f64
+    [4, 4]); depth f32 -> out_depth = f32(depth * scale) (scale f64 [1] on the device); points_conf / depth_conf f32 are copied.
+    Outputs are allocated in the input's shape when None and may be their own inputs.
+    -> (out_points, out_depth, out_points_conf, out_depth_conf), None for an absent map. Nothing is read back."""
+    what = "align_move_maps"
+    n = _int_in(what, "n", n, 1, 1 << 31)
+    maps = ((points, out_points, "points", (n, 3)), (depth, out_depth, "depth", (n,)), (points_conf, out_points_conf, "points_conf", (n,)),
+            (depth_conf, out_depth_conf, "depth_conf", (n,)))
+    if all(m[0] is None for m in maps):
+        raise L.OvgError("%s: at least one of points, depth, points_conf, depth_conf is needed" % what)
+    for t, o, name, shape in maps:                                           # maps come as [V, H, W(, 3)] or flat: the element count is the rule
+        _tensor(what, t, name, _F32, numel=math.prod(shape), optional=True)
+        _tensor(what, o, "out_" + name, _F32, numel=math.prod(shape), optional=True)
+        if t is None and o is not None:
+            raise L.OvgError("%s: out_%s without %s" % (what, name, name))
+    _tensor(what, transform, "transform", _F64, (4, 4), optional=points is None)
+    _tensor(what, scale, "scale", _F64, (1,), optional=depth is None)
+    _chk_dev(transform, scale, *(t for m in maps for t in m[:2]))
+    dev = next(m[0] for m in maps if m[0] is not None).device
+    outs = [None if t is None else _out(what, o, "out_" + name, _F32, tuple(t.shape), dev) for t, o, name, shape in maps]
+    p = L.AlignMoveMapsParams()
+    p.points, p.depth, p.points_conf, p.depth_conf = L.ptr(points), L.ptr(depth), L.ptr(points_conf), L.ptr(depth_conf)
+    p.transform, p.scale, p.n = L.ptr(transform), L.ptr(scale), n
+    p.out_points, p.out_depth, p.out_points_conf, p.out_depth_conf = (L.ptr(o) for o in outs)
+    L.call("ovg_align_move_maps", p, _stream())
+    return tuple(outs)
+
+
+def align_move_cameras(extrinsic, transform, scale, out=None):
+    """ovg_align_move_cameras on contiguous device tensors: extrinsic f32 [V, 3, 4] (world-to-camera in the frame the points were in),
+    transform f64 [4, 4] = [s R, t] that moved the points, scale f64 [1] = s -> out f32 [V, 3, 4] (allocated when None; may be
+    `extrinsic` itself): the cameras that see the moved points at s times the old depth. Nothing is read back."""
+    what = "align_move_cameras"
+    _tensor(what, extrinsic, "extrinsic", _F32)
+    if extrinsic.dim() != 3 or tuple(extrinsic.shape[1:]) != (3, 4) or not 1 <= extrinsic.shape[0] < 1 << 31:
+        raise L.OvgError("%s: extrinsic must be a contiguous float32 tensor [V, 3, 4], V >= 1" % what)
+    V = int(extrinsic.shape[0])
+    _tensor(what, transform, "transform", _F64, (4, 4))
+    _tensor(what, scale, "scale", _F64, (1,))
+    _tensor(what, out, "out", _F32, (V, 3, 4), optional=True)
+    _chk_dev(extrinsic, transform, scale, out)
+    out = _out(what, out, "out", _F32, (V, 3, 4), extrinsic.device)
+    p = L.AlignMoveCamerasParams()
+    p.extrinsic, p.transform, p.scale, p.views, p.out = L.ptr(extrinsic), L.ptr(transform), L.ptr(scale), V, L.ptr(out)
+    L.call("ovg_align_move_cameras", p, _stream())
+    return out
+
+
 def deptheval_median_workspace_bytes(groups, n):
     return _ws_query("ovg_deptheval_median_workspace_bytes", groups=groups, n=n)
 
